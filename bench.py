@@ -12,9 +12,16 @@ dim=100k, nnz=100, cosine theta=0.8" (the configuration the metric is quoted on)
     python bench.py --gpus N ...                  (typed without a launcher: starts the line above as a child, relays its line)
     python bench.py --gpus N --engine group ...   (ONE process: apss_group, the sharded index + RCCL exchange behind the C ABI)
 
-N > 1 times BOTH layouts of SURVEY.md 8(e), K steps each, same barriers: the contract's (term-range shards across the N
-GPUs, RCCL all-gather of candidate lists + all-reduce of partial scores: WriteWorkerActor.scala:164-183 turned into
-range shards) is `value`; candidate-range shards (no data-path collective) are the `candidate_range_layout` row.
+N > 1 times the contract's layout (term-range shards across the N GPUs, RCCL all-gather of candidate lists + all-reduce of
+partial scores: WriteWorkerActor.scala:164-183 turned into range shards) as `value`.
+
+A plain run does only what the headline needs: set up, warm up, time K steps, print the line.  --full adds everything else the
+line used to carry, each measured in runs of its own: the CPU baseline, the two-directional and the exact-accumulate siblings
+at N = 1, and at N > 1 the other layouts of SURVEY.md 8(e) (candidate-range shards, no data-path collective: the
+`candidate_range_layout` row; from N = 4 on the 2 x N/2 grid), K steps each, same barriers.
+--dump-outputs DIR writes the result pairs of the last timed step (one process: N = 1 or --engine group) as DIR/query_ids.npy,
+DIR/candidate_ids.npy (float64) and DIR/scores.npy (float32), sorted by (query, candidate); a fixed hash-chosen sample of
+them when they exceed 64 MB.
 
 Prints ONE JSON line (rank 0).  A rank that stalls ends the process with exit code 3 (watchdog), never 0.
 """
@@ -67,7 +74,16 @@ def parse():
                     "behind the C ABI (apss_group: member threads + RCCL below the boundary)")
     ap.add_argument("--share-device", action="store_true", help="--engine group rehearsal on a one-GPU box: every member on GPU 0 "
                                                                 "(exchange by device-to-device copies instead of RCCL)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline, the "
+                                                        "two-directional and exact-accumulate siblings (N = 1), the other layouts (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the result pairs of the last timed step as DIR/*.npy "
+                                                                         "(N = 1 or --engine group)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and (a.solo or (a.gpus > 1 and a.engine != "group")):
+        ap.error("--dump-outputs needs a one-process run: --gpus 1 or --engine group (not --solo, not one process per GPU)")
+    return a
 
 
 class Watchdog:
@@ -134,6 +150,37 @@ def cpu_baseline(cfg, rp, idx, val, budget_s):
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_BYTES_PER_PAIR = 8 + 8 + 4  # query id, candidate id (float64), score (float32)
+
+
+def output_arrays(q, c, s, limit_bytes=DUMP_LIMIT_BYTES):
+    """What --dump-outputs writes: the result pairs (q, c, s) as a caller fetches them, sorted by (query, candidate), ids as
+    float64 (exact below 2^53), scores float32.  Beyond the size limit a fixed sample: the pairs whose (query, candidate)
+    hash lowest -- a pair's membership depends on the pair alone, so two builds with the same result set dump the same pairs."""
+    q, c, s = np.asarray(q, np.int64), np.asarray(c, np.int64), np.asarray(s, np.float32)
+    keep = max(0, (limit_bytes - 3 * 4096) // DUMP_BYTES_PER_PAIR)  # (room for the three .npy headers)
+    if q.size > keep:
+        h = (q.astype(np.uint64) << np.uint64(32)) ^ c.astype(np.uint64)  # splitmix64 finaliser of the pair
+        h ^= h >> np.uint64(30)
+        h *= np.uint64(0xBF58476D1CE4E5B9)
+        h ^= h >> np.uint64(27)
+        h *= np.uint64(0x94D049BB133111EB)
+        h ^= h >> np.uint64(31)
+        sel = np.lexsort((c, q, h))[:keep]  # ties of h broken by the pair itself
+        q, c, s = q[sel], c[sel], s[sel]
+    order = np.lexsort((c, q))
+    return {"query_ids": q[order].astype(np.float64), "candidate_ids": c[order].astype(np.float64), "scores": s[order]}
+
+
+def write_outputs(dirname, q, c, s):
+    os.makedirs(dirname, exist_ok=True)
+    arrays = output_arrays(q, c, s)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    sys.stderr.write("[bench] %d of %d result pairs written to %s\n" % (arrays["scores"].size, len(s), dirname))
+
+
 PROBE_TRAFFIC = os.path.join(ROOT, "profiles", "r04_probe_traffic.json")
 
 
@@ -178,7 +225,7 @@ def single_gpu(a, cfg, rp, idx, val, d_arrays, dev, local_rank, sync, wd):
     d_ids = torch.arange(n, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()  # the library runs on its own stream
 
-    def run(flags, steps, warmup):
+    def run(flags, steps, warmup, dump=None):
         ix = ApssIndex(cfg["dim"], cfg["theta"], device=local_rank, tile_rows=a.tile_rows, capacity_rows=n,
                        capacity_nnz=d_idx.numel(), flags=flags, head_terms=a.head_terms)
 
@@ -196,11 +243,14 @@ def single_gpu(a, cfg, rp, idx, val, d_arrays, dev, local_rank, sync, wd):
             per.append(ix.stats())
         sync()
         dt = time.perf_counter() - t0
+        if dump:
+            wd.phase = "writing outputs"
+            write_outputs(dump, *ix.fetch())  # the last timed step's result pairs, as a caller fetches them
         ix.close()
         return dt, n_pairs, per
 
     wd.phase = "timed steps"
-    dt, n_pairs, per = run(0, a.steps, a.warmup)
+    dt, n_pairs, per = run(0, a.steps, a.warmup, a.dump_outputs)
     st = per[-1]
     mean = lambda k: float(np.mean([s[k] for s in per]))  # noqa: E731
     sec_per_step = dt / a.steps
@@ -286,7 +336,7 @@ def single_gpu(a, cfg, rp, idx, val, d_arrays, dev, local_rank, sync, wd):
             out["roofline"], out["roofline_dense_head"] = sparse_roof, head_roof
     else:
         out["roofline"] = sparse_roof
-    if st["symmetric"] and not a.no_exact_row and not a.no_two_directional_row:
+    if a.full and st["symmetric"] and not a.no_exact_row and not a.no_two_directional_row:
         # the same join with every pair probed in BOTH directions, as the reference does it (APSS_FLAG_NO_SYMMETRY): same result
         # list, measured beside the headline so that the line carries both
         wd.phase = "two-directional sibling"
@@ -307,7 +357,7 @@ def single_gpu(a, cfg, rp, idx, val, d_arrays, dev, local_rank, sync, wd):
         }
     # the fp32-everywhere sibling: single-pass kernel with exact u32 / fp32 accumulators, 8-B postings (what `frac`
     # means literally); measured in the same run so that the line carries both
-    if not a.no_exact_row and not hybrid:
+    if a.full and not a.no_exact_row and not hybrid:
         wd.phase = "exact-accumulate sibling"
         dt2, n2, per2 = run(_lib.FLAG_EXACT_ACCUM, max(1, min(2, a.steps)), 1)
         s2 = per2[-1]
@@ -423,7 +473,7 @@ def multi_gpu(a, cfg, rp, idx, val, dev, comm_dev, rank, world, local_rank, sync
     extra = {"layout": "term-range shards (the contract: BASELINE.json configs[3], SURVEY.md 8e)", "backend": a.backend,
              "exchange": head["exchange"], "shard_touched_pairs_sum": head["shard_touched_pairs_sum"],
              "collectives": head["collectives"]}
-    if not a.no_comparison_row and T != 1:
+    if a.full and not a.no_comparison_row and T != 1:
         comp = timed(1, "comparison layout: candidate ranges")
         extra["candidate_range_layout"] = comp
         # (same set up to the pairs within an ulp of theta: a row-range cell reports a cross pair in both directions with ONE fp32
@@ -496,6 +546,9 @@ def group_gpu(a, cfg, rp, idx, val, wd):
         n_pairs = step()
         per.append(g.stats())
     dt = time.perf_counter() - t0  # (the group call returns when every member has finished: nothing is in flight)
+    if a.dump_outputs:
+        wd.phase = "group: writing outputs"
+        write_outputs(a.dump_outputs, *g.fetch())
     st = per[-1]
     members = [g.member_stats(i) for i in range(N)]
     g.close()
@@ -563,6 +616,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     group_engine = world == 1 and a.gpus > 1 and a.engine == "group"
+    if a.dump_outputs and world > 1:
+        sys.exit("bench.py: --dump-outputs needs a one-process run (--gpus 1 or --engine group), not %d ranks" % world)
     if world == 1 and a.gpus > 1 and not group_engine:
         # typed without a launcher: the ranks are started here, as a child process, before anything touches the GPU
         sys.exit(relay_child(a))
@@ -689,7 +744,7 @@ def main():
         if sym:
             out["value_two_directional"] = sym["two_directional"]["value"]
             out["ms_per_step_two_directional"] = sym["two_directional"]["ms_per_step"]
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             wd.phase = "cpu baseline"
             out["cpu_baseline"] = cpu_baseline(cfg, rp, idx, val, a.cpu_seconds if (world == 1 and not group_engine) else min(a.cpu_seconds, 6.0))
         print(json.dumps(out), flush=True)

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 W=${1:-c3}; shift
 OUT=gpurun_out/r03/$W
 mkdir -p $OUT
-B="python3 bench.py --workload $W $@"
+B="python3 bench.py --full --workload $W $@"
 $B --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 # (the traced and counted runs skip the two-directional sibling: its launches carry the headline kernel's name)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B --steps 3 --warmup 1 --no-cpu-baseline --no-two-directional-row > $OUT/trace.log 2>&1; echo "trace rc=$?"

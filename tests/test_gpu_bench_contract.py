@@ -4,7 +4,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from apss import synth
+from helpers import BAND, TOL, assert_same_pairs, to_map
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +24,7 @@ def _one_line(out):
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "60000", "--steps", "2", "--warmup", "1",
-                          "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_line(out)
     for k in DRIVER_KEYS:
@@ -60,7 +64,7 @@ def test_bench_json_contract():
 def test_bench_skewed_workload_reports_an_mfma_roofline():
     """C3 with Zipf(1) terms at reduced N: the dense-head block takes the frequent terms, the line names both kernels"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c3z1", "--n", "50000", "--steps", "2",
-                          "--warmup", "1", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _one_line(out)
     for k in DRIVER_KEYS:
@@ -90,7 +94,7 @@ def test_bench_two_ranks_report_both_layouts():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "40000",
-                          "--steps", "2", "--warmup", "1", "--backend", "gloo", "--cpu-seconds", "1"],
+                          "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
@@ -113,7 +117,7 @@ def test_bench_two_ranks_skewed_terms_take_the_dense_head_block():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c3z1",
-                          "--rows", "50000", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--cpu-seconds", "1"],
+                          "--rows", "50000", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
@@ -134,7 +138,7 @@ def test_bench_four_ranks_report_three_layouts():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
                           "127.0.0.1", "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--rows", "40000",
-                          "--steps", "2", "--warmup", "1", "--backend", "gloo", "--cpu-seconds", "1"],
+                          "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
@@ -150,7 +154,7 @@ def test_bench_gpus_2_typed_without_a_launcher():
     the line comes back with n_gpus = 2 and rc 0 (gloo rehearsal: both ranks drive GPU 0)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", "40000",
-                          "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
     for k in DRIVER_KEYS:
@@ -159,15 +163,16 @@ def test_bench_gpus_2_typed_without_a_launcher():
     assert d["value"] <= d["value_reference_equivalent"]
 
 
-def test_bench_group_engine_in_one_process():
+def test_bench_group_engine_in_one_process(tmp_path):
     """--engine group: N members of ONE apss_group (the term-sharded index behind the C ABI, exchange below the boundary) in
     one process; on the one-GPU box the members share GPU 0 (rehearsal: exchange by copies).  Same result set as one GPU."""
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "60000", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-exact-row", "--no-two-directional-row"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-cpu-baseline", "--no-exact-row", "--no-two-directional-row", "--dump-outputs", str(tmp_path / "one")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = _one_line(one)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--engine", "group", "--share-device", "--rows", "60000",
-                          "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1", "--dump-outputs", str(tmp_path / "group")], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _one_line(out)
     for k in DRIVER_KEYS:
@@ -178,3 +183,33 @@ def test_bench_group_engine_in_one_process():
     assert len(g["term_cuts"]) == 5 and g["union"] >= d["result_pairs_per_step"] > 0 and g["all_reduce_bytes"] == 4 * g["union"]
     assert d["result_pairs_per_step"] == d1["result_pairs_per_step"] and d["candidate_pairs_per_step"] == d1["candidate_pairs_per_step"]
     assert d["posting_visits_per_step"] == d1["posting_visits_per_step"]
+    # the dumped result pairs of the last timed step: the group's are the one-GPU handle's (each within BAND / TOL of the exact
+    # scores, so within twice that of each other)
+    assert_same_pairs(_dumped(tmp_path / "group"), _dumped(tmp_path / "one"), 0.8, band=2 * BAND, tol=2 * TOL)
+
+
+def _dumped(d):
+    q, c, s = (np.load(os.path.join(str(d), name + ".npy")) for name in ("query_ids", "candidate_ids", "scores"))
+    assert q.dtype == np.float64 and c.dtype == np.float64 and s.dtype == np.float32 and q.size == c.size == s.size
+    return to_map(q, c, s)
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, oracle):
+    """a plain run (no --full) times the steps it is asked for and prints the headline without the runs of its own that
+    --full adds; --dump-outputs writes the last timed step's result pairs, sorted, which are the oracle's pairs"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "60000", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _one_line(out)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 1e9 and d["dtype"] == "u16+f32"
+    assert "cpu_baseline" not in d and "symmetric_join" not in d and "exact_accum" not in d["roofline"]
+    got = _dumped(tmp_path)
+    assert len(got) == d["result_pairs_per_step"] > 100
+    q = np.load(os.path.join(str(tmp_path), "query_ids.npy"))
+    c = np.load(os.path.join(str(tmp_path), "candidate_ids.npy"))
+    assert np.all((np.diff(q) > 0) | ((np.diff(q) == 0) & (np.diff(c) > 0)))  # sorted by (query, candidate), no repeats
+    cfg = synth.CONFIGS["c3"]
+    rp, idx, val = synth.make_vectors(60000, cfg["dim"], cfg["nnz"], cfg["zipf_s"], cfg["seed"])
+    assert_same_pairs(got, to_map(*oracle.selfjoin_pairs(cfg["dim"], cfg["theta"], rp, idx, val)), cfg["theta"])
