@@ -17,13 +17,14 @@ SYMBOLS = [
     "apss_insert_and_query", "apss_self_join", "apss_result_count", "apss_fetch_results", "apss_size",
     "apss_stats_get", "apss_insert_dev", "apss_query_dev", "apss_insert_and_query_dev", "apss_clear",
     "apss_results_dev", "apss_results_copy_dev", "apss_partial_scores_dev", "apss_set_head_terms", "apss_get_head_terms", "apss_set_head_fold",
-    "apss_ext_ids_dev",
+    "apss_ext_ids_dev", "apss_get_store_dev", "apss_insert_stored_dev",
     # the term-sharded index of one node behind one object (csrc/apss_group.hip)
     "apss_group_create", "apss_group_destroy", "apss_group_last_error", "apss_group_set_term_cuts", "apss_group_insert",
     "apss_group_query", "apss_group_insert_and_query", "apss_group_insert_and_query_dev", "apss_group_clear",
     "apss_group_result_count", "apss_group_fetch_results", "apss_group_stats_get", "apss_group_member_stats",
+    "apss_group_relayout", "apss_group_layout_get",
 ]
-GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL = 1, 2
+GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
 EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
 GROUP_MAX_MEMBERS = 64
 DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
@@ -58,6 +59,13 @@ class GroupStats(C.Structure):
                 ("all_reduce_bytes", C.c_int64), ("member_ms_max", C.c_double), ("probe_ms_max", C.c_double),
                 ("build_ms_max", C.c_double), ("head_ms_max", C.c_double), ("exchange_ms", C.c_double),
                 ("partial_ms_max", C.c_double), ("total_ms", C.c_double), ("term_cuts", C.c_int32 * (GROUP_MAX_MEMBERS + 1))]
+
+
+class GroupLayout(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_members", C.c_int32), ("layout_rows", C.c_int64), ("next_eval_rows", C.c_int64),
+                ("evaluations", C.c_int64), ("relayouts", C.c_int64), ("last_relayout_ms", C.c_double),
+                ("total_relayout_ms", C.c_double), ("relayout_bytes", C.c_int64), ("head_terms", C.c_int32),
+                ("term_cuts", C.c_int32 * (GROUP_MAX_MEMBERS + 1)), ("dfsq", C.c_double * GROUP_MAX_MEMBERS)]
 
 
 def build_sources():
@@ -166,6 +174,10 @@ def lib():
     L.apss_get_head_terms.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.apss_ext_ids_dev.restype = i32
     L.apss_ext_ids_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.apss_get_store_dev.restype = i32
+    L.apss_get_store_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi64, pi64]
+    L.apss_insert_stored_dev.restype = i32
+    L.apss_insert_stored_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.apss_group_create.restype = i32
     L.apss_group_create.argtypes = [C.POINTER(Config), i32, vp, C.c_uint32, C.POINTER(vp)]
     L.apss_group_destroy.restype = None
@@ -192,5 +204,9 @@ def lib():
     L.apss_group_stats_get.argtypes = [vp, C.POINTER(GroupStats)]
     L.apss_group_member_stats.restype = i32
     L.apss_group_member_stats.argtypes = [vp, i32, C.POINTER(Stats)]
+    L.apss_group_relayout.restype = i32
+    L.apss_group_relayout.argtypes = [vp, vp]
+    L.apss_group_layout_get.restype = i32
+    L.apss_group_layout_get.argtypes = [vp, C.POINTER(GroupLayout)]
     _lib = L
     return L

@@ -297,6 +297,27 @@ class ApssGroup:
         d["term_cuts"] = list(st.term_cuts[: self.n_members + 1])
         return d
 
+    def relayout(self, cuts=None):
+        """re-decide the layout from the stored rows now (apss_group_relayout): cuts=None decides cuts and dense head, explicit
+        cuts (n_members + 1 entries) re-decide only the head; the store is rebuilt when the layout changes"""
+        if cuts is None:
+            self._chk(self._L.apss_group_relayout(self._g, None))
+            return
+        cuts = _np(cuts, np.int32)
+        if cuts.size != self.n_members + 1:
+            raise ValueError("cuts must have n_members + 1 entries")
+        self._chk(self._L.apss_group_relayout(self._g, _ptr(cuts)))
+
+    def layout(self):
+        """the layout and its re-layout history (apss_group_layout_get; dfsq is computed on the device at this call)"""
+        lo = _lib.GroupLayout()
+        lo.struct_size = C.sizeof(_lib.GroupLayout)
+        self._chk(self._L.apss_group_layout_get(self._g, C.byref(lo)))
+        d = {k: getattr(lo, k) for k, _ in _lib.GroupLayout._fields_}
+        d["term_cuts"] = list(lo.term_cuts[: self.n_members + 1])
+        d["dfsq"] = list(lo.dfsq[: self.n_members])
+        return d
+
     def member_stats(self, member):
         st = _lib.Stats()
         st.struct_size = C.sizeof(_lib.Stats)

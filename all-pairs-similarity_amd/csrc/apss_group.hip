@@ -18,6 +18,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -26,6 +27,7 @@
 
 #include <rccl/rccl.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/apss.h"
@@ -101,20 +103,24 @@ Rccl *load_rccl() {
   return &r;
 }
 
-// ---- a reusable barrier for the member threads of one call (C++17: no std::barrier)
+// ---- a reusable barrier for the member threads of one call (C++17: no std::barrier).  wait() returns the call's failure flag
+// as the LAST thread to arrive read it, under the mutex: every thread of one generation takes the same go / no-go decision,
+// even when a thread that already left fails (and sets the flag) before a slower one has woken up.
 class Barrier {
  public:
-  explicit Barrier(int n) : n_(n) {}
-  void wait() {
+  Barrier(int n, const std::atomic<int> *failed) : n_(n), failed_(failed) {}
+  bool wait() {
     std::unique_lock<std::mutex> lk(mu_);
     const uint64_t gen = gen_;
     if (++count_ == n_) {
       count_ = 0;
+      snap_ = failed_->load() != 0;
       ++gen_;
       cv_.notify_all();
     } else {
       cv_.wait(lk, [&] { return gen_ != gen; });
     }
+    return snap_;  // (the next generation cannot overwrite it before this thread arrives there)
   }
 
  private:
@@ -122,6 +128,8 @@ class Barrier {
   std::condition_variable cv_;
   int n_, count_ = 0;
   uint64_t gen_ = 0;
+  const std::atomic<int> *failed_;
+  bool snap_ = false;
 };
 
 template <class T>
@@ -181,11 +189,54 @@ __global__ void k_gather_ext(const int32_t *q_row, const int32_t *c_slot, const 
   }
 }
 
-// document frequencies of a device-resident batch (the layout decision of a group fed through the device entry point)
-__global__ void k_df_hist(const int32_t *idx, int64_t nnz, int32_t dim, unsigned int *df) {
+// document frequencies of terms [lo, hi) (df[t - lo]) over a device-resident batch (the layout decision of a group fed through the
+// device entry point) or over one member's stored slice (a re-layout: each member's range, the histograms side by side)
+__global__ void k_df_hist(const int32_t *idx, int64_t nnz, int32_t lo, int32_t hi, unsigned int *df) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * blockDim.x) {
     const int32_t t = idx[i];
-    if (t >= 0 && t < dim) atomicAdd(&df[t], 1u);  // (a malformed index is the shard handle's to refuse)
+    if (t >= lo && t < hi) atomicAdd(&df[t - lo], 1u);  // (a malformed index is the shard handle's to refuse)
+  }
+}
+
+// ---- re-layout: whole rows out of the members' slices.  Slot r is row r on every member, the ranges are contiguous and in
+// member order, so whole row r = member 0's slice of r, then member 1's, ... (terms stay strictly increasing).
+// whole-row lengths: len[r] += the row's entries in one member's slice (one launch per member)
+__global__ void k_row_len_add(const int64_t *rowptr, int64_t rows, int64_t *len) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x)
+    len[r] += rowptr[r + 1] - rowptr[r];
+}
+
+// one member's slice into the whole rows: cur[r] = where the row's next entries go (starts as the whole row's offset; the
+// launches run in member order on one stream and each advances it by the member's part).  A wave takes 64 consecutive rows;
+// their entries are one contiguous run of the slice, which the wave copies 64 entries at a time -- coalesced 4-B loads and
+// stores, every lane busy however short the rows -- and each lane finds its entry's row by a binary search over the lanes'
+// row starts (shuffles).
+__global__ __launch_bounds__(256) void k_merge_slice(const int64_t *rowptr, const int32_t *idx, const float *val, int64_t rows,
+                                                     int64_t *cur, int32_t *out_idx, float *out_val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t r0 = wave * 64; r0 < rows; r0 += n_waves * 64) {
+    const int64_t r = r0 + lane;
+    const bool live = r < rows;
+    const int64_t s = live ? rowptr[r] : rowptr[rows];  // (lanes past the end: empty rows at the end of the slice)
+    const int64_t e = live ? rowptr[r + 1] : s;
+    const int64_t d = live ? cur[r] - s : 0;  // entry k of this row goes to d + k
+    const int64_t run_b = __shfl(s, 0), run_e = __shfl(e, 63);
+    for (int64_t k0 = run_b; k0 < run_e; k0 += 64) {
+      const int64_t k = k0 + lane;
+      int j = 0;  // the last lane whose row starts at or before k (empty rows share their start with the next row)
+      for (int step = 32; step; step >>= 1) {
+        const int64_t sj = __shfl(s, j + step);
+        if (sj <= k) j += step;
+      }
+      const int64_t dj = __shfl(d, j);
+      if (k < run_e) {
+        out_idx[dj + k] = idx[k];
+        out_val[dj + k] = val[k];
+      }
+    }
+    if (live) cur[r] += e - s;
   }
 }
 
@@ -223,6 +274,11 @@ struct apss_group {
   int exchange = APSS_EXCHANGE_NONE;
   bool distinct_devices = true;
   int64_t n_rows = 0;
+  // layout history (apss_group_layout)
+  int64_t layout_rows = 0;
+  int64_t evaluations = 0, relayouts = 0, relayout_bytes = 0;
+  double last_relayout_ms = 0, total_relayout_ms = 0;
+  int relayout_fail = -1;  // APSS_DEBUG=relayout_fail=<member>: that member's insert of a re-layout fails (test hook)
   // results of the last query-type call (exchange modes): on member 0's device
   DevBuf<int32_t> res_q, res_c;
   DevBuf<float> res_s;
@@ -309,40 +365,67 @@ std::vector<int32_t> equal_cuts(int32_t dim, int T) {
   return cuts;
 }
 
-// Decide the layout from the first batch: the shared dense-head block (member 0's device runs the library's own policy on a
-// sample of the rows: a plain handle indexes them and is asked which terms it took) and the term cuts, then create the
-// members' shard handles, their streams and -- when every member has its own GPU -- the RCCL communicators.
-int32_t create_members(apss_group *g, const Batch &b) {
+// document frequencies of a batch as the caller handed it in, added to df (on member 0's device for a device batch)
+int32_t add_batch_df(apss_group *g, const Batch &b, std::vector<uint32_t> &df) {
+  const int32_t dim = g->cfg.dim;
+  apss_group::Member &M0 = g->m[0];
+  if (!b.on_device) {
+    for (int64_t i = 0; i < b.nnz; ++i) {
+      const int32_t t = b.indices[i];
+      if (t >= 0 && t < dim) ++df[(size_t)t];
+    }
+    return APSS_OK;
+  }
+  if (b.nnz == 0) return APSS_OK;
+  if (hipSetDevice(M0.dev) != hipSuccess) return gfail(g, APSS_E_DEVICE, "hipSetDevice failed");
+  std::vector<uint32_t> part((size_t)dim, 0u);
+  unsigned int *d_df = nullptr;
+  hipError_t e = hipMalloc((void **)&d_df, (size_t)dim * sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMemsetAsync(d_df, 0, (size_t)dim * sizeof(unsigned int), M0.stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_df_hist, dim3(grid_for(b.nnz)), dim3(256), 0, M0.stream, b.d_indices[0], b.nnz, 0, dim, d_df);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_df, (size_t)dim * sizeof(unsigned int), hipMemcpyDeviceToHost, M0.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(M0.stream);
+  if (d_df) (void)hipFree(d_df);
+  if (e != hipSuccess) return gfail(g, APSS_E_DEVICE, std::string("document frequencies: ") + hipGetErrorString(e));
+  for (size_t t = 0; t < part.size(); ++t) df[t] += part[t];
+  return APSS_OK;
+}
+
+// the first `count` rows of a batch into a handle (the head policy's sample)
+int32_t feed_batch(apss_group *g, apss_handle *ph, const Batch &b, int64_t count) {
+  if (count <= 0) return APSS_OK;
+  if (!b.on_device) return apss_insert(ph, count, b.rowptr, b.indices, b.values, b.ext);
+  int64_t e_end = 0;
+  (void)hipSetDevice(g->m[0].dev);
+  if (hipMemcpy(&e_end, b.d_rowptr[0] + count, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
+  return apss_insert_dev(ph, count, e_end, b.d_rowptr[0], b.d_indices[0], b.d_values[0], b.d_ext[0]);
+}
+
+bool needs_df(const apss_group *g, bool cuts_fixed) { return g->T > 1 && (!cuts_fixed || g->cfg.head_terms == 0); }
+
+bool head_possible(const apss_group *g) {
+  return g->T > 1 && g->cfg.head_terms >= 0 && g->cfg.theta > 0.0 &&
+         !(g->cfg.flags & (APSS_FLAG_EXACT_ACCUM | APSS_FLAG_FORCE_GENERAL | APSS_FLAG_FORCE_SCAN | APSS_FLAG_ADMISSION));
+}
+
+struct Layout {
+  std::vector<int32_t> cuts;  // T + 1
+  std::vector<int32_t> head;  // shared dense-head terms
+};
+
+// Decide a layout for n_rows rows with document frequencies df (needs_df; the head's terms are zeroed on return): the shared
+// dense-head block (member 0's device runs the library's own policy on a sample of the rows, put into a plain handle by
+// `feed`, which is asked which terms it took) and the term cuts -- `fixed` when named, else balanced by sum df^2.
+int32_t decide_layout(apss_group *g, std::vector<uint32_t> &df, int64_t n_rows, const std::vector<int32_t> *fixed,
+                      const std::function<int32_t(apss_handle *)> &feed, Layout &out) {
   const int T = g->T;
   const int32_t dim = g->cfg.dim;
   apss_group::Member &M0 = g->m[0];
-  std::vector<uint32_t> df;
-  const bool need_df = T > 1 && (!g->cuts_named || g->cfg.head_terms == 0);
-  if (need_df) {
-    df.assign((size_t)dim, 0u);
-    if (!b.on_device) {
-      for (int64_t i = 0; i < b.nnz; ++i) {
-        const int32_t t = b.indices[i];
-        if (t >= 0 && t < dim) ++df[(size_t)t];
-      }
-    } else if (b.nnz > 0) {
-      if (hipSetDevice(M0.dev) != hipSuccess) return gfail(g, APSS_E_DEVICE, "hipSetDevice failed");
-      unsigned int *d_df = nullptr;
-      hipError_t e = hipMalloc((void **)&d_df, (size_t)dim * sizeof(unsigned int));
-      if (e == hipSuccess) e = hipMemsetAsync(d_df, 0, (size_t)dim * sizeof(unsigned int), M0.stream);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_df_hist, dim3(grid_for(b.nnz)), dim3(256), 0, M0.stream, b.d_indices[0], b.nnz, dim, d_df);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipMemcpyAsync(df.data(), d_df, (size_t)dim * sizeof(unsigned int), hipMemcpyDeviceToHost, M0.stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(M0.stream);
-      if (d_df) (void)hipFree(d_df);
-      if (e != hipSuccess) return gfail(g, APSS_E_DEVICE, std::string("document frequencies: ") + hipGetErrorString(e));
-    }
-  }
-  g->head.clear();
-  if (T > 1 && g->cfg.head_terms >= 0 && g->cfg.theta > 0.0 && b.n > 0 &&
-      !(g->cfg.flags & (APSS_FLAG_EXACT_ACCUM | APSS_FLAG_FORCE_GENERAL | APSS_FLAG_FORCE_SCAN | APSS_FLAG_ADMISSION))) {
+  out.head.clear();
+  if (head_possible(g) && n_rows > 0) {
     apss_config pc = g->cfg;
     pc.struct_size = (int32_t)sizeof(apss_config);
     pc.device_id = M0.dev;
@@ -351,65 +434,96 @@ int32_t create_members(apss_group *g, const Batch &b) {
     apss_handle *ph = nullptr;
     int32_t rc = apss_create(&pc, &ph);
     if (rc != APSS_OK) return gfail(g, rc, std::string("head policy handle: ") + apss_last_error(nullptr));
-    const int64_t sample = std::min<int64_t>(b.n, 131072);
-    if (!b.on_device) {
-      rc = apss_insert(ph, sample, b.rowptr, b.indices, b.values, b.ext);
-    } else {
-      int64_t e_end = 0;
-      (void)hipSetDevice(M0.dev);
-      if (hipMemcpy(&e_end, b.d_rowptr[0] + sample, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = APSS_E_DEVICE;
-      else rc = apss_insert_dev(ph, sample, e_end, b.d_rowptr[0], b.d_indices[0], b.d_values[0], b.d_ext[0]);
-    }
+    rc = feed(ph);
     int32_t nt = 0;
     if (rc == APSS_OK) rc = apss_get_head_terms(ph, 0, nullptr, &nt);
     if (rc == APSS_OK && nt > 0) {
-      g->head.resize((size_t)nt);
-      rc = apss_get_head_terms(ph, nt, g->head.data(), &nt);
+      out.head.resize((size_t)nt);
+      rc = apss_get_head_terms(ph, nt, out.head.data(), &nt);
     }
     const std::string perr = rc == APSS_OK ? "" : apss_last_error(ph);
     apss_destroy(ph);
     if (rc != APSS_OK) return gfail(g, rc, "head policy handle: " + perr);
-    if (g->cfg.head_terms == 0 && g->head.size() > 256) {
+    if (g->cfg.head_terms == 0 && out.head.size() > 256) {
       // A deep head leaves few tail terms per row, and T term ranges cut them T ways: a row with a single term in a range
       // pairs up at within-range cosine 1 with every row sharing it and the candidate rule stops being selective.  Keep the
       // head only as deep as leaves about 8 tail terms per row and member, never shallower than the 256 terms that hold the
       // long posting lists (measured on C3 with Zipf(1) terms).
       double total = 0;
       for (uint32_t f : df) total += (double)f;
-      size_t k = g->head.size();
+      size_t k = out.head.size();
       for (;;) {
         double in_head = 0;
-        for (size_t i = 0; i < k; ++i) in_head += (double)df[(size_t)g->head[i]];
-        if (k <= 256 || (total - in_head) / (double)std::max<int64_t>(1, b.n) / (double)T >= 8.0) break;
+        for (size_t i = 0; i < k; ++i) in_head += (double)df[(size_t)out.head[i]];
+        if (k <= 256 || (total - in_head) / (double)std::max<int64_t>(1, n_rows) / (double)T >= 8.0) break;
         k /= 2;
       }
-      g->head.resize(std::max<size_t>(k, 256));
+      out.head.resize(std::max<size_t>(k, 256));
     }
   }
-  if (!g->cuts_named) {
-    if (T == 1) {
-      g->cuts = {0, dim};
-    } else if (b.n < 1024) {
-      g->cuts = equal_cuts(dim, T);  // (a first batch this small says nothing about the term distribution)
-    } else {
-      for (int32_t t : g->head) df[(size_t)t] = 0;  // the block's terms are in no member's index: balance the tail's visits
-      g->cuts = balanced_cuts(df, T);
-    }
+  if (fixed) {
+    out.cuts = *fixed;
+  } else if (T == 1) {
+    out.cuts = {0, dim};
+  } else if (n_rows < 1024) {
+    out.cuts = equal_cuts(dim, T);  // (this few rows say nothing about the term distribution)
+  } else {
+    for (int32_t t : out.head) df[(size_t)t] = 0;  // the block's terms are in no member's index: balance the tail's visits
+    out.cuts = balanced_cuts(df, T);
   }
   if (dim < T) return gfail(g, APSS_E_INVALID, "more members than terms");
+  return APSS_OK;
+}
 
+// member i's shard handle for a layout, on the member's stream (*out stays NULL on failure; the message is in err)
+int32_t create_member_handle(apss_group *g, int i, const Layout &L, apss_handle **out, std::string &err) {
+  const int T = g->T;
+  apss_group::Member &M = g->m[(size_t)i];
+  *out = nullptr;
+  apss_config c = g->cfg;
+  c.struct_size = (int32_t)sizeof(apss_config);
+  c.device_id = M.dev;
+  c.term_lo = T == 1 ? 0 : L.cuts[(size_t)i];
+  c.term_hi = T == 1 ? 0 : L.cuts[(size_t)i + 1];
+  apss_handle *h = nullptr;
+  int32_t rc = apss_create(&c, &h);
+  if (rc != APSS_OK) {
+    err = std::string("member handle: ") + apss_last_error(nullptr);
+    return rc;
+  }
+  if ((rc = apss_set_stream(h, (void *)M.stream, 0)) != APSS_OK) {
+    err = apss_last_error(h);
+  } else if (!L.head.empty() && (rc = apss_set_head_terms(h, (int32_t)L.head.size(), L.head.data(), i, T)) != APSS_OK) {
+    err = std::string("member head block: ") + apss_last_error(h);
+  }
+  if (rc != APSS_OK) {
+    apss_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return APSS_OK;
+}
+
+// Decide the layout from the first batch, then create the members' shard handles, their streams and -- when every member has
+// its own GPU -- the RCCL communicators.
+int32_t create_members(apss_group *g, const Batch &b) {
+  const int T = g->T;
+  std::vector<uint32_t> df;
+  if (needs_df(g, g->cuts_named)) {
+    df.assign((size_t)g->cfg.dim, 0u);
+    const int32_t rc = add_batch_df(g, b, df);
+    if (rc != APSS_OK) return rc;
+  }
+  Layout L;
+  const std::vector<int32_t> named = g->cuts;
+  int32_t rc = decide_layout(g, df, b.n, g->cuts_named ? &named : nullptr,
+                             [&](apss_handle *ph) { return feed_batch(g, ph, b, std::min<int64_t>(b.n, 131072)); }, L);
+  if (rc != APSS_OK) return rc;
+  g->cuts = L.cuts;
+  g->head = L.head;
   for (int i = 0; i < T; ++i) {
-    apss_group::Member &M = g->m[(size_t)i];
-    apss_config c = g->cfg;
-    c.struct_size = (int32_t)sizeof(apss_config);
-    c.device_id = M.dev;
-    c.term_lo = T == 1 ? 0 : g->cuts[(size_t)i];
-    c.term_hi = T == 1 ? 0 : g->cuts[(size_t)i + 1];
-    int32_t rc = apss_create(&c, &M.h);
-    if (rc != APSS_OK) return gfail(g, rc, std::string("member handle: ") + apss_last_error(nullptr));
-    if ((rc = apss_set_stream(M.h, (void *)M.stream, 0)) != APSS_OK) return gfail(g, rc, apss_last_error(M.h));
-    if (!g->head.empty() && (rc = apss_set_head_terms(M.h, (int32_t)g->head.size(), g->head.data(), i, T)) != APSS_OK)
-      return gfail(g, rc, std::string("member head block: ") + apss_last_error(M.h));
+    std::string err;
+    if ((rc = create_member_handle(g, i, L, &g->m[(size_t)i].h, err)) != APSS_OK) return gfail(g, rc, err);
   }
   const bool exchange_needed = T > 1 || (g->flags & APSS_GROUP_FORCE_EXCHANGE);
   g->exchange = !exchange_needed ? APSS_EXCHANGE_NONE : APSS_EXCHANGE_COPIES;
@@ -424,12 +538,14 @@ int32_t create_members(apss_group *g, const Batch &b) {
     for (int i = 0; i < T; ++i) g->m[(size_t)i].comm = comms[(size_t)i];
     g->exchange = APSS_EXCHANGE_RCCL;
   }
+  g->layout_rows = b.n;
   g->created = true;
   return APSS_OK;
 }
 
 // ---- one member's share of a call; every member thread runs this, the barriers keep the phases in step.  A failure is
-// published BEFORE the next barrier, so after it every thread sees the same flag and they leave (or skip a collective) together.
+// published BEFORE the next barrier, and every thread acts on the flag as the barrier returned it: they leave (or skip a
+// collective) together.
 struct CallCtx {
   apss_group *g;
   int mode;  // 0 insert, 1 query (frozen index), 2 insert-and-query
@@ -523,8 +639,8 @@ void member_main(int i, CallCtx *pcx) {
     if (rc != APSS_OK) fail_here(rc);
   }
   M.member_ms = ms_since(t0);
-  cx.bar->wait();  // ---- B1: every member's candidate count (or failure) is known
-  if (cx.failed.load() || cx.mode == 0 || g->exchange == APSS_EXCHANGE_NONE) return;
+  const bool failed_b1 = cx.bar->wait();  // ---- B1: every member's candidate count (or failure) is known
+  if (failed_b1 || cx.mode == 0 || g->exchange == APSS_EXCHANGE_NONE) return;
   const auto tx = Clock::now();
   int64_t total = 0, my_off = 0;
   std::vector<int64_t> off((size_t)T + 1, 0);
@@ -542,8 +658,7 @@ void member_main(int i, CallCtx *pcx) {
     const int32_t rc = member_pack(M, total, my_off);
     if (rc != APSS_OK) fail_here(rc);
   }
-  cx.bar->wait();  // ---- B2: every list is packed
-  if (cx.failed.load()) return;
+  if (cx.bar->wait()) return;  // ---- B2: every list is packed
   // ---- step 2: all-gather of the candidate lists (in place: member k's list sits at off[k] in every member's buffer)
   int32_t rc = APSS_OK;
   if (g->exchange == APSS_EXCHANGE_RCCL) {
@@ -583,15 +698,13 @@ void member_main(int i, CallCtx *pcx) {
     M.partial_ms = ms_since(tp);
   }
   if (rc != APSS_OK) fail_here(rc);
-  cx.bar->wait();  // ---- B3: every member's partial scores are complete
-  if (cx.failed.load()) return;
+  if (cx.bar->wait()) return;  // ---- B3: every member's partial scores are complete
   const int64_t nu = M.n_union;
   if (g->m[0].n_union != nu) {  // (cannot happen: the same sort of the same keys; checked because a collective of unequal counts hangs)
     M.err = "members disagree on the candidate union";
     fail_here(APSS_E_STATE);
   }
-  cx.bar->wait();  // ---- B3b
-  if (cx.failed.load()) return;
+  if (cx.bar->wait()) return;  // ---- B3b
   // ---- step 4: all-reduce(SUM) of the partial scores
   const float *total_score = M.partial.p;
   if (!cx.failed.load() && nu > 0) {
@@ -657,6 +770,279 @@ void member_main(int i, CallCtx *pcx) {
   cx.bar->wait();  // ---- B4: member 0 has read every peer's partial scores (copies exchange) before anyone returns
 }
 
+// ---- re-layout (apss_group_relayout, APSS_GROUP_ADAPT_LAYOUT): decide a layout from the store (+ the incoming batch), build
+// new member handles from whole rows reassembled out of the old members' slices, swap only when every member succeeded.
+
+// whole rows of the store on one device, assembled by the first member on it and read in place by the others there
+struct WholeRows {
+  int64_t *rowptr = nullptr, *len = nullptr, *cur = nullptr;
+  int32_t *idx = nullptr;
+  float *val = nullptr;
+  int64_t nnz = 0;
+  std::vector<void *> owned;  // every allocation above + staged copies of other devices' slices + scan scratch
+};
+
+struct RelayoutCtx {
+  apss_group *g = nullptr;
+  const Batch *b = nullptr;             // the incoming batch of the call that triggered it (NULL: apss_group_relayout)
+  const std::vector<int32_t> *fixed = nullptr;  // cuts to take (named, or given to apss_group_relayout)
+  Barrier *bar = nullptr;
+  std::atomic<int> failed{0};
+  int64_t rows = 0;                     // stored rows (every member holds a slice of each)
+  bool decide_df = false;
+  std::vector<uint32_t> df;             // of the store: member i fills its range [cuts[i], cuts[i + 1])
+  std::vector<int> builder;             // per member: the member that assembles whole rows on its device
+  std::vector<WholeRows> whole;         // per member (used at the builders' indices)
+  std::atomic<int64_t> bytes{0};
+  Layout next;
+  bool rebuild = false;
+  std::vector<apss_handle *> fresh;
+};
+
+hipError_t dev_alloc(WholeRows &w, void **p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+  if (e == hipSuccess) w.owned.push_back(*p);
+  return e;
+}
+
+void free_whole(WholeRows &w) {
+  for (void *p : w.owned) (void)hipFree(p);
+  w = WholeRows{};
+}
+
+// document frequencies of member i's stored slice: its range of the store's terms (on the member's stream)
+int32_t member_df(apss_group *g, int i, const int32_t *cuts, uint32_t *df_range) {
+  apss_group::Member &M = g->m[(size_t)i];
+  const int32_t lo = g->T == 1 ? 0 : cuts[i], hi = g->T == 1 ? g->cfg.dim : cuts[i + 1];
+  const int64_t *rp = nullptr;
+  const int32_t *ix = nullptr;
+  const float *vl = nullptr;
+  int64_t rows = 0, nnz = 0;
+  (void)apss_get_store_dev(M.h, &rp, &ix, &vl, &rows, &nnz);
+  std::memset(df_range, 0, (size_t)(hi - lo) * sizeof(uint32_t));
+  if (nnz == 0) return APSS_OK;
+  unsigned int *d_df = nullptr;
+  GHIP(nullptr, M, hipMalloc((void **)&d_df, (size_t)(hi - lo) * sizeof(unsigned int)));
+  hipError_t e = hipMemsetAsync(d_df, 0, (size_t)(hi - lo) * sizeof(unsigned int), M.stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_df_hist, dim3(grid_for(nnz)), dim3(256), 0, M.stream, ix, nnz, lo, hi, d_df);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(df_range, d_df, (size_t)(hi - lo) * sizeof(unsigned int), hipMemcpyDeviceToHost, M.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(M.stream);
+  (void)hipFree(d_df);
+  GHIP(nullptr, M, e);
+  return APSS_OK;
+}
+
+// whole rows on member i's device (i is the builder there): lengths, exclusive scan, then every member's slice in member order
+int32_t assemble_whole(RelayoutCtx &cx, int i) {
+  apss_group *g = cx.g;
+  apss_group::Member &M = g->m[(size_t)i];
+  WholeRows &w = cx.whole[(size_t)i];
+  const int64_t rows = cx.rows;
+  GHIP(nullptr, M, dev_alloc(w, (void **)&w.rowptr, (size_t)(rows + 1) * sizeof(int64_t)));
+  GHIP(nullptr, M, dev_alloc(w, (void **)&w.len, (size_t)(rows + 1) * sizeof(int64_t)));
+  GHIP(nullptr, M, dev_alloc(w, (void **)&w.cur, (size_t)(rows + 1) * sizeof(int64_t)));
+  GHIP(nullptr, M, hipMemsetAsync(w.len, 0, (size_t)(rows + 1) * sizeof(int64_t), M.stream));
+  struct Slice {
+    const int64_t *rp;
+    const int32_t *ix;
+    const float *vl;
+  };
+  std::vector<Slice> sl((size_t)g->T);
+  for (int k = 0; k < g->T; ++k) {
+    const apss_group::Member &P = g->m[(size_t)k];
+    Slice &s = sl[(size_t)k];
+    int64_t r = 0, z = 0;
+    (void)apss_get_store_dev(P.h, &s.rp, &s.ix, &s.vl, &r, &z);
+    if (r != rows || !s.rp) {
+      M.err = "member " + std::to_string(k) + " holds " + std::to_string(r) + " rows, member 0 " + std::to_string(rows);
+      return APSS_E_STATE;
+    }
+    if (P.dev != M.dev) {  // another device's slice: brought over first (peer copy, or staged by the runtime)
+      int64_t *rp2 = nullptr;
+      int32_t *ix2 = nullptr;
+      float *vl2 = nullptr;
+      GHIP(nullptr, M, dev_alloc(w, (void **)&rp2, (size_t)(rows + 1) * sizeof(int64_t)));
+      GHIP(nullptr, M, dev_alloc(w, (void **)&ix2, (size_t)z * sizeof(int32_t)));
+      GHIP(nullptr, M, dev_alloc(w, (void **)&vl2, (size_t)z * sizeof(float)));
+      GHIP(nullptr, M, hipMemcpyAsync(rp2, s.rp, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDefault, M.stream));
+      if (z > 0) {
+        GHIP(nullptr, M, hipMemcpyAsync(ix2, s.ix, (size_t)z * sizeof(int32_t), hipMemcpyDefault, M.stream));
+        GHIP(nullptr, M, hipMemcpyAsync(vl2, s.vl, (size_t)z * sizeof(float), hipMemcpyDefault, M.stream));
+      }
+      cx.bytes += (rows + 1) * (int64_t)sizeof(int64_t) + z * (int64_t)(sizeof(int32_t) + sizeof(float));
+      s = Slice{rp2, ix2, vl2};
+    }
+    hipLaunchKernelGGL(k_row_len_add, dim3(grid_for(rows)), dim3(256), 0, M.stream, s.rp, rows, w.len);
+    GHIP(nullptr, M, hipGetLastError());
+  }
+  size_t tmp_bytes = 0;
+  GHIP(nullptr, M, rocprim::exclusive_scan(nullptr, tmp_bytes, w.len, w.rowptr, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
+  void *tmp = nullptr;
+  GHIP(nullptr, M, dev_alloc(w, &tmp, tmp_bytes));
+  GHIP(nullptr, M, rocprim::exclusive_scan(tmp, tmp_bytes, w.len, w.rowptr, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
+  GHIP(nullptr, M, hipMemcpyAsync(&w.nnz, w.rowptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
+  GHIP(nullptr, M, hipMemcpyAsync(w.cur, w.rowptr, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToDevice, M.stream));
+  GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+  GHIP(nullptr, M, dev_alloc(w, (void **)&w.idx, (size_t)w.nnz * sizeof(int32_t)));
+  GHIP(nullptr, M, dev_alloc(w, (void **)&w.val, (size_t)w.nnz * sizeof(float)));
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, 256), 8192));  // 4 waves x 64 rows
+  for (int k = 0; k < g->T; ++k) {
+    const Slice &s = sl[(size_t)k];
+    hipLaunchKernelGGL(k_merge_slice, dim3(blocks), dim3(256), 0, M.stream, s.rp, s.ix, s.vl, rows, w.cur, w.idx, w.val);
+    GHIP(nullptr, M, hipGetLastError());
+  }
+  GHIP(nullptr, M, hipStreamSynchronize(M.stream));  // (the other members on this device read the rows on their own streams)
+  return APSS_OK;
+}
+
+void relayout_main(int i, RelayoutCtx *pcx) {
+  RelayoutCtx &cx = *pcx;
+  apss_group *g = cx.g;
+  apss_group::Member &M = g->m[(size_t)i];
+  M.rc = APSS_OK;
+  M.err.clear();
+  auto fail_here = [&](int32_t rc) {
+    M.rc = rc;
+    cx.failed.store(1);
+  };
+  if (hipSetDevice(M.dev) != hipSuccess) {
+    M.err = "hipSetDevice failed";
+    fail_here(APSS_E_DEVICE);
+  }
+  // ---- phase A: this member's document frequencies; the builder of each device assembles the whole rows there
+  if (!cx.failed.load() && cx.decide_df) {
+    const int32_t lo = g->T == 1 ? 0 : g->cuts[(size_t)i];
+    const int32_t rc = member_df(g, i, g->cuts.data(), cx.df.data() + lo);
+    if (rc != APSS_OK) fail_here(rc);
+  }
+  if (!cx.failed.load() && cx.rows > 0 && cx.builder[(size_t)i] == i) {
+    const int32_t rc = assemble_whole(cx, i);
+    if (rc != APSS_OK) fail_here(rc);
+  }
+  if (cx.bar->wait()) {  // ---- R1: document frequencies and whole rows are complete
+    if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+    return;
+  }
+  // ---- phase B: member 0 decides (the head policy runs on its device over whole rows)
+  if (i == 0) {
+    const WholeRows &w = cx.whole[(size_t)cx.builder[0]];
+    const int64_t batch_n = cx.b ? cx.b->n : 0;
+    auto feed = [&](apss_handle *ph) -> int32_t {
+      const int64_t s_rows = std::min<int64_t>(cx.rows, 131072);
+      if (s_rows > 0) {
+        int64_t s_nnz = 0;
+        if (hipMemcpy(&s_nnz, w.rowptr + s_rows, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
+        const int64_t *d_ext = nullptr;
+        (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
+        const int32_t rc = apss_insert_stored_dev(ph, s_rows, s_nnz, w.rowptr, w.idx, w.val, d_ext);
+        if (rc != APSS_OK) return rc;
+      }
+      return cx.b ? feed_batch(g, ph, *cx.b, std::min<int64_t>(batch_n, 131072 - s_rows)) : APSS_OK;
+    };
+    int32_t rc = APSS_OK;
+    if (cx.decide_df && cx.b) rc = add_batch_df(g, *cx.b, cx.df);
+    if (rc == APSS_OK) rc = decide_layout(g, cx.df, cx.rows + batch_n, cx.fixed, feed, cx.next);
+    if (rc != APSS_OK) {
+      M.err = g->err;
+      fail_here(rc);
+    } else {
+      cx.rebuild = cx.next.cuts != g->cuts || cx.next.head != g->head;
+    }
+  }
+  if (cx.bar->wait() || !cx.rebuild) {  // ---- R2: the decision is known
+    if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+    return;
+  }
+  // ---- phase C: a new handle for this member in the new layout, filled with the whole rows of its device
+  {
+    std::string err;
+    int32_t rc = create_member_handle(g, i, cx.next, &cx.fresh[(size_t)i], err);
+    if (rc == APSS_OK && cx.rows > 0) {
+      const WholeRows &w = cx.whole[(size_t)cx.builder[(size_t)i]];
+      const int64_t *d_ext = nullptr;
+      (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
+      const bool inject = g->relayout_fail == i;  // (the test hook: the handle's own argument check refuses the call)
+      rc = apss_insert_stored_dev(cx.fresh[(size_t)i], inject ? -1 : cx.rows, w.nnz, w.rowptr, w.idx, w.val, d_ext);
+      if (rc != APSS_OK) err = std::string(inject ? "APSS_DEBUG relayout_fail: " : "") + apss_last_error(cx.fresh[(size_t)i]);
+      else if (hipStreamSynchronize(M.stream) != hipSuccess) rc = APSS_E_DEVICE, err = "stream synchronisation failed after the re-insert";
+    }
+    if (rc != APSS_OK) {
+      M.err = "re-layout: " + err;
+      fail_here(rc);
+    }
+  }
+  const bool failed_r3 = cx.bar->wait();  // ---- R3: every new member is filled (or one failed): swap together, or not at all
+  if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+  if (failed_r3) {
+    if (cx.fresh[(size_t)i]) apss_destroy(cx.fresh[(size_t)i]);
+    cx.fresh[(size_t)i] = nullptr;
+    return;
+  }
+  apss_destroy(M.h);
+  M.h = cx.fresh[(size_t)i];
+  cx.fresh[(size_t)i] = nullptr;
+}
+
+bool layout_can_change(const apss_group *g, bool cuts_given) { return g->T > 1 && (!(g->cuts_named || cuts_given) || head_possible(g)); }
+
+int64_t next_eval_rows(const apss_group *g) {
+  if (!(g->flags & APSS_GROUP_ADAPT_LAYOUT) || !g->created || !layout_can_change(g, false)) return 0;
+  return std::max<int64_t>(1024, 2 * g->layout_rows);
+}
+
+// decide again on the store (+ b) and rebuild the store when the layout changes; cuts: taken as given (NULL: named or decided)
+int32_t relayout(apss_group *g, const std::vector<int32_t> *cuts, const Batch *b) {
+  const auto t0 = Clock::now();
+  const int T = g->T;
+  RelayoutCtx cx;
+  cx.g = g;
+  cx.b = b;
+  cx.fixed = cuts ? cuts : (g->cuts_named ? &g->cuts : nullptr);
+  (void)apss_size(g->m[0].h, &cx.rows, nullptr);
+  const int64_t decided_on = cx.rows + (b ? b->n : 0);
+  if (layout_can_change(g, cuts != nullptr) || (cuts && *cuts != g->cuts)) {
+    cx.decide_df = needs_df(g, cx.fixed != nullptr);
+    if (cx.decide_df) cx.df.assign((size_t)g->cfg.dim, 0u);
+    cx.builder.assign((size_t)T, 0);
+    for (int i = 0; i < T; ++i) {
+      int k = 0;
+      while (g->m[(size_t)k].dev != g->m[(size_t)i].dev) ++k;
+      cx.builder[(size_t)i] = k;
+    }
+    cx.whole.resize((size_t)T);
+    cx.fresh.assign((size_t)T, nullptr);
+    Barrier bar(T, &cx.failed);
+    cx.bar = &bar;
+    std::vector<std::thread> th;
+    for (int i = 1; i < T; ++i) th.emplace_back(relayout_main, i, &cx);
+    relayout_main(0, &cx);
+    for (std::thread &t : th) t.join();
+    (void)hipSetDevice(g->m[0].dev);
+    if (cx.failed.load()) {
+      for (int i = 0; i < T; ++i)
+        if (g->m[(size_t)i].rc != APSS_OK)
+          return gfail(g, g->m[(size_t)i].rc, "member " + std::to_string(i) + ": " + g->m[(size_t)i].err);
+      return gfail(g, APSS_E_STATE, "a member failed during the re-layout");
+    }
+    if (cx.rebuild) {
+      g->cuts = cx.next.cuts;
+      g->head = cx.next.head;
+      ++g->relayouts;
+      g->relayout_bytes += cx.bytes.load();
+      g->n_res = -1;  // (the old handles held the last results)
+      g->results_in_handle = false;
+    }
+  }
+  ++g->evaluations;
+  g->layout_rows = decided_on;
+  g->last_relayout_ms = ms_since(t0);
+  g->total_relayout_ms += g->last_relayout_ms;
+  return APSS_OK;
+}
+
 int32_t run_call(apss_group *g, int mode, const Batch &b, int64_t *n_results) {
   if (n_results) *n_results = 0;
   g->err.clear();
@@ -676,13 +1062,21 @@ int32_t run_call(apss_group *g, int mode, const Batch &b, int64_t *n_results) {
       }
       return rc;
     }
+  } else if (mode != 1 && b.n > 0) {
+    // APSS_GROUP_ADAPT_LAYOUT: the store doubled since the layout was decided -- decide again on the store plus this batch,
+    // rebuild, and let the batch land in the new layout
+    const int64_t at = next_eval_rows(g);
+    if (at > 0 && g->n_rows + b.n >= at) {
+      const int32_t rc = relayout(g, nullptr, &b);
+      if (rc != APSS_OK) return rc;
+    }
   }
   const auto t0 = Clock::now();
   CallCtx cx;
   cx.g = g;
   cx.mode = mode;
   cx.b = b;
-  Barrier bar(g->T);
+  Barrier bar(g->T, &cx.failed);
   cx.bar = &bar;
   std::vector<std::thread> th;
   for (int i = 1; i < g->T; ++i) th.emplace_back(member_main, i, &cx);
@@ -810,6 +1204,11 @@ int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32
   g->T = n_members;
   g->m.resize((size_t)n_members);
   g->st.struct_size = (int32_t)sizeof(apss_group_stats);
+  if (const char *dbg = getenv("APSS_DEBUG")) {  // (the group's only token; the handles skip it)
+    const std::string s = std::string(",") + dbg;
+    const size_t at = s.find(",relayout_fail=");
+    if (at != std::string::npos) g->relayout_fail = atoi(s.c_str() + at + 15);
+  }
   for (int i = 0; i < n_members; ++i) {
     const int d = device_ids[i];
     if (d < 0 || d >= ndev) {
@@ -921,6 +1320,59 @@ int32_t apss_group_clear(apss_group *g) {
     const int32_t rc = apss_clear(M.h);
     if (rc != APSS_OK) return gfail(g, rc, "member " + std::to_string(i) + ": " + apss_last_error(M.h));
   }
+  return APSS_OK;
+}
+
+int32_t apss_group_relayout(apss_group *g, const int32_t *cuts) {
+  if (!g) return APSS_E_INVALID;
+  g->err.clear();
+  if (!g->created || g->n_rows == 0) return gfail(g, APSS_E_STATE, "apss_group_relayout: the group holds no rows");
+  std::vector<int32_t> given;
+  if (cuts) {
+    if (cuts[0] != 0 || cuts[g->T] != g->cfg.dim) return gfail(g, APSS_E_INVALID, "apss_group_relayout: cuts[0] = 0 and cuts[n_members] = dim");
+    for (int i = 0; i < g->T; ++i)
+      if (cuts[i] >= cuts[i + 1]) return gfail(g, APSS_E_INVALID, "apss_group_relayout: cuts must be strictly increasing");
+    given.assign(cuts, cuts + g->T + 1);
+  }
+  return relayout(g, cuts ? &given : nullptr, nullptr);
+}
+
+int32_t apss_group_layout_get(apss_group *g, apss_group_layout *out) {
+  if (!g || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return gfail(g, APSS_E_INVALID, "apss_group_layout.struct_size must be set to sizeof(apss_group_layout) before the call");
+  apss_group_layout L{};
+  L.n_members = g->T;
+  L.layout_rows = g->layout_rows;
+  L.next_eval_rows = next_eval_rows(g);
+  L.evaluations = g->evaluations;
+  L.relayouts = g->relayouts;
+  L.last_relayout_ms = g->last_relayout_ms;
+  L.total_relayout_ms = g->total_relayout_ms;
+  L.relayout_bytes = g->relayout_bytes;
+  L.head_terms = (int32_t)g->head.size();
+  for (size_t i = 0; i < g->cuts.size() && i <= APSS_GROUP_MAX_MEMBERS; ++i) L.term_cuts[i] = g->cuts[i];
+  if (g->created) {
+    // sum of df^2 over each member's stored tail terms (its range without the head's): a df pass over every member's slice
+    std::vector<uint32_t> df((size_t)g->cfg.dim, 0u);
+    std::vector<char> in_head((size_t)g->cfg.dim, 0);
+    for (int32_t t : g->head) in_head[(size_t)t] = 1;
+    for (int i = 0; i < g->T; ++i) {
+      apss_group::Member &M = g->m[(size_t)i];
+      const int32_t lo = g->T == 1 ? 0 : g->cuts[(size_t)i], hi = g->T == 1 ? g->cfg.dim : g->cuts[(size_t)i + 1];
+      int32_t rc = hipSetDevice(M.dev) == hipSuccess ? APSS_OK : APSS_E_DEVICE;
+      if (rc == APSS_OK) rc = member_df(g, i, g->cuts.data(), df.data() + lo);
+      if (rc != APSS_OK) return gfail(g, rc, "member " + std::to_string(i) + ": " + M.err);
+      double sq = 0;
+      for (int32_t t = lo; t < hi; ++t)
+        if (!in_head[(size_t)t]) sq += (double)df[(size_t)t] * (double)df[(size_t)t];
+      L.dfsq[i] = sq;
+    }
+  }
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_group_layout));
+  L.struct_size = n;
+  std::memcpy(out, &L, (size_t)n);
   return APSS_OK;
 }
 

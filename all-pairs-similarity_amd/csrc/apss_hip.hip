@@ -117,6 +117,7 @@ DebugCfg parse_debug_env() {
     else if (key == "merge_u") d.merge_u = (int)val;
     else if (key == "no_merge_prune") d.no_merge_prune = val != 0;
     else if (key == "merge_single") d.merge_single = (int)val;
+    else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
   return d;
@@ -142,6 +143,7 @@ struct apss_handle {
   int64_t store_nonempty = 0;  // stored rows with at least one indexed entry (each touches itself in a self-join)
   int64_t last_batch_nonempty = 0;
   int32_t cb = 16384;
+  bool stored_rows = false;  // the rows being ingested passed this configuration's filters already (apss_insert_stored_dev)
 
   // store (CSR) -- vectorsStore, IWA:22
   int64_t n_rows = 0, nnz = 0;
@@ -351,7 +353,10 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   *n_out = 0;
   *nnz_out = 0;
   if (n == 0) return APSS_OK;
-  const bool transform = h->sharded || (h->cfg.flags & (APSS_FLAG_VALUE_PRUNE | APSS_FLAG_ADMISSION | APSS_FLAG_NORMALIZE));
+  // rows out of a store (apss_insert_stored_dev) were normalised, pruned and admitted when they first came in: a second pass
+  // would change them (a pruned row re-normalised) or drop them (admission on the pruned sum)
+  const uint32_t in_flags = h->stored_rows ? h->cfg.flags & ~(APSS_FLAG_VALUE_PRUNE | APSS_FLAG_ADMISSION | APSS_FLAG_NORMALIZE) : h->cfg.flags;
+  const bool transform = h->sharded || (in_flags & (APSS_FLAG_VALUE_PRUNE | APSS_FLAG_ADMISSION | APSS_FLAG_NORMALIZE));
   APSS_TRY(ensure(h, h->s_keep, (size_t)n + 1));
   APSS_TRY(ensure(h, h->s_cnt, (size_t)n + 1));
   APSS_TRY(ensure(h, h->s_inv, (size_t)n));
@@ -368,7 +373,7 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   a.dim = h->cfg.dim;
   a.term_lo = h->cfg.term_lo;
   a.term_hi = h->cfg.term_hi;
-  a.flags = h->cfg.flags;
+  a.flags = in_flags;
   a.theta = (float)h->cfg.theta;
   a.index_threshold = (float)h->cfg.index_threshold;
   a.row_keep = h->s_keep.p;
@@ -480,8 +485,8 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
     p.w_pad = w_pad;
     p.ratio_t = nullptr;  // k_ingest_count wrote this shard's ratio
     p.head_nonempty = reinterpret_cast<unsigned int *>(h->head_ctr.p);
-    p.row_inv = (h->cfg.flags & APSS_FLAG_NORMALIZE) ? h->s_inv.p : nullptr;
-    p.prune_above = (h->cfg.flags & APSS_FLAG_VALUE_PRUNE) ? (float)h->cfg.index_threshold : -INFINITY;
+    p.row_inv = (in_flags & APSS_FLAG_NORMALIZE) ? h->s_inv.p : nullptr;
+    p.prune_above = (in_flags & APSS_FLAG_VALUE_PRUNE) ? (float)h->cfg.index_threshold : -INFINITY;
     p.fold_from = h->head_exact;
     p.part = h->head_part;  // (a stored query's product with itself is counted by the shard that owns its tile)
     p.n_parts = h->head_parts;
@@ -2784,6 +2789,31 @@ int32_t apss_insert_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d
     return fail(h, APSS_E_INVALID, "null device pointer");
   int64_t first = 0;
   return insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first);
+}
+
+int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_indices,
+                               const float *d_values, const int64_t *d_ext_ids) {
+  APSS_TRY(enter(h));
+  if (n < 0 || nnz < 0) return fail(h, APSS_E_INVALID, "negative size");
+  if (n > 0 && (!d_rowptr || !d_ext_ids || (nnz > 0 && (!d_indices || !d_values))))
+    return fail(h, APSS_E_INVALID, "null device pointer");
+  int64_t first = 0;
+  h->stored_rows = true;
+  const int32_t rc = insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first);
+  h->stored_rows = false;
+  return rc;
+}
+
+int32_t apss_get_store_dev(apss_handle *h, const int64_t **d_rowptr, const int32_t **d_indices, const float **d_values, int64_t *rows,
+                       int64_t *nnz) {
+  if (!h) return APSS_E_INVALID;
+  const bool any = h->n_rows > 0;
+  if (d_rowptr) *d_rowptr = any ? h->rowptr.p : nullptr;
+  if (d_indices) *d_indices = any ? h->idx.p : nullptr;
+  if (d_values) *d_values = any ? h->val.p : nullptr;
+  if (rows) *rows = h->n_rows;
+  if (nnz) *nnz = h->nnz;
+  return APSS_OK;
 }
 
 int32_t apss_query_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_indices,

@@ -38,8 +38,14 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
   private val headTerms = if (conf.hasPath("cpslab.allpair.gpu.headTerms")) conf.getInt("cpslab.allpair.gpu.headTerms") else 0
   private val flags = if (indexThreshold > 0.0) NativeApss.FLAG_VALUE_PRUNE else 0
   private val grouped = devices.length > 1
+  // cpslab.allpair.gpu.adaptiveLayout = true: the group re-decides its term cuts and shared head as the index grows
+  // (APSS_GROUP_ADAPT_LAYOUT): a stream of single vectors from an empty index does not keep its first message's layout
+  private val groupFlags =
+    if (conf.hasPath("cpslab.allpair.gpu.adaptiveLayout") && conf.getBoolean("cpslab.allpair.gpu.adaptiveLayout"))
+      NativeApss.GROUP_ADAPT_LAYOUT
+    else 0
   private val handle =
-    if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, 0)
+    if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags)
     else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =

@@ -31,6 +31,7 @@ object NativeApss {
   // members' answers (all-gather of candidate lists, RCCL all-reduce of per-candidate partial scores) runs below this call.
   val GROUP_FORCE_EXCHANGE = 1
   val GROUP_NO_RCCL = 2
+  val GROUP_ADAPT_LAYOUT = 4 // re-decide term cuts and shared head as the store grows (include/apss.h)
   /** returns the group's handle or 0 (groupLastError(0) says why) */
   @native def createGroup(dim: Int, theta: Double, indexThreshold: Double, flags: Int, devices: Array[Int], headTerms: Int,
                           groupFlags: Int): Long

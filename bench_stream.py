@@ -13,6 +13,10 @@ Small batches (B < --full-below) are SAMPLED: the store is pre-filled in bulk to
 `refcpu` beside it: the oracle's IndexingWorkerActor restatement (hash-map posting lists + per-candidate hash-map dot, one
 thread = one actor) fed the same batches for a bounded number of seconds -- the harness's baseline, never a fallback.
 Not BASELINE.json's metric (bench.py is); workload = configs[2]'s shape (C3) unless told otherwise.
+
+`--engine group --members T` streams into an apss_group of T term-range members (device 0 for all by default, --devices
+to place them) with APSS_GROUP_ADAPT_LAYOUT on (--no-adapt: off): every row adds the group's re-layouts over that stream
+and their total time (apss_group_layout).
 """
 import argparse
 import json
@@ -51,6 +55,43 @@ def stream_gpu(cfg, d_ids, d_rp, d_idx, d_val, B, n_end, ix=None, start=0, max_c
     return rec
 
 
+class GroupStream:
+    """an apss_group behind the handle's face that stream_gpu drives (every member reads the same device tensors)"""
+
+    def __init__(self, dim, theta, devices, adapt):
+        from apss import _lib
+        from apss.engine import ApssGroup
+        self.g = ApssGroup(dim, theta, devices, group_flags=_lib.GROUP_ADAPT_LAYOUT if adapt else 0)
+        self.devices = devices
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.g.close()
+
+    def insert_and_query_dev(self, ids, rp, bi, bv):
+        import torch
+        per = {}
+        for d in set(self.devices):
+            dev = torch.device("cuda", d)
+            per[d] = tuple(t.to(dev) for t in (ids, rp, bi, bv))
+        return self.g.insert_and_query_dev([per[d] for d in self.devices])
+
+    def stats(self):
+        st = self.g.stats()
+        return {"probe_ms": st["probe_ms_max"], "rescore_ms": 0.0, "head_ms": st["head_ms_max"], "build_ms": st["build_ms_max"],
+                "device_posting_visits": st["device_posting_visits"], "candidate_pairs": st["union_pairs"]}
+
+    def clear(self):
+        self.g.clear()
+
+    def relayout_figures(self):
+        lo = self.g.layout()
+        return {"relayouts": lo["relayouts"], "evaluations": lo["evaluations"], "total_relayout_ms": lo["total_relayout_ms"],
+                "relayout_bytes": lo["relayout_bytes"], "head_terms": lo["head_terms"], "layout_rows": lo["layout_rows"]}
+
+
 def summarize(rec):
     a = np.array(rec, dtype=np.float64)
     rows, wall = a[:, 0].sum(), a[:, 1].sum()
@@ -73,6 +114,10 @@ def main():
     ap.add_argument("--sample-calls", type=int, default=1500)
     ap.add_argument("--refcpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-refcpu", action="store_true")
+    ap.add_argument("--engine", choices=("handle", "group"), default="handle")
+    ap.add_argument("--members", type=int, default=4, help="--engine group: term-range members")
+    ap.add_argument("--devices", default=None, help="--engine group: comma-separated device of every member (default: all on 0)")
+    ap.add_argument("--no-adapt", action="store_true", help="--engine group: without APSS_GROUP_ADAPT_LAYOUT")
     a = ap.parse_args()
     import torch
     from apss import synth
@@ -82,15 +127,21 @@ def main():
         cfg["n"] = a.rows
     n, dim, theta = cfg["n"], cfg["dim"], cfg["theta"]
     rp, idx, val = synth.make_vectors(n, dim, cfg["nnz"], cfg["zipf_s"], cfg["seed"])
+    if a.engine == "group":
+        devices = [int(x) for x in a.devices.split(",")] if a.devices else [0] * a.members
+        make = lambda: GroupStream(dim, theta, devices, not a.no_adapt)  # noqa: E731
+    else:
+        make = lambda: ApssIndex(dim, theta, capacity_rows=n, capacity_nnz=idx.size)  # noqa: E731
     dev = torch.device("cuda", 0)
     d_rp, d_idx, d_val = torch.from_numpy(rp).to(dev), torch.from_numpy(idx).to(dev), torch.from_numpy(val.astype(np.float32)).to(dev)
     d_ids = torch.arange(n, dtype=torch.int64, device=dev)
     df2 = float(synth.workload_counts(dim, rp, idx)[1])
     out = {"metric": "streaming IndexData batches (store grows 0 -> N): vectors/s and scored candidate pairs/s per batch size",
            "config": {"workload": "%s: N=%d dim=%d nnz=%d theta=%g" % (a.workload, n, dim, cfg["nnz"], theta)},
+           "engine": a.engine if a.engine == "handle" else "group of %d members, adaptive layout %s" % (a.members, "off" if a.no_adapt else "on"),
            "posting_visits_whole_store_join": df2, "posting_visits_stream_expected": "~ (sum df^2 + postings) / 2 = %.4g" % ((df2 + idx.size) / 2)}
     # the whole store as ONE batch, for scale (bench.py's step)
-    with ApssIndex(dim, theta, capacity_rows=n, capacity_nnz=idx.size) as ix:
+    with make() as ix:
         rec = stream_gpu(cfg, d_ids, d_rp, d_idx, d_val, n, n, ix)
         ix.clear()
         rec = stream_gpu(cfg, d_ids, d_rp, d_idx, d_val, n, n, ix)
@@ -99,9 +150,12 @@ def main():
     rows = {}
     for B in [int(x) for x in a.batches.split(",")]:
         if B >= a.full_below:
-            with ApssIndex(dim, theta, capacity_rows=n, capacity_nnz=idx.size) as ix:
+            with make() as ix:
                 rec = stream_gpu(cfg, d_ids, d_rp, d_idx, d_val, B, n, ix)
+                relayout = ix.relayout_figures() if a.engine == "group" else None
             s = summarize(rec)
+            if relayout:
+                s.update(relayout)
             s["mode"] = "streamed whole"
             # every unordered pair is found once by the later vector (+ both directions inside a batch): between half and all
             s["result_pairs_vs_whole_store_join"] = s["result_pairs"] / max(1, whole_pairs)
@@ -110,7 +164,7 @@ def main():
         else:
             levels = [int(n * (i + 0.5) / a.levels) for i in range(a.levels)]
             per_level = []
-            with ApssIndex(dim, theta, capacity_rows=n, capacity_nnz=idx.size) as ix:
+            with make() as ix:
                 at = 0
                 for lv in levels:
                     if lv > at:
@@ -120,12 +174,15 @@ def main():
                     ss = summarize(rec)
                     ss["store_rows"] = lv
                     per_level.append(ss)
+                relayout = ix.relayout_figures() if a.engine == "group" else None
             wall_per_vec = float(np.mean([1.0 / p["vectors_per_s"] for p in per_level]))
             s = {"mode": "sampled: %d calls at each of %d fill levels" % (a.sample_calls, a.levels), "levels": per_level,
                  "vectors_per_s": 1.0 / wall_per_vec, "wall_s_extrapolated": wall_per_vec * n,
                  "ms_per_call_mean": float(np.mean([p["ms_per_call_mean"] for p in per_level])),
                  "ms_per_call_p50": float(np.mean([p["ms_per_call_p50"] for p in per_level])),
                  "candidate_pairs_per_s": float(np.mean([p["candidate_pairs_per_s"] for p in per_level]))}
+            if relayout:
+                s.update(relayout)
         rows[str(B)] = s
     out["batch_size"] = rows
     if not a.no_refcpu:

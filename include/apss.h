@@ -241,6 +241,17 @@ int32_t apss_get_head_terms(apss_handle *h, int32_t capacity, int32_t *out_terms
 /* device views of the external ids: int64[rows] of the store, int64[query rows] of the last query batch (NULL before
  * any query-type call / after an insert); valid until the next insert, query-type call or clear */
 int32_t apss_ext_ids_dev(apss_handle *h, const int64_t **d_store_ext, const int64_t **d_query_ext);
+/* device views of the stored CSR: int64[rows + 1] row offsets (from 0), int32[nnz] terms, float[nnz] weights -- the rows as they
+ * are scored (after normalisation, value prune and admission; a term shard holds only its range of every row).  NULL views
+ * when the store is empty; valid until the next insert or clear */
+int32_t apss_get_store_dev(apss_handle *h, const int64_t **d_rowptr, const int32_t **d_indices, const float **d_values,
+                       int64_t *rows, int64_t *nnz);
+/* as apss_insert_dev, for rows that ALREADY passed this configuration's ingest filters (rows of some handle's store, e.g.
+ * reassembled from term shards): no normalisation, value prune or admission is applied again (a pruned row re-normalised
+ * would change, an admission test on its pruned sum could drop it).  A term shard still keeps its range of every row and
+ * takes its sub-norms and dense-head rows from the whole rows it is handed */
+int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_indices,
+                               const float *d_values, const int64_t *d_ext_ids);
 
 /* =====================================================================================================================
  * apss_group: the term-sharded index of one node -- T member shards, one per GPU -- behind ONE object.
@@ -250,7 +261,8 @@ int32_t apss_ext_ids_dev(apss_handle *h, const int64_t **d_store_ext, const int6
  * to maxIndexEntryActorNum IndexingWorkerActors by dim % maxIndexEntryActorNum (EntryProxyActor.scala:37-49), and every
  * worker handles IndexData on its own (IndexingWorkerActor.scala:122-137), re-scoring the full vectors it was sent.  A group
  * is that fan-out and its workers on the GPUs of one node: member g owns a contiguous term RANGE (cut on the first batch,
- * balanced by sum df^2), stores only that slice of every vector and runs the member-local phase of the join; the group
+ * balanced by sum df^2; re-cut as the store grows with APSS_GROUP_ADAPT_LAYOUT), stores only that slice of every vector
+ * and runs the member-local phase of the join; the group
  * combines the members' answers with the exchange the reference does not need because it replicates whole vectors:
  *
  *   1. every member, concurrently (one host thread per member): apss_insert_and_query_dev / apss_query_dev on its shard
@@ -276,6 +288,9 @@ typedef struct apss_group apss_group;
                                         term space and whose answer is already final (test hook: the RCCL path on one GPU) */
 #define APSS_GROUP_NO_RCCL 2u        /* never load RCCL: combine the members with device-to-device copies (peer access or staging
                                         through the host) even when every member has its own GPU */
+#define APSS_GROUP_ADAPT_LAYOUT 4u   /* re-decide the layout as the store grows: before an insert-type call that brings the store to
+                                        max(1024, 2 x layout_rows) rows, cuts and head are decided again on the store plus the
+                                        batch and the store is rebuilt in the new layout (apss_group_relayout) */
 
 #define APSS_EXCHANGE_NONE 0   /* one member, its answer is final */
 #define APSS_EXCHANGE_COPIES 1 /* device-to-device copies + summing kernel (members share a device, or APSS_GROUP_NO_RCCL) */
@@ -309,6 +324,24 @@ typedef struct apss_group_stats {
   int32_t term_cuts[APSS_GROUP_MAX_MEMBERS + 1]; /* member g owns terms [term_cuts[g], term_cuts[g + 1]) (head terms excepted) */
 } apss_group_stats;
 
+/* the group's layout and the history of its re-layouts (apss_group_layout_get; struct_size as apss_stats) */
+typedef struct apss_group_layout {
+  int32_t struct_size;        /* IN: sizeof(apss_group_layout) of the caller; OUT: bytes written */
+  int32_t n_members;
+  int64_t layout_rows;        /* store rows (plus the batch that triggered it) the current layout was decided on */
+  int64_t next_eval_rows;     /* APSS_GROUP_ADAPT_LAYOUT: an insert-type call that brings the store to this many rows re-decides
+                                 (0: the flag is off, or nothing about the layout can change) */
+  int64_t evaluations;        /* layout decisions since create, the first batch's excepted (schedule checks and apss_group_relayout) */
+  int64_t relayouts;          /* ... of those, the ones that rebuilt the store (the decision differed from the layout in place) */
+  double last_relayout_ms;    /* wall time of the last evaluation (decision + rebuild) */
+  double total_relayout_ms;   /* ... summed over every evaluation */
+  int64_t relayout_bytes;     /* bytes copied between the members' devices to reassemble whole rows, in total */
+  int32_t head_terms;         /* terms of the shared dense-head block (0: none) */
+  int32_t term_cuts[APSS_GROUP_MAX_MEMBERS + 1];
+  double dfsq[APSS_GROUP_MAX_MEMBERS]; /* per member: sum of df^2 over the stored rows' tail terms in its range (what the
+                                          balanced cuts even out), computed on the device at this call */
+} apss_group_layout;
+
 /* n_members >= 1 shards on the HIP devices device_ids[0 .. n_members) (a device may appear more than once) */
 int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32_t *device_ids, uint32_t group_flags,
                           apss_group **out);
@@ -333,9 +366,20 @@ int32_t apss_group_insert_and_query_dev(apss_group *g, int64_t n, int64_t nnz, c
                                         const int32_t *const *d_indices, const float *const *d_values,
                                         const int64_t *const *d_ext_ids, int64_t *n_results);
 /* drop index and store of every member; the reservations and the LAYOUT stay -- term cuts and dense-head terms, whether named
- * by the caller or decided from the first batch the group ever saw (they are configuration, like apss_set_head_terms on a
- * handle: a benchmark step re-runs build + join on the same layout); a new layout needs a new group */
+ * by the caller or decided from the batches so far, and layout_rows (they are configuration, like apss_set_head_terms on a
+ * handle: a benchmark step re-runs build + join on the same layout and does not re-layout).  A new layout comes from
+ * apss_group_relayout, from APSS_GROUP_ADAPT_LAYOUT as the store grows, or from a new group */
 int32_t apss_group_clear(apss_group *g);
+/* Re-decide the layout now, from the stored rows.  cuts == NULL: term cuts balanced by sum df^2 over the store's tail terms
+ * (equal widths below 1024 rows) unless they were named (apss_group_set_term_cuts), and the dense head from the library's
+ * policy on a sample of up to 131072 whole rows; non-NULL: these cuts (the contract of apss_group_set_term_cuts) and only the
+ * head is re-decided (the next schedule check or NULL call may cut again, unless cuts were named before the first insert).  A layout that differs from the one in place is BUILT, then
+ * swapped: the members' slices are reassembled into whole rows on every device that holds a member, new member handles are
+ * filled from them (apss_insert_stored_dev) and only when every member succeeded are the old ones destroyed -- so for a
+ * moment each member's store exists twice.  A failure leaves the old layout and store untouched and returns the member's
+ * error.  The results of the last query-type call are gone afterwards.  APSS_E_STATE on a group without rows. */
+int32_t apss_group_relayout(apss_group *g, const int32_t *cuts);
+int32_t apss_group_layout_get(apss_group *g, apss_group_layout *out);
 
 int32_t apss_group_result_count(const apss_group *g, int64_t *n_results);
 /* (query ext id, candidate ext id, score) of the last query-type call, as apss_fetch_results */
