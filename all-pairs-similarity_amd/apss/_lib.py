@@ -23,8 +23,11 @@ SYMBOLS = [
     "apss_group_query", "apss_group_insert_and_query", "apss_group_insert_and_query_dev", "apss_group_clear",
     "apss_group_result_count", "apss_group_fetch_results", "apss_group_stats_get", "apss_group_member_stats",
     "apss_group_relayout", "apss_group_layout_get",
+    # T x D grids of term ranges x row ranges
+    "apss_group_create_grid", "apss_group_grid_get",
 ]
 GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
+GROUP_NO_SYMMETRIC_RANGES = 8
 EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
 GROUP_MAX_MEMBERS = 64
 DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
@@ -66,6 +69,13 @@ class GroupLayout(C.Structure):
                 ("evaluations", C.c_int64), ("relayouts", C.c_int64), ("last_relayout_ms", C.c_double),
                 ("total_relayout_ms", C.c_double), ("relayout_bytes", C.c_int64), ("head_terms", C.c_int32),
                 ("term_cuts", C.c_int32 * (GROUP_MAX_MEMBERS + 1)), ("dfsq", C.c_double * GROUP_MAX_MEMBERS)]
+
+
+class GroupGrid(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_term_ranges", C.c_int32), ("n_row_ranges", C.c_int32),
+                ("symmetric_ranges", C.c_int32), ("rows_in_range", C.c_int64 * GROUP_MAX_MEMBERS),
+                ("outside_rows_max", C.c_int64), ("mirrored_pairs", C.c_int64), ("own_ms_max", C.c_double),
+                ("outside_ms_max", C.c_double)]
 
 
 def build_sources():
@@ -180,6 +190,10 @@ def lib():
     L.apss_insert_stored_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.apss_group_create.restype = i32
     L.apss_group_create.argtypes = [C.POINTER(Config), i32, vp, C.c_uint32, C.POINTER(vp)]
+    L.apss_group_create_grid.restype = i32
+    L.apss_group_create_grid.argtypes = [C.POINTER(Config), i32, i32, vp, C.c_uint32, C.POINTER(vp)]
+    L.apss_group_grid_get.restype = i32
+    L.apss_group_grid_get.argtypes = [vp, C.POINTER(GroupGrid)]
     L.apss_group_destroy.restype = None
     L.apss_group_destroy.argtypes = [vp]
     L.apss_group_last_error.restype = C.c_char_p

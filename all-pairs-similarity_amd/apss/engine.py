@@ -200,10 +200,12 @@ class ApssGroup:
     """Python face of apss_group (include/apss.h): the term-sharded index of one node -- `devices[i]` holds member i's
     term range -- behind one object; the members' exchange (all-gather of candidate lists, all-reduce of partial scores)
     runs below the C ABI (RCCL when every member has its own GPU, device-to-device copies when members share one).
-    Mirrors WriteWorkerActor.scala:164-183 + EntryProxyActor.scala:37-49 + IndexingWorkerActor.scala:122-137."""
+    Mirrors WriteWorkerActor.scala:164-183 + EntryProxyActor.scala:37-49 + IndexingWorkerActor.scala:122-137.
+    row_ranges = D > 1: a T x D grid (apss_group_create_grid), T = len(devices) / D term ranges x D row ranges, member
+    (j, i) = row range j, term range i on devices[j * T + i]; every call answers as one plain handle would."""
 
     def __init__(self, dim, theta, devices, flags=0, index_threshold=0.0, tile_rows=0, head_terms=0, group_flags=0,
-                 term_cuts=None, capacity_rows=0, capacity_nnz=0):
+                 term_cuts=None, capacity_rows=0, capacity_nnz=0, row_ranges=1):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -212,15 +214,21 @@ class ApssGroup:
         cfg.capacity_rows, cfg.capacity_nnz = int(capacity_rows), int(capacity_nnz)
         devs = _np(devices, np.int32)
         g = C.c_void_p()
-        rc = L.apss_group_create(C.byref(cfg), devs.size, _ptr(devs), int(group_flags), C.byref(g))
+        row_ranges = int(row_ranges)
+        if row_ranges >= 1 and devs.size % row_ranges:
+            raise ValueError("len(devices) must be term ranges x row_ranges")
+        # (row_ranges = 1 goes through apss_group_create_grid too: the two entry points are one)
+        rc = L.apss_group_create_grid(C.byref(cfg), devs.size // row_ranges if row_ranges >= 1 else 0, row_ranges, _ptr(devs),
+                                      int(group_flags), C.byref(g))
         if rc != _lib.OK:
             raise ApssError(rc, (L.apss_group_last_error(None) or b"").decode())
         self._g, self._L = g, L
         self.dim, self.theta, self.n_members = int(dim), float(theta), int(devs.size)
+        self.row_ranges, self.term_ranges = row_ranges, int(devs.size) // row_ranges
         if term_cuts is not None:
             cuts = _np(term_cuts, np.int32)
-            if cuts.size != devs.size + 1:
-                raise ValueError("term_cuts must have n_members + 1 entries")
+            if cuts.size != self.term_ranges + 1:
+                raise ValueError("term_cuts must have one entry more than there are term ranges")
             self._chk(L.apss_group_set_term_cuts(self._g, _ptr(cuts)))
 
     def close(self):
@@ -294,7 +302,16 @@ class ApssGroup:
         st.struct_size = C.sizeof(_lib.GroupStats)
         self._chk(self._L.apss_group_stats_get(self._g, C.byref(st)))
         d = {k: getattr(st, k) for k, _ in _lib.GroupStats._fields_}
-        d["term_cuts"] = list(st.term_cuts[: self.n_members + 1])
+        d["term_cuts"] = list(st.term_cuts[: self.term_ranges + 1])
+        return d
+
+    def grid(self):
+        """the grid's shape and what its row ranges did in the last call (apss_group_grid_get)"""
+        gr = _lib.GroupGrid()
+        gr.struct_size = C.sizeof(_lib.GroupGrid)
+        self._chk(self._L.apss_group_grid_get(self._g, C.byref(gr)))
+        d = {k: getattr(gr, k) for k, _ in _lib.GroupGrid._fields_}
+        d["rows_in_range"] = list(gr.rows_in_range[: self.row_ranges])
         return d
 
     def relayout(self, cuts=None):
@@ -304,8 +321,8 @@ class ApssGroup:
             self._chk(self._L.apss_group_relayout(self._g, None))
             return
         cuts = _np(cuts, np.int32)
-        if cuts.size != self.n_members + 1:
-            raise ValueError("cuts must have n_members + 1 entries")
+        if cuts.size != self.term_ranges + 1:
+            raise ValueError("cuts must have one entry more than there are term ranges")
         self._chk(self._L.apss_group_relayout(self._g, _ptr(cuts)))
 
     def layout(self):
@@ -314,7 +331,7 @@ class ApssGroup:
         lo.struct_size = C.sizeof(_lib.GroupLayout)
         self._chk(self._L.apss_group_layout_get(self._g, C.byref(lo)))
         d = {k: getattr(lo, k) for k, _ in _lib.GroupLayout._fields_}
-        d["term_cuts"] = list(lo.term_cuts[: self.n_members + 1])
+        d["term_cuts"] = list(lo.term_cuts[: self.term_ranges + 1])
         d["dfsq"] = list(lo.dfsq[: self.n_members])
         return d
 

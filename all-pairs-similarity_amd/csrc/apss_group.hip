@@ -1,4 +1,5 @@
-// apss_group.hip -- the term-sharded index of one node behind ONE object of the C ABI (include/apss.h, apss_group_*).
+// apss_group.hip -- the sharded index of one node (T term ranges x D row ranges) behind ONE object of the C ABI
+// (include/apss.h, apss_group_*).
 //
 // What the reference does with actors -- WriteWorkerActor buckets a vector by dim % maxShardNum and flushes a DataPacket per
 // shard (WriteWorkerActor.scala:164-183), EntryProxyActor fans it out to the IndexingWorkerActors by
@@ -6,6 +7,9 @@
 // (IndexingWorkerActor.scala:122-137) -- with the workers resident on the GPUs of one node: member g = one shard handle
 // (apss_hip.hip) on one device, one host thread per member for the member-local phase, and the exchange of the members'
 // answers (all-gather of candidate lists, all-reduce(SUM) of per-candidate partial scores) over RCCL on the members' streams.
+// A grid (apss_group_create_grid, D > 1 row ranges) runs that exchange INSIDE each row range, once per phase: the row range's
+// own span of the batch (insert-and-query), then one outside batch made of the other spans (query); the phases' results are
+// gathered as (ext, ext, score) triples per row range.
 // This file only uses the public handle ABI; it holds no index state of its own.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -240,6 +245,73 @@ __global__ __launch_bounds__(256) void k_merge_slice(const int64_t *rowptr, cons
   }
 }
 
+// ---- grids: the spans of a device-resident batch.  A phase's batch is a concatenation of contiguous row spans of the whole
+// batch (one span: a row range's own rows; several: its outside batch), described by a small table passed by value.
+constexpr int kMaxSpans = APSS_GROUP_MAX_MEMBERS;
+struct SpanBounds {
+  int32_t n;
+  int64_t row[kMaxSpans + 1];
+};
+struct SpanTable {
+  int32_t n;                       // spans, in output order (each with at least one row)
+  int64_t src_row[kMaxSpans];      // first row of span s in the whole batch
+  int64_t src_ent[kMaxSpans];      // ... its first entry
+  int64_t out_row[kMaxSpans + 1];  // first row of span s in the output; [n] = rows of the output
+  int64_t out_ent[kMaxSpans + 1];  // first entry of span s in the output; [n] = entries of the output
+};
+
+// the batch's row offsets at the span boundaries (b.row[k] <= n rows), for the one small read-back of a call
+__global__ void k_span_offsets(const int64_t *rowptr, SpanBounds b, int64_t *out) {
+  const int t = (int)threadIdx.x;
+  if (t < b.n) out[t] = rowptr[b.row[t]];
+}
+
+// rows of the output: rebased row offsets and external ids, span after span
+__global__ void k_concat_rows(const int64_t *rowptr, const int64_t *ext, SpanTable t, int64_t *out_rowptr, int64_t *out_ext) {
+  const int64_t rows = t.out_row[t.n];
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= rows; r += (int64_t)gridDim.x * blockDim.x) {
+    if (r == rows) {
+      out_rowptr[r] = t.out_ent[t.n];
+      continue;
+    }
+    int s = 0;
+    while (s + 1 < t.n && t.out_row[s + 1] <= r) ++s;
+    const int64_t src = t.src_row[s] + (r - t.out_row[s]);
+    out_rowptr[r] = rowptr[src] - t.src_ent[s] + t.out_ent[s];
+    out_ext[r] = ext[src];
+  }
+}
+
+// entries of the output: a span's entries are one contiguous run of the whole batch
+__global__ void k_concat_entries(const int32_t *idx, const float *val, SpanTable t, int32_t *out_idx, float *out_val) {
+  const int64_t total = t.out_ent[t.n];
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    int s = 0;
+    while (s + 1 < t.n && t.out_ent[s + 1] <= e) ++s;  // (a span of empty rows shares its offset with the next: skipped)
+    const int64_t src = t.src_ent[s] + (e - t.out_ent[s]);
+    out_idx[e] = idx[src];
+    out_val[e] = val[src];
+  }
+}
+
+// a phase's results as (query ext id, candidate ext id, score) triples, appended to the row range's list; a mirrored phase
+// (the symmetry across row ranges) reports every pair in the other direction as well, n entries further on
+__global__ void k_triples(const int32_t *q_row, const int32_t *c_slot, const float *score, const int64_t *q_ext, const int64_t *c_ext,
+                          int64_t n, int mirrored, int64_t *out_q, int64_t *out_c, float *out_s) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t q = q_ext[q_row[i]], c = c_ext[c_slot[i]];
+    const float sc = score[i];
+    out_q[i] = q;
+    out_c[i] = c;
+    out_s[i] = sc;
+    if (mirrored) {
+      out_q[n + i] = c;
+      out_c[n + i] = q;
+      out_s[n + i] = sc;
+    }
+  }
+}
+
 inline unsigned grid_for(int64_t n, int threads = 256, int64_t cap = 4096) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div(n, threads)));
 }
@@ -261,11 +333,35 @@ struct apss_group {
     double member_ms = 0, partial_ms = 0;
     int32_t rc = APSS_OK;
     std::string err;
+    // the call's sums over its phases (a grid's own join and outside batch; one phase otherwise)
+    int64_t visits = 0, dev_visits = 0, touched = 0, cand_sum = 0, cand_max = 0;
+    double probe_ms = 0, head_ms = 0;
+    // grids, device-pointer entry: the phases' batches cut out of the whole batch on this device ([0] own span, [1] outside)
+    DevBuf<int64_t> sp_rowptr[2], sp_ext[2], sp_off;
+    DevBuf<int32_t> sp_idx[2];
+    DevBuf<float> sp_val[2];
+  };
+  // one row range: its T members hold the same rows; its buffers live on its first member's device
+  struct Range {
+    int64_t rows = 0;
+    // results of the phase in flight (exchange modes): query row of the phase's batch, candidate slot, score
+    DevBuf<int32_t> res_q, res_c;
+    DevBuf<float> res_s;
+    int64_t n_phase = 0;
+    // grids: the call's results as triples, phase after phase
+    DevBuf<int64_t> tri_q, tri_c;
+    DevBuf<float> tri_s;
+    int64_t n_tri = 0;
+    int64_t union_pairs = 0, gather_bytes = 0, mirrored = 0, outside_rows = 0;
+    double own_ms = 0, outside_ms = 0, exchange_ms = 0;
   };
   apss_config cfg{};
   uint32_t flags = 0;
-  int T = 0;
+  int T = 0;  // term ranges
+  int D = 1;  // row ranges; member (j, i) = row range j, term range i = m[j * T + i]
   std::vector<Member> m;
+  std::vector<Range> rr;
+  bool symmetric_ranges = false;  // the last query-type call used half spans and mirrored
   std::string err;
   bool created = false;         // the members' handles exist (the layout is decided)
   bool cuts_named = false;      // apss_group_set_term_cuts
@@ -279,9 +375,7 @@ struct apss_group {
   int64_t evaluations = 0, relayouts = 0, relayout_bytes = 0;
   double last_relayout_ms = 0, total_relayout_ms = 0;
   int relayout_fail = -1;  // APSS_DEBUG=relayout_fail=<member>: that member's insert of a re-layout fails (test hook)
-  // results of the last query-type call (exchange modes): on member 0's device
-  DevBuf<int32_t> res_q, res_c;
-  DevBuf<float> res_s;
+  // results of the last query-type call: D = 1, exchange modes: rr[0].res_* on member 0's device; grids: the ranges' triples
   DevBuf<int64_t> ext_q, ext_c;
   int64_t n_res = -1;
   bool results_in_handle = false;  // one member, no exchange: the handle's own result list
@@ -315,6 +409,27 @@ int32_t ensure(apss_group::Member &M, DevBuf<T> &b, size_t n) {
     b.cap = 0;
   }
   GHIP(nullptr, M, hipMalloc((void **)&b.p, ncap * sizeof(T)));
+  b.cap = ncap;
+  return APSS_OK;
+}
+
+// the same for a buffer that is appended to: the first `used` elements survive the growth
+template <class T>
+int32_t ensure_keep(apss_group::Member &M, DevBuf<T> &b, size_t n, size_t used) {
+  if (n <= b.cap && b.p) return APSS_OK;
+  const size_t ncap = std::max<size_t>(std::max(n, b.cap + b.cap / 2), 256);
+  T *np = nullptr;
+  GHIP(nullptr, M, hipMalloc((void **)&np, ncap * sizeof(T)));
+  if (b.p) {
+    hipError_t e = used ? hipMemcpyAsync(np, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, M.stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(M.stream);
+    if (e != hipSuccess) {
+      (void)hipFree(np);
+      GHIP(nullptr, M, e);
+    }
+    GHIP(nullptr, M, hipFree(b.p));
+  }
+  b.p = np;
   b.cap = ncap;
   return APSS_OK;
 }
@@ -475,10 +590,12 @@ int32_t decide_layout(apss_group *g, std::vector<uint32_t> &df, int64_t n_rows, 
   return APSS_OK;
 }
 
-// member i's shard handle for a layout, on the member's stream (*out stays NULL on failure; the message is in err)
-int32_t create_member_handle(apss_group *g, int i, const Layout &L, apss_handle **out, std::string &err) {
+// member m's shard handle for a layout (term range m % T), on the member's stream (*out stays NULL on failure; the message
+// is in err)
+int32_t create_member_handle(apss_group *g, int m, const Layout &L, apss_handle **out, std::string &err) {
   const int T = g->T;
-  apss_group::Member &M = g->m[(size_t)i];
+  const int i = m % T;
+  apss_group::Member &M = g->m[(size_t)m];
   *out = nullptr;
   apss_config c = g->cfg;
   c.struct_size = (int32_t)sizeof(apss_config);
@@ -504,8 +621,9 @@ int32_t create_member_handle(apss_group *g, int i, const Layout &L, apss_handle 
   return APSS_OK;
 }
 
-// Decide the layout from the first batch, then create the members' shard handles, their streams and -- when every member has
-// its own GPU -- the RCCL communicators.
+// Decide the layout from the first batch (the WHOLE batch, all spans of a grid: one set of cuts and one head for every row
+// range), then create the members' shard handles and -- when the members of every row range have a GPU each -- the RCCL
+// communicators.
 int32_t create_members(apss_group *g, const Batch &b) {
   const int T = g->T;
   std::vector<uint32_t> df;
@@ -521,21 +639,23 @@ int32_t create_members(apss_group *g, const Batch &b) {
   if (rc != APSS_OK) return rc;
   g->cuts = L.cuts;
   g->head = L.head;
-  for (int i = 0; i < T; ++i) {
+  for (int m = 0; m < T * g->D; ++m) {
     std::string err;
-    if ((rc = create_member_handle(g, i, L, &g->m[(size_t)i].h, err)) != APSS_OK) return gfail(g, rc, err);
+    if ((rc = create_member_handle(g, m, L, &g->m[(size_t)m].h, err)) != APSS_OK) return gfail(g, rc, err);
   }
   const bool exchange_needed = T > 1 || (g->flags & APSS_GROUP_FORCE_EXCHANGE);
   g->exchange = !exchange_needed ? APSS_EXCHANGE_NONE : APSS_EXCHANGE_COPIES;
   if (exchange_needed && g->distinct_devices && !(g->flags & APSS_GROUP_NO_RCCL)) {
     Rccl *r = load_rccl();
     if (!r->lib) return gfail(g, APSS_E_UNSUPPORTED, "RCCL exchange: " + r->err + " (APSS_GROUP_NO_RCCL combines the members by copies)");
-    std::vector<ncclComm_t> comms((size_t)T, nullptr);
-    std::vector<int> devs;
-    for (const apss_group::Member &M : g->m) devs.push_back(M.dev);
-    const ncclResult_t nr = r->CommInitAll(comms.data(), T, devs.data());
-    if (nr != ncclSuccess) return gfail(g, APSS_E_DEVICE, std::string("ncclCommInitAll: ") + r->GetErrorString(nr));
-    for (int i = 0; i < T; ++i) g->m[(size_t)i].comm = comms[(size_t)i];
+    for (int j = 0; j < g->D; ++j) {  // one communicator per row range
+      std::vector<ncclComm_t> comms((size_t)T, nullptr);
+      std::vector<int> devs;
+      for (int i = 0; i < T; ++i) devs.push_back(g->m[(size_t)(j * T + i)].dev);
+      const ncclResult_t nr = r->CommInitAll(comms.data(), T, devs.data());
+      if (nr != ncclSuccess) return gfail(g, APSS_E_DEVICE, std::string("ncclCommInitAll: ") + r->GetErrorString(nr));
+      for (int i = 0; i < T; ++i) g->m[(size_t)(j * T + i)].comm = comms[(size_t)i];
+    }
     g->exchange = APSS_EXCHANGE_RCCL;
   }
   g->layout_rows = b.n;
@@ -545,29 +665,174 @@ int32_t create_members(apss_group *g, const Batch &b) {
 
 // ---- one member's share of a call; every member thread runs this, the barriers keep the phases in step.  A failure is
 // published BEFORE the next barrier, and every thread acts on the flag as the barrier returned it: they leave (or skip a
-// collective) together.
+// collective) together.  A grid has one barrier per row range (its T members are a term-sharded group of their own and never
+// wait for another row range) and ONE failure flag for all T x D threads.
+
+// a phase's batch as ONE member reads it (host form: values; device form, on the member's device: d_values)
+struct MemberBatch {
+  int64_t n = 0, nnz = 0;
+  const int64_t *rowptr = nullptr;
+  const int32_t *indices = nullptr;
+  const double *values = nullptr;
+  const float *d_values = nullptr;
+  const int64_t *ext = nullptr;
+  bool on_device = false;
+};
+
+// a CSR cut out of a host batch
+struct HostCsr {
+  std::vector<int64_t> rowptr, ext;
+  std::vector<int32_t> idx;
+  std::vector<double> val;
+};
+
+// what one row range does in a call
+struct RangePlan {
+  int span = 0;              // the span of the batch this row range stores
+  std::vector<int> outside;  // the spans of its outside batch, in span order
+  bool mirrored = false;     // the outside phase's pairs are reported in both directions
+  int64_t out_rows = 0;
+  HostCsr own, out;          // host-pointer entry points: sliced by the caller's thread before the members start
+};
+
 struct CallCtx {
   apss_group *g;
   int mode;  // 0 insert, 1 query (frozen index), 2 insert-and-query
   Batch b;
-  Barrier *bar;
+  std::vector<Barrier *> bar;    // per row range
+  std::vector<int64_t> span_lo;  // grids: span k = rows [span_lo[k], span_lo[k + 1]) of the batch
+  std::vector<RangePlan> plan;   // grids: per row range
   std::atomic<int> failed{0};
-  double exchange_ms = 0;
 };
 
-int32_t member_phase1(apss_group::Member &M, int i, CallCtx &cx) {
-  const Batch &b = cx.b;
+MemberBatch whole_batch(const Batch &b, int m) {
+  MemberBatch mb;
+  mb.n = b.n;
+  mb.nnz = b.nnz;
+  mb.on_device = b.on_device;
+  if (!b.on_device) {
+    mb.rowptr = b.rowptr;
+    mb.indices = b.indices;
+    mb.values = b.values;
+    mb.ext = b.ext;
+  } else if (b.n > 0) {
+    mb.rowptr = b.d_rowptr[m];
+    mb.indices = b.d_indices[m];
+    mb.d_values = b.d_values[m];
+    mb.ext = b.d_ext[m];
+  }
+  return mb;
+}
+
+MemberBatch host_csr_batch(const HostCsr &c) {
+  MemberBatch mb;
+  mb.n = (int64_t)c.ext.size();
+  mb.nnz = (int64_t)c.idx.size();
+  mb.rowptr = c.rowptr.data();
+  mb.indices = c.idx.data();
+  mb.values = c.val.data();
+  mb.ext = c.ext.data();
+  return mb;
+}
+
+// rows [lo, hi) of a host batch, appended to a CSR
+void append_span(HostCsr &c, const Batch &b, int64_t lo, int64_t hi) {
+  if (c.rowptr.empty()) c.rowptr.push_back(0);
+  const int64_t shift = (int64_t)c.idx.size() - b.rowptr[lo];
+  for (int64_t r = lo; r < hi; ++r) c.rowptr.push_back(b.rowptr[r + 1] + shift);
+  c.ext.insert(c.ext.end(), b.ext + lo, b.ext + hi);
+  if (b.rowptr[hi] > b.rowptr[lo]) {
+    c.idx.insert(c.idx.end(), b.indices + b.rowptr[lo], b.indices + b.rowptr[hi]);
+    c.val.insert(c.val.end(), b.values + b.rowptr[lo], b.values + b.rowptr[hi]);
+  }
+}
+
+// grids, device-pointer entry: this member's copies of its row range's span (slot 0) and outside batch (slot 1), cut out of
+// the whole batch resident on its device.  Only the batch's row offsets at the span boundaries come back to the host.
+int32_t member_slice(apss_group::Member &M, const CallCtx &cx, const MemberBatch &whole, const RangePlan &P, MemberBatch out[2]) {
+  const int D = cx.g->D;
+  SpanBounds sb{};
+  sb.n = D + 1;
+  for (int k = 0; k <= D; ++k) sb.row[k] = cx.span_lo[(size_t)k];
+  int32_t rc;
+  if ((rc = ensure(M, M.sp_off, (size_t)kMaxSpans + 1)) != APSS_OK) return rc;
+  hipLaunchKernelGGL(k_span_offsets, dim3(1), dim3(128), 0, M.stream, whole.rowptr, sb, M.sp_off.p);
+  GHIP(nullptr, M, hipGetLastError());
+  int64_t ent[kMaxSpans + 1];
+  GHIP(nullptr, M, hipMemcpyAsync(ent, M.sp_off.p, (size_t)(D + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
+  GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+  bool sane = ent[0] == 0 && ent[D] == whole.nnz;
+  for (int k = 0; k < D; ++k) sane = sane && ent[k] <= ent[k + 1];
+  if (!sane) {  // (the gathers below read entries [ent[k], ent[k + 1]) of arrays that are nnz long)
+    M.err = "d_rowptr is not the row offsets of a batch of nnz entries";
+    return APSS_E_INVALID;
+  }
+  for (int slot = 0; slot < 2; ++slot) {
+    SpanTable t{};
+    std::vector<int> one(1, P.span);
+    for (int k : slot == 0 ? one : P.outside) {
+      const int64_t lo = cx.span_lo[(size_t)k], hi = cx.span_lo[(size_t)k + 1];
+      if (hi == lo) continue;
+      t.src_row[t.n] = lo;
+      t.src_ent[t.n] = ent[k];
+      t.out_row[t.n + 1] = t.out_row[t.n] + (hi - lo);
+      t.out_ent[t.n + 1] = t.out_ent[t.n] + (ent[k + 1] - ent[k]);
+      ++t.n;
+    }
+    MemberBatch &o = out[slot];
+    o = MemberBatch{};
+    o.on_device = true;
+    if (t.n == 0) continue;
+    o.n = t.out_row[t.n];
+    o.nnz = t.out_ent[t.n];
+    if ((rc = ensure(M, M.sp_rowptr[slot], (size_t)o.n + 1)) != APSS_OK) return rc;
+    if ((rc = ensure(M, M.sp_ext[slot], (size_t)o.n)) != APSS_OK) return rc;
+    if ((rc = ensure(M, M.sp_idx[slot], (size_t)std::max<int64_t>(1, o.nnz))) != APSS_OK) return rc;
+    if ((rc = ensure(M, M.sp_val[slot], (size_t)std::max<int64_t>(1, o.nnz))) != APSS_OK) return rc;
+    hipLaunchKernelGGL(k_concat_rows, dim3(grid_for(o.n + 1)), dim3(256), 0, M.stream, whole.rowptr, whole.ext, t, M.sp_rowptr[slot].p,
+                       M.sp_ext[slot].p);
+    GHIP(nullptr, M, hipGetLastError());
+    if (o.nnz > 0) {
+      hipLaunchKernelGGL(k_concat_entries, dim3(grid_for(o.nnz)), dim3(256), 0, M.stream, whole.indices, whole.d_values, t,
+                         M.sp_idx[slot].p, M.sp_val[slot].p);
+      GHIP(nullptr, M, hipGetLastError());
+    }
+    o.rowptr = M.sp_rowptr[slot].p;
+    o.indices = M.sp_idx[slot].p;
+    o.d_values = M.sp_val[slot].p;
+    o.ext = M.sp_ext[slot].p;
+  }
+  return APSS_OK;
+}
+
+// step 1: the handle call of a phase (mode as CallCtx::mode), and what it adds to the member's sums of the call.  A
+// mirrored phase found each pair once and reports it twice: the reference's two-directional probe visits twice as much.
+int32_t member_phase1(apss_group::Member &M, int mode, const MemberBatch &b, bool mirrored) {
   int64_t n_res = 0;
   int32_t rc;
   if (!b.on_device) {
-    if (cx.mode == 0) rc = apss_insert(M.h, b.n, b.rowptr, b.indices, b.values, b.ext);
-    else if (cx.mode == 1) rc = apss_query(M.h, b.n, b.rowptr, b.indices, b.values, b.ext, &n_res);
+    if (mode == 0) rc = apss_insert(M.h, b.n, b.rowptr, b.indices, b.values, b.ext);
+    else if (mode == 1) rc = apss_query(M.h, b.n, b.rowptr, b.indices, b.values, b.ext, &n_res);
     else rc = apss_insert_and_query(M.h, b.n, b.rowptr, b.indices, b.values, b.ext, &n_res);
+  } else if (mode == 1) {
+    rc = apss_query_dev(M.h, b.n, b.nnz, b.rowptr, b.indices, b.d_values, b.ext, &n_res);
   } else {
-    rc = apss_insert_and_query_dev(M.h, b.n, b.nnz, b.d_rowptr[i], b.d_indices[i], b.d_values[i], b.d_ext[i], &n_res);
+    rc = apss_insert_and_query_dev(M.h, b.n, b.nnz, b.rowptr, b.indices, b.d_values, b.ext, &n_res);
   }
   if (rc != APSS_OK) M.err = apss_last_error(M.h);
   M.n_cand = n_res;
+  if (rc == APSS_OK && mode != 0) {
+    apss_stats ms{};
+    ms.struct_size = (int32_t)sizeof(apss_stats);
+    (void)apss_stats_get(M.h, &ms);
+    M.visits += (mirrored ? 2 : 1) * ms.posting_visits;
+    M.dev_visits += ms.device_posting_visits;
+    M.touched += ms.candidate_pairs;
+    M.cand_sum += n_res;
+    M.cand_max = std::max(M.cand_max, n_res);
+    M.probe_ms += ms.probe_ms;
+    M.head_ms += ms.head_ms;
+  }
   return rc;
 }
 
@@ -615,56 +880,93 @@ int32_t member_union(apss_group::Member &M, int64_t total, int key_bits) {
   return APSS_OK;
 }
 
-void member_main(int i, CallCtx *pcx) {
-  CallCtx &cx = *pcx;
+// the phase's results on the row range's first member -- (query row, candidate slot, score), n of them, on M's device -- into
+// the row range's list of triples (grids); the query side's ids are the handle's view of its last query batch
+int32_t append_triples(apss_group::Member &M, apss_group::Range &R, const int32_t *q_row, const int32_t *c_slot, const float *score,
+                       int64_t n, bool mirrored) {
+  if (n == 0) return APSS_OK;
+  const int64_t add = mirrored ? 2 * n : n;
+  const int64_t *d_store = nullptr, *d_query = nullptr;
+  int32_t rc = apss_ext_ids_dev(M.h, &d_store, &d_query);
+  if (rc != APSS_OK || !d_store || !d_query) {
+    M.err = "the member's external ids are gone";
+    return APSS_E_STATE;
+  }
+  if ((rc = ensure_keep(M, R.tri_q, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
+  if ((rc = ensure_keep(M, R.tri_c, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
+  if ((rc = ensure_keep(M, R.tri_s, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
+  hipLaunchKernelGGL(k_triples, dim3(grid_for(n)), dim3(256), 0, M.stream, q_row, c_slot, score, d_query, d_store, n, mirrored ? 1 : 0,
+                     R.tri_q.p + R.n_tri, R.tri_c.p + R.n_tri, R.tri_s.p + R.n_tri);
+  GHIP(nullptr, M, hipGetLastError());
+  GHIP(nullptr, M, hipStreamSynchronize(M.stream));  // (the next phase's handle call replaces the views read here)
+  R.n_tri += add;
+  if (mirrored) R.mirrored += n;
+  return APSS_OK;
+}
+
+// One phase of a call for member m = (row range j, term range i): the handle call on the phase's batch (step 1), then the
+// exchange among the T members of the row range (steps 2-4) and, on a grid, the phase's triples.  A plain group's call is one
+// phase; a grid's insert-and-query is two (its own span, then the outside batch as a query).  false: the call has failed, and
+// every thread of the row range has taken that decision at the same barrier.
+bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirrored) {
   apss_group *g = cx.g;
-  apss_group::Member &M = g->m[(size_t)i];
   const int T = g->T;
+  const int j = m / T, i = m % T;
+  apss_group::Member &M = g->m[(size_t)m];
+  apss_group::Member *peers = &g->m[(size_t)(j * T)];  // the row range's members, by term range
+  apss_group::Range &R = g->rr[(size_t)j];
+  Barrier &bar = *cx.bar[(size_t)j];
   Rccl *r = g->exchange == APSS_EXCHANGE_RCCL ? load_rccl() : nullptr;
-  M.rc = APSS_OK;
-  M.err.clear();
-  M.n_cand = M.n_union = 0;
-  M.member_ms = M.partial_ms = 0;
   auto fail_here = [&](int32_t rc) {
     M.rc = rc;
     cx.failed.store(1);
   };
-  if (hipSetDevice(M.dev) != hipSuccess) {
-    M.err = "hipSetDevice failed";
-    fail_here(APSS_E_DEVICE);
-  }
+  M.n_cand = M.n_union = 0;
+  if (i == 0) R.n_phase = 0;
   const auto t0 = Clock::now();
   if (!cx.failed.load()) {
-    const int32_t rc = member_phase1(M, i, cx);
+    const int32_t rc = member_phase1(M, mode, b, mirrored);
     if (rc != APSS_OK) fail_here(rc);
   }
-  M.member_ms = ms_since(t0);
-  const bool failed_b1 = cx.bar->wait();  // ---- B1: every member's candidate count (or failure) is known
-  if (failed_b1 || cx.mode == 0 || g->exchange == APSS_EXCHANGE_NONE) return;
+  M.member_ms += ms_since(t0);
+  if (bar.wait()) return false;  // ---- B1: every member's candidate count (or failure) is known
+  if (mode == 0) return true;
+  if (g->exchange == APSS_EXCHANGE_NONE) {  // one member per row range: its answer is final
+    R.n_phase = M.n_cand;
+    if (g->D > 1 && M.n_cand > 0) {
+      const int32_t *dq = nullptr, *dc = nullptr;
+      const float *ds = nullptr;
+      int64_t n = 0;
+      int32_t rc = apss_results_dev(M.h, &dq, &dc, &ds, &n);
+      if (rc != APSS_OK) M.err = apss_last_error(M.h);
+      else rc = append_triples(M, R, dq, dc, ds, n, mirrored);
+      if (rc != APSS_OK) fail_here(rc);
+    }
+    return !bar.wait();
+  }
   const auto tx = Clock::now();
-  int64_t total = 0, my_off = 0;
+  int64_t total = 0, my_off = 0, least = INT64_MAX;
   std::vector<int64_t> off((size_t)T + 1, 0);
   for (int k = 0; k < T; ++k) {
     if (k == i) my_off = total;
     off[(size_t)k] = total;
-    total += g->m[(size_t)k].n_cand;
+    total += peers[k].n_cand;
+    least = std::min(least, peers[k].n_cand);
   }
   off[(size_t)T] = total;
-  if (total == 0) {  // nothing to exchange: every member leaves together
-    if (i == 0) g->n_res = 0;
-    return;
-  }
+  if (total == 0) return true;  // nothing to exchange: every member leaves together
+  if (i == 0) R.gather_bytes += 8 * (total - least);
   {
     const int32_t rc = member_pack(M, total, my_off);
     if (rc != APSS_OK) fail_here(rc);
   }
-  if (cx.bar->wait()) return;  // ---- B2: every list is packed
+  if (bar.wait()) return false;  // ---- B2: every list is packed
   // ---- step 2: all-gather of the candidate lists (in place: member k's list sits at off[k] in every member's buffer)
   int32_t rc = APSS_OK;
   if (g->exchange == APSS_EXCHANGE_RCCL) {
     ncclResult_t nr = r->GroupStart();
     for (int k = 0; k < T && nr == ncclSuccess; ++k) {
-      const int64_t nk = g->m[(size_t)k].n_cand;
+      const int64_t nk = peers[k].n_cand;
       if (nk > 0) nr = r->Broadcast(M.keys.p + off[(size_t)k], M.keys.p + off[(size_t)k], (size_t)nk, ncclUint64, k, M.comm, M.stream);
     }
     const ncclResult_t ne = r->GroupEnd();
@@ -675,9 +977,9 @@ void member_main(int i, CallCtx *pcx) {
     }
   } else {
     for (int k = 0; k < T && rc == APSS_OK; ++k) {
-      const int64_t nk = g->m[(size_t)k].n_cand;
+      const int64_t nk = peers[k].n_cand;
       if (k == i || nk == 0) continue;
-      const hipError_t e = hipMemcpyAsync(M.keys.p + off[(size_t)k], g->m[(size_t)k].keys.p + off[(size_t)k], (size_t)nk * sizeof(unsigned long long),
+      const hipError_t e = hipMemcpyAsync(M.keys.p + off[(size_t)k], peers[k].keys.p + off[(size_t)k], (size_t)nk * sizeof(unsigned long long),
                                           hipMemcpyDefault, M.stream);
       if (e != hipSuccess) {
         M.err = std::string("candidate list copy: ") + hipGetErrorString(e);
@@ -687,39 +989,41 @@ void member_main(int i, CallCtx *pcx) {
   }
   // sorted union (the same list in the same order on every member), then this member's exact partial score of every pair
   if (rc == APSS_OK) {
-    int q_bits = 1;
-    while (q_bits < 31 && (1LL << q_bits) < std::max<int64_t>(2, cx.b.n)) ++q_bits;
+    int q_bits = 1;  // (query rows are rows of the PHASE's batch: a span or an outside batch)
+    while (q_bits < 31 && (1LL << q_bits) < std::max<int64_t>(2, b.n)) ++q_bits;
     rc = member_union(M, total, 32 + q_bits);
   }
   if (rc == APSS_OK && M.n_union > 0) {
     const auto tp = Clock::now();
     rc = apss_partial_scores_dev(M.h, M.n_union, M.uq.p, M.uc.p, M.partial.p);  // (synchronises the member's stream)
     if (rc != APSS_OK) M.err = apss_last_error(M.h);
-    M.partial_ms = ms_since(tp);
+    M.partial_ms += ms_since(tp);
   }
   if (rc != APSS_OK) fail_here(rc);
-  if (cx.bar->wait()) return;  // ---- B3: every member's partial scores are complete
+  if (bar.wait()) return false;  // ---- B3: every member's partial scores are complete
   const int64_t nu = M.n_union;
-  if (g->m[0].n_union != nu) {  // (cannot happen: the same sort of the same keys; checked because a collective of unequal counts hangs)
+  if (peers[0].n_union != nu) {  // (cannot happen: the same sort of the same keys; checked because a collective of unequal counts hangs)
     M.err = "members disagree on the candidate union";
     fail_here(APSS_E_STATE);
   }
-  if (cx.bar->wait()) return;  // ---- B3b
+  if (bar.wait()) return false;  // ---- B3b: (the decision to run the collective is this barrier's, the same on every member)
   // ---- step 4: all-reduce(SUM) of the partial scores
   const float *total_score = M.partial.p;
-  if (!cx.failed.load() && nu > 0) {
+  bool ok = true;
+  if (nu > 0) {
     if (g->exchange == APSS_EXCHANGE_RCCL) {
       const ncclResult_t nr = r->AllReduce(M.partial.p, M.sum.p, (size_t)nu, ncclFloat, ncclSum, M.comm, M.stream);
       if (nr != ncclSuccess) {
         M.err = std::string("RCCL all-reduce of partial scores: ") + r->GetErrorString(nr);
         fail_here(APSS_E_DEVICE);
+        ok = false;
       }
       total_score = M.sum.p;
     } else if (i == 0) {
       hipError_t e = hipMemcpyAsync(M.sum.p, M.partial.p, (size_t)nu * sizeof(float), hipMemcpyDeviceToDevice, M.stream);
       for (int k = 1; k < T && e == hipSuccess; ++k) {
-        const float *src = g->m[(size_t)k].partial.p;
-        if (g->m[(size_t)k].dev != M.dev) {  // (another device: bring the vector over first)
+        const float *src = peers[k].partial.p;
+        if (peers[k].dev != M.dev) {  // (another device: bring the vector over first)
           if (ensure(M, M.stage, (size_t)nu) != APSS_OK) {
             e = hipErrorOutOfMemory;
             break;
@@ -735,39 +1039,97 @@ void member_main(int i, CallCtx *pcx) {
       if (e != hipSuccess) {
         M.err = std::string("partial score reduction: ") + hipGetErrorString(e);
         fail_here(e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE);
+        ok = false;
       }
       total_score = M.sum.p;
     }
   }
-  // ---- the `>= theta` prune, on member 0 (every member of the RCCL exchange holds the same sums)
-  if (i == 0 && !cx.failed.load()) {
+  // ---- the `>= theta` prune, on the row range's first member (every member of the RCCL exchange holds the same sums)
+  if (i == 0 && ok) {
     auto finish = [&]() -> int32_t {
       int32_t rc2;
-      if ((rc2 = ensure(M, g->res_q, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
-      if ((rc2 = ensure(M, g->res_c, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
-      if ((rc2 = ensure(M, g->res_s, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
+      if ((rc2 = ensure(M, R.res_q, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
+      if ((rc2 = ensure(M, R.res_c, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
+      if ((rc2 = ensure(M, R.res_s, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
       GHIP(nullptr, M, hipMemsetAsync(M.count.p, 0, sizeof(unsigned long long), M.stream));
       if (nu > 0) {
         hipLaunchKernelGGL(k_threshold_compact, dim3(grid_for(nu)), dim3(256), 0, M.stream, total_score, (const int32_t *)M.uq.p,
-                           (const int32_t *)M.uc.p, nu, (float)g->cfg.theta, g->res_q.p, g->res_c.p, g->res_s.p, M.count.p);
+                           (const int32_t *)M.uc.p, nu, (float)g->cfg.theta, R.res_q.p, R.res_c.p, R.res_s.p, M.count.p);
         GHIP(nullptr, M, hipGetLastError());
       }
       unsigned long long nres = 0;
       GHIP(nullptr, M, hipMemcpyAsync(&nres, M.count.p, sizeof(nres), hipMemcpyDeviceToHost, M.stream));
       GHIP(nullptr, M, hipStreamSynchronize(M.stream));
-      g->n_res = (int64_t)nres;
+      R.n_phase = (int64_t)nres;
+      R.union_pairs += nu;
+      if (g->D > 1) return append_triples(M, R, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, mirrored);
       return APSS_OK;
     };
     const int32_t rc2 = finish();
     if (rc2 != APSS_OK) fail_here(rc2);
-    cx.exchange_ms = ms_since(tx);
-  } else if (!cx.failed.load()) {
+    R.exchange_ms += ms_since(tx);
+  } else if (ok) {
     if (hipStreamSynchronize(M.stream) != hipSuccess) {
       M.err = "stream synchronisation failed after the exchange";
       fail_here(APSS_E_DEVICE);
     }
   }
-  cx.bar->wait();  // ---- B4: member 0 has read every peer's partial scores (copies exchange) before anyone returns
+  return !bar.wait();  // ---- B4: the first member has read every peer's partial scores (copies exchange) before anyone goes on
+}
+
+void member_main(int m, CallCtx *pcx) {
+  CallCtx &cx = *pcx;
+  apss_group *g = cx.g;
+  apss_group::Member &M = g->m[(size_t)m];
+  const int j = m / g->T, i = m % g->T;
+  M.rc = APSS_OK;
+  M.err.clear();
+  M.n_cand = M.n_union = 0;
+  M.member_ms = M.partial_ms = M.probe_ms = M.head_ms = 0;
+  M.visits = M.dev_visits = M.touched = M.cand_sum = M.cand_max = 0;
+  auto fail_here = [&](int32_t rc) {
+    M.rc = rc;
+    cx.failed.store(1);
+  };
+  if (hipSetDevice(M.dev) != hipSuccess) {
+    M.err = "hipSetDevice failed";
+    fail_here(APSS_E_DEVICE);
+  }
+  const MemberBatch whole = whole_batch(cx.b, m);
+  if (g->D == 1) {  // T x 1: every member holds its slice of every row, one phase
+    (void)member_phase(m, cx, cx.mode, whole, false);
+    return;
+  }
+  apss_group::Range &R = g->rr[(size_t)j];
+  const RangePlan &P = cx.plan[(size_t)j];
+  if (cx.mode == 1) {  // frozen index: every row range that holds rows is asked the whole batch
+    if (R.rows > 0) (void)member_phase(m, cx, 1, whole, false);
+    return;
+  }
+  if (cx.b.n == 0) return;  // (an empty batch: no span, no outside batch, and no row offsets to read)
+  MemberBatch ph[2];  // [0] the row range's own span, [1] its outside batch
+  if (cx.b.on_device) {
+    if (!cx.failed.load()) {
+      const int32_t rc = member_slice(M, cx, whole, P, ph);
+      if (rc != APSS_OK) fail_here(rc);  // (published before the row range's next barrier, B1 of the first phase below)
+    }
+  } else {
+    ph[0] = host_csr_batch(P.own);
+    ph[1] = host_csr_batch(P.out);
+  }
+  // (which phases run follows from the plan alone, so the T members of a row range run the same ones)
+  const int64_t own_n = cx.span_lo[(size_t)P.span + 1] - cx.span_lo[(size_t)P.span];
+  if (own_n > 0) {  // an empty span: the row range skips the handle call
+    const auto t0 = Clock::now();
+    const bool ok = member_phase(m, cx, cx.mode, ph[0], false);
+    if (i == 0) R.own_ms = ms_since(t0);
+    if (!ok) return;
+  }
+  if (cx.mode == 2 && P.out_rows > 0 && R.rows + own_n > 0) {
+    const auto t0 = Clock::now();
+    (void)member_phase(m, cx, 1, ph[1], P.mirrored);
+    if (i == 0) R.outside_ms = ms_since(t0), R.outside_rows = P.out_rows;
+  }
 }
 
 // ---- re-layout (apss_group_relayout, APSS_GROUP_ADAPT_LAYOUT): decide a layout from the store (+ the incoming batch), build
@@ -811,8 +1173,9 @@ void free_whole(WholeRows &w) {
 }
 
 // document frequencies of member i's stored slice: its range of the store's terms (on the member's stream)
-int32_t member_df(apss_group *g, int i, const int32_t *cuts, uint32_t *df_range) {
-  apss_group::Member &M = g->m[(size_t)i];
+int32_t member_df(apss_group *g, int m, const int32_t *cuts, uint32_t *df_range) {
+  apss_group::Member &M = g->m[(size_t)m];
+  const int i = m % g->T;
   const int32_t lo = g->T == 1 ? 0 : cuts[i], hi = g->T == 1 ? g->cfg.dim : cuts[i + 1];
   const int64_t *rp = nullptr;
   const int32_t *ix = nullptr;
@@ -1043,12 +1406,66 @@ int32_t relayout(apss_group *g, const std::vector<int32_t> *cuts, const Batch *b
   return APSS_OK;
 }
 
+// span k of a batch of n rows cut D ways: [ceil(n k / D), ceil(n (k + 1) / D)) -- the longer spans first, so a single row is span 0
+std::vector<int64_t> span_bounds(int64_t n, int D) {
+  std::vector<int64_t> lo((size_t)D + 1, 0);
+  for (int k = 0; k <= D; ++k) lo[(size_t)k] = ceil_div(n * k, D);
+  return lo;
+}
+
+// grids: which span every row range stores and which spans it meets as its outside batch (include/apss.h, GRIDS)
+void plan_ranges(apss_group *g, CallCtx &cx) {
+  const int D = g->D;
+  cx.span_lo = span_bounds(cx.b.n, D);
+  cx.plan.assign((size_t)D, RangePlan{});
+  if (cx.mode == 1) return;  // (a query of the frozen index: the whole batch to every row range)
+  int first = 0;
+  bool empty = true;
+  for (int j = 0; j < D; ++j) {
+    if (g->rr[(size_t)j].rows < g->rr[(size_t)first].rows) first = j;
+    empty = empty && g->rr[(size_t)j].rows == 0;
+  }
+  // a whole-store join may use the symmetry across the row ranges; onto a store, half spans would lose the pairs of a skipped
+  // span's rows with this range's STORED rows
+  const bool symmetric = cx.mode == 2 && empty && !(g->flags & APSS_GROUP_NO_SYMMETRIC_RANGES) && !(g->cfg.flags & APSS_FLAG_NO_SYMMETRY);
+  if (cx.mode == 2) g->symmetric_ranges = symmetric;
+  for (int j = 0; j < D; ++j) {
+    RangePlan &P = cx.plan[(size_t)j];
+    P.span = ((j - first) % D + D) % D;
+    if (cx.mode == 2) {
+      if (symmetric) {  // (first = 0 here: span k is row range k) the (D - 1) / 2 ranges before j, cyclically ...
+        for (int d = 1; d <= (D - 1) / 2; ++d) P.outside.push_back(((j - d) % D + D) % D);
+        const int k = (j + D / 2) % D;  // ... and for even D the opposite range, taken by the lower-numbered of the two
+        if (D % 2 == 0 && j < k) P.outside.push_back(k);
+        std::sort(P.outside.begin(), P.outside.end());
+        P.mirrored = true;
+      } else {
+        for (int k = 0; k < D; ++k)
+          if (k != P.span) P.outside.push_back(k);
+      }
+      for (int k : P.outside) P.out_rows += cx.span_lo[(size_t)k + 1] - cx.span_lo[(size_t)k];
+    }
+    if (!cx.b.on_device) {  // the host-pointer entry points slice here, once per row range
+      append_span(P.own, cx.b, cx.span_lo[(size_t)P.span], cx.span_lo[(size_t)P.span + 1]);
+      for (int k : P.outside)
+        if (cx.span_lo[(size_t)k + 1] > cx.span_lo[(size_t)k]) append_span(P.out, cx.b, cx.span_lo[(size_t)k], cx.span_lo[(size_t)k + 1]);
+      if (P.out.rowptr.empty()) P.out.rowptr.push_back(0);
+    }
+  }
+}
+
 int32_t run_call(apss_group *g, int mode, const Batch &b, int64_t *n_results) {
   if (n_results) *n_results = 0;
   g->err.clear();
   if (b.n < 0 || b.nnz < 0) return gfail(g, APSS_E_INVALID, "negative size");
   g->n_res = -1;
   g->results_in_handle = false;
+  const int T = g->T, D = g->D, n_members = T * D;
+  for (apss_group::Range &R : g->rr) {
+    R.n_phase = R.n_tri = 0;
+    R.union_pairs = R.gather_bytes = R.mirrored = R.outside_rows = 0;
+    R.own_ms = R.outside_ms = R.exchange_ms = 0;
+  }
   if (!g->created) {
     if (mode == 1 || b.n == 0) {  // nothing is indexed yet: an empty answer, no layout decided
       g->n_res = mode == 0 ? -1 : 0;
@@ -1076,69 +1493,89 @@ int32_t run_call(apss_group *g, int mode, const Batch &b, int64_t *n_results) {
   cx.g = g;
   cx.mode = mode;
   cx.b = b;
-  Barrier bar(g->T, &cx.failed);
-  cx.bar = &bar;
+  if (D > 1) plan_ranges(g, cx);
+  std::vector<std::unique_ptr<Barrier>> bars;
+  for (int j = 0; j < D; ++j) {
+    bars.emplace_back(new Barrier(T, &cx.failed));
+    cx.bar.push_back(bars.back().get());
+  }
   std::vector<std::thread> th;
-  for (int i = 1; i < g->T; ++i) th.emplace_back(member_main, i, &cx);
+  for (int m = 1; m < n_members; ++m) th.emplace_back(member_main, m, &cx);
   member_main(0, &cx);  // (member 0 runs on the caller's thread)
   for (std::thread &t : th) t.join();
+  (void)hipSetDevice(g->m[0].dev);
   if (cx.failed.load()) {
     g->n_res = -1;
-    for (int i = 0; i < g->T; ++i)
-      if (g->m[(size_t)i].rc != APSS_OK)
-        return gfail(g, g->m[(size_t)i].rc, "member " + std::to_string(i) + ": " + g->m[(size_t)i].err);
+    for (int m = 0; m < n_members; ++m)
+      if (g->m[(size_t)m].rc != APSS_OK)
+        return gfail(g, g->m[(size_t)m].rc, "member " + std::to_string(m) + ": " + g->m[(size_t)m].err);
     return gfail(g, APSS_E_STATE, "a member failed");
   }
   if (mode != 1) {
-    int64_t rows = 0;
-    (void)apss_size(g->m[0].h, &rows, nullptr);
-    g->n_rows = rows;
+    g->n_rows = 0;
+    for (int j = 0; j < D; ++j) {
+      int64_t rows = 0;
+      (void)apss_size(g->m[(size_t)(j * T)].h, &rows, nullptr);
+      g->rr[(size_t)j].rows = rows;
+      g->n_rows += rows;
+    }
   }
   // statistics of the call
   apss_group_stats &st = g->st;
   const int32_t keep_size = st.struct_size;
   st = apss_group_stats{};
   st.struct_size = keep_size;
-  st.n_members = g->T;
+  st.n_members = n_members;
   st.exchange = g->exchange;
   st.head_terms = (int32_t)g->head.size();
-  for (int i = 0; i <= g->T && i <= APSS_GROUP_MAX_MEMBERS; ++i) st.term_cuts[i] = g->cuts[(size_t)i];
-  for (int i = 0; i < g->T; ++i) {
-    apss_group::Member &M = g->m[(size_t)i];
+  st.rows = g->n_rows;
+  for (int i = 0; i <= T && i <= APSS_GROUP_MAX_MEMBERS; ++i) st.term_cuts[i] = g->cuts[(size_t)i];
+  int64_t least = INT64_MAX;
+  for (int m = 0; m < n_members; ++m) {
+    apss_group::Member &M = g->m[(size_t)m];
     apss_stats ms{};
     ms.struct_size = (int32_t)sizeof(apss_stats);
     (void)apss_stats_get(M.h, &ms);
     st.nnz += ms.nnz;
-    st.rows = ms.rows;
     if (mode != 0) {
-      st.posting_visits += ms.posting_visits;
-      st.device_posting_visits += ms.device_posting_visits;
-      st.member_touched_pairs += ms.candidate_pairs;
-      st.candidates_sum += M.n_cand;
-      st.candidates_max = std::max(st.candidates_max, M.n_cand);
-      st.probe_ms_max = std::max(st.probe_ms_max, ms.probe_ms);
-      st.head_ms_max = std::max(st.head_ms_max, ms.head_ms);
+      st.posting_visits += M.visits;
+      st.device_posting_visits += M.dev_visits;
+      st.member_touched_pairs += M.touched;
+      st.candidates_sum += M.cand_sum;
+      st.candidates_max = std::max(st.candidates_max, M.cand_max);
+      st.probe_ms_max = std::max(st.probe_ms_max, M.probe_ms);
+      st.head_ms_max = std::max(st.head_ms_max, M.head_ms);
+      least = std::min(least, M.cand_sum);
     }
     st.build_ms_max = std::max(st.build_ms_max, ms.build_ms);
     st.member_ms_max = std::max(st.member_ms_max, M.member_ms);
     st.partial_ms_max = std::max(st.partial_ms_max, M.partial_ms);
   }
   if (mode != 0) {
-    if (g->exchange == APSS_EXCHANGE_NONE) {
+    if (D > 1) {  // the row ranges' triples, one list after the other
+      g->n_res = 0;
+      for (const apss_group::Range &R : g->rr) {
+        g->n_res += R.n_tri;
+        st.union_pairs += g->exchange == APSS_EXCHANGE_NONE ? R.n_tri - R.mirrored : R.union_pairs;
+        st.all_gather_bytes += R.gather_bytes;
+        st.exchange_ms = std::max(st.exchange_ms, R.exchange_ms);
+      }
+      if (g->exchange != APSS_EXCHANGE_NONE) st.all_reduce_bytes = 4 * st.union_pairs;
+    } else if (g->exchange == APSS_EXCHANGE_NONE) {
       g->results_in_handle = true;
       g->n_res = g->m[0].n_cand;
       st.union_pairs = g->n_res;
     } else {
+      g->n_res = g->rr[0].n_phase;
       st.union_pairs = g->m[0].n_union;
-      int64_t least = st.candidates_max;
-      for (const apss_group::Member &M : g->m) least = std::min(least, M.n_cand);
       st.all_gather_bytes = 8 * (st.candidates_sum - least);
       st.all_reduce_bytes = 4 * st.union_pairs;
-      st.exchange_ms = cx.exchange_ms;
+      st.exchange_ms = g->rr[0].exchange_ms;
     }
     st.result_pairs = g->n_res;
     if (n_results) *n_results = g->n_res;
   }
+  if (mode == 1) g->symmetric_ranges = false;
   st.total_ms = ms_since(t0);
   return APSS_OK;
 }
@@ -1170,6 +1607,11 @@ Batch host_batch(int64_t n, const int64_t *rowptr, const int32_t *indices, const
 extern "C" {
 
 int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32_t *device_ids, uint32_t group_flags, apss_group **out) {
+  return apss_group_create_grid(cfg, n_members, 1, device_ids, group_flags, out);
+}
+
+int32_t apss_group_create_grid(const apss_config *cfg, int32_t n_term_ranges, int32_t n_row_ranges, const int32_t *device_ids,
+                               uint32_t group_flags, apss_group **out) {
   if (!cfg || !out || !device_ids) {
     g_group_create_error = "null argument";
     return APSS_E_INVALID;
@@ -1179,15 +1621,20 @@ int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32
     g_group_create_error = "apss_config.struct_size mismatch";
     return APSS_E_INVALID;
   }
-  if (n_members < 1 || n_members > APSS_GROUP_MAX_MEMBERS) {
-    g_group_create_error = "n_members must be in [1, 64]";
+  if (n_term_ranges < 1 || n_row_ranges < 1 || (int64_t)n_term_ranges * n_row_ranges > APSS_GROUP_MAX_MEMBERS) {
+    g_group_create_error = n_row_ranges == 1 ? "n_members must be in [1, 64]" : "term ranges x row ranges must be in [1, 64], each at least 1";
     return APSS_E_INVALID;
   }
+  const int32_t n_members = n_term_ranges * n_row_ranges;
   if (cfg->dim <= 0 || !std::isfinite(cfg->theta)) {
     g_group_create_error = "dim must be > 0 and theta finite";
     return APSS_E_INVALID;
   }
-  if (n_members > 1 && !(cfg->theta > 0.0)) {
+  if (n_row_ranges > 1 && (group_flags & APSS_GROUP_ADAPT_LAYOUT)) {
+    g_group_create_error = "APSS_GROUP_ADAPT_LAYOUT is not supported with more than one row range (name the cuts: apss_group_set_term_cuts)";
+    return APSS_E_UNSUPPORTED;
+  }
+  if (n_term_ranges > 1 && !(cfg->theta > 0.0)) {
     g_group_create_error = "term-range shards need theta > 0 (candidate test p_g >= theta*|q_g|*|c_g|)";
     return APSS_E_UNSUPPORTED;
   }
@@ -1201,8 +1648,10 @@ int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32
   if (!g) return APSS_E_NOMEM;
   g->cfg = *cfg;
   g->flags = group_flags;
-  g->T = n_members;
+  g->T = n_term_ranges;
+  g->D = n_row_ranges;
   g->m.resize((size_t)n_members);
+  g->rr.resize((size_t)n_row_ranges);
   g->st.struct_size = (int32_t)sizeof(apss_group_stats);
   if (const char *dbg = getenv("APSS_DEBUG")) {  // (the group's only token; the handles skip it)
     const std::string s = std::string(",") + dbg;
@@ -1216,7 +1665,7 @@ int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32
       apss_group_destroy(g);
       return APSS_E_DEVICE;
     }
-    for (int k = 0; k < i; ++k)
+    for (int k = i - i % n_term_ranges; k < i; ++k)  // (the exchange runs among the members of ONE row range)
       if (g->m[(size_t)k].dev == d) g->distinct_devices = false;
     g->m[(size_t)i].dev = d;
     if (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&g->m[(size_t)i].stream, hipStreamDefault) != hipSuccess) {
@@ -1238,10 +1687,18 @@ void apss_group_destroy(apss_group *g) {
     if (M.comm && r && r->lib) (void)r->CommDestroy(M.comm);
     if (M.h) apss_destroy(M.h);
     release(M.keys); release(M.sorted); release(M.uniq); release(M.count); release(M.tmp);
-    release(M.uq); release(M.uc); release(M.partial); release(M.sum); release(M.stage);
+    release(M.uq); release(M.uc); release(M.partial); release(M.sum); release(M.stage); release(M.sp_off);
+    for (int k = 0; k < 2; ++k) {
+      release(M.sp_rowptr[k]); release(M.sp_ext[k]); release(M.sp_idx[k]); release(M.sp_val[k]);
+    }
+  }
+  for (size_t j = 0; j < g->rr.size() && j * (size_t)g->T < g->m.size(); ++j) {
+    apss_group::Range &R = g->rr[j];
+    (void)hipSetDevice(g->m[j * (size_t)g->T].dev);
+    release(R.res_q); release(R.res_c); release(R.res_s); release(R.tri_q); release(R.tri_c); release(R.tri_s);
   }
   if (!g->m.empty()) (void)hipSetDevice(g->m[0].dev);
-  release(g->res_q); release(g->res_c); release(g->res_s); release(g->ext_q); release(g->ext_c);
+  release(g->ext_q); release(g->ext_c);
   for (apss_group::Member &M : g->m)
     if (M.stream) {
       (void)hipSetDevice(M.dev);
@@ -1295,7 +1752,7 @@ int32_t apss_group_insert_and_query_dev(apss_group *g, int64_t n, int64_t nnz, c
   if (n < 0 || nnz < 0) return gfail(g, APSS_E_INVALID, "negative size");
   if (n > 0) {
     if (!d_rowptr || !d_indices || !d_values || !d_ext_ids) return gfail(g, APSS_E_INVALID, "null pointer table");
-    for (int i = 0; i < g->T; ++i)
+    for (int i = 0; i < g->T * g->D; ++i)
       if (!d_rowptr[i] || !d_ext_ids[i] || (nnz > 0 && (!d_indices[i] || !d_values[i]))) return gfail(g, APSS_E_INVALID, "null device pointer");
   }
   Batch b;
@@ -1314,7 +1771,8 @@ int32_t apss_group_clear(apss_group *g) {
   g->n_res = -1;
   g->results_in_handle = false;
   g->n_rows = 0;
-  for (int i = 0; i < g->T; ++i) {
+  for (apss_group::Range &R : g->rr) R.rows = R.n_tri = R.n_phase = 0;
+  for (int i = 0; i < g->T * g->D; ++i) {
     apss_group::Member &M = g->m[(size_t)i];
     if (!M.h) continue;
     const int32_t rc = apss_clear(M.h);
@@ -1326,6 +1784,7 @@ int32_t apss_group_clear(apss_group *g) {
 int32_t apss_group_relayout(apss_group *g, const int32_t *cuts) {
   if (!g) return APSS_E_INVALID;
   g->err.clear();
+  if (g->D > 1) return gfail(g, APSS_E_UNSUPPORTED, "apss_group_relayout: not supported on a grid with more than one row range");
   if (!g->created || g->n_rows == 0) return gfail(g, APSS_E_STATE, "apss_group_relayout: the group holds no rows");
   std::vector<int32_t> given;
   if (cuts) {
@@ -1343,7 +1802,7 @@ int32_t apss_group_layout_get(apss_group *g, apss_group_layout *out) {
   if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
     return gfail(g, APSS_E_INVALID, "apss_group_layout.struct_size must be set to sizeof(apss_group_layout) before the call");
   apss_group_layout L{};
-  L.n_members = g->T;
+  L.n_members = g->T * g->D;
   L.layout_rows = g->layout_rows;
   L.next_eval_rows = next_eval_rows(g);
   L.evaluations = g->evaluations;
@@ -1358,16 +1817,17 @@ int32_t apss_group_layout_get(apss_group *g, apss_group_layout *out) {
     std::vector<uint32_t> df((size_t)g->cfg.dim, 0u);
     std::vector<char> in_head((size_t)g->cfg.dim, 0);
     for (int32_t t : g->head) in_head[(size_t)t] = 1;
-    for (int i = 0; i < g->T; ++i) {
-      apss_group::Member &M = g->m[(size_t)i];
+    for (int m = 0; m < g->T * g->D; ++m) {  // (a grid: member (j, i)'s own rows, at dfsq[j * T + i])
+      const int i = m % g->T;
+      apss_group::Member &M = g->m[(size_t)m];
       const int32_t lo = g->T == 1 ? 0 : g->cuts[(size_t)i], hi = g->T == 1 ? g->cfg.dim : g->cuts[(size_t)i + 1];
       int32_t rc = hipSetDevice(M.dev) == hipSuccess ? APSS_OK : APSS_E_DEVICE;
-      if (rc == APSS_OK) rc = member_df(g, i, g->cuts.data(), df.data() + lo);
-      if (rc != APSS_OK) return gfail(g, rc, "member " + std::to_string(i) + ": " + M.err);
+      if (rc == APSS_OK) rc = member_df(g, m, g->cuts.data(), df.data() + lo);
+      if (rc != APSS_OK) return gfail(g, rc, "member " + std::to_string(m) + ": " + M.err);
       double sq = 0;
       for (int32_t t = lo; t < hi; ++t)
         if (!in_head[(size_t)t]) sq += (double)df[(size_t)t] * (double)df[(size_t)t];
-      L.dfsq[i] = sq;
+      L.dfsq[m] = sq;
     }
   }
   const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_group_layout));
@@ -1389,6 +1849,30 @@ int32_t apss_group_fetch_results(apss_group *g, int64_t offset, int64_t count, i
   if (offset < 0 || count < 0 || offset + count > g->n_res) return gfail(g, APSS_E_INVALID, "fetch range out of bounds");
   if (count == 0) return APSS_OK;
   if (!out_q || !out_c || !out_score) return gfail(g, APSS_E_INVALID, "null output buffer");
+  if (g->D > 1) {  // the row ranges' triples, one list after the other
+    int64_t base = 0;
+    for (int j = 0; j < g->D; ++j) {
+      const apss_group::Range &R = g->rr[(size_t)j];
+      const int64_t lo = std::max(offset, base), hi = std::min(offset + count, base + R.n_tri);
+      if (lo < hi) {
+        apss_group::Member &Mj = g->m[(size_t)(j * g->T)];
+        const size_t n = (size_t)(hi - lo);
+        auto copy = [&]() -> int32_t {
+          GHIP(nullptr, Mj, hipSetDevice(Mj.dev));
+          GHIP(nullptr, Mj, hipMemcpyAsync(out_q + (lo - offset), R.tri_q.p + (lo - base), n * sizeof(int64_t), hipMemcpyDeviceToHost, Mj.stream));
+          GHIP(nullptr, Mj, hipMemcpyAsync(out_c + (lo - offset), R.tri_c.p + (lo - base), n * sizeof(int64_t), hipMemcpyDeviceToHost, Mj.stream));
+          GHIP(nullptr, Mj, hipMemcpyAsync(out_score + (lo - offset), R.tri_s.p + (lo - base), n * sizeof(float), hipMemcpyDeviceToHost, Mj.stream));
+          GHIP(nullptr, Mj, hipStreamSynchronize(Mj.stream));
+          return APSS_OK;
+        };
+        const int32_t rc = copy();
+        if (rc != APSS_OK) return gfail(g, rc, Mj.err);
+      }
+      base += R.n_tri;
+    }
+    (void)hipSetDevice(g->m[0].dev);
+    return APSS_OK;
+  }
   apss_group::Member &M = g->m[0];
   if (g->results_in_handle) {
     const int32_t rc = apss_fetch_results(M.h, offset, count, out_q, out_c, out_score);
@@ -1405,12 +1889,12 @@ int32_t apss_group_fetch_results(apss_group *g, int64_t offset, int64_t count, i
     }
     if ((rc = ensure(M, g->ext_q, (size_t)count)) != APSS_OK) return rc;
     if ((rc = ensure(M, g->ext_c, (size_t)count)) != APSS_OK) return rc;
-    hipLaunchKernelGGL(k_gather_ext, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, M.stream, (const int32_t *)g->res_q.p + offset,
-                       (const int32_t *)g->res_c.p + offset, d_query, d_store, count, g->ext_q.p, g->ext_c.p);
+    hipLaunchKernelGGL(k_gather_ext, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, M.stream, (const int32_t *)g->rr[0].res_q.p + offset,
+                       (const int32_t *)g->rr[0].res_c.p + offset, d_query, d_store, count, g->ext_q.p, g->ext_c.p);
     GHIP(nullptr, M, hipGetLastError());
     GHIP(nullptr, M, hipMemcpyAsync(out_q, g->ext_q.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
     GHIP(nullptr, M, hipMemcpyAsync(out_c, g->ext_c.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
-    GHIP(nullptr, M, hipMemcpyAsync(out_score, g->res_s.p + offset, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, M.stream));
+    GHIP(nullptr, M, hipMemcpyAsync(out_score, g->rr[0].res_s.p + offset, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, M.stream));
     GHIP(nullptr, M, hipStreamSynchronize(M.stream));
     return APSS_OK;
   };
@@ -1425,15 +1909,38 @@ int32_t apss_group_stats_get(apss_group *g, apss_group_stats *out) {
   if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
     return gfail(g, APSS_E_INVALID, "apss_group_stats.struct_size must be set to sizeof(apss_group_stats) before the call");
   const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_group_stats));
-  g->st.n_members = g->T;
+  g->st.n_members = g->T * g->D;
   g->st.struct_size = n;
   std::memcpy(out, &g->st, (size_t)n);
   return APSS_OK;
 }
 
+int32_t apss_group_grid_get(apss_group *g, apss_group_grid *out) {
+  if (!g || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return gfail(g, APSS_E_INVALID, "apss_group_grid.struct_size must be set to sizeof(apss_group_grid) before the call");
+  apss_group_grid G{};
+  G.n_term_ranges = g->T;
+  G.n_row_ranges = g->D;
+  G.symmetric_ranges = g->symmetric_ranges ? 1 : 0;
+  for (int j = 0; j < g->D; ++j) {
+    const apss_group::Range &R = g->rr[(size_t)j];
+    G.rows_in_range[j] = R.rows;
+    G.outside_rows_max = std::max(G.outside_rows_max, R.outside_rows);
+    G.mirrored_pairs += R.mirrored;
+    G.own_ms_max = std::max(G.own_ms_max, R.own_ms);
+    G.outside_ms_max = std::max(G.outside_ms_max, R.outside_ms);
+  }
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_group_grid));
+  G.struct_size = n;
+  std::memcpy(out, &G, (size_t)n);
+  return APSS_OK;
+}
+
 int32_t apss_group_member_stats(apss_group *g, int32_t member, apss_stats *out) {
   if (!g || !out) return APSS_E_INVALID;
-  if (member < 0 || member >= g->T) return gfail(g, APSS_E_INVALID, "no such member");
+  if (member < 0 || member >= g->T * g->D) return gfail(g, APSS_E_INVALID, "no such member");
   if (!g->m[(size_t)member].h) return gfail(g, APSS_E_STATE, "the members are created by the group's first insert");
   const int32_t rc = apss_stats_get(g->m[(size_t)member].h, out);
   if (rc != APSS_OK) g->err = apss_last_error(g->m[(size_t)member].h);

@@ -216,7 +216,10 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
     // (WriteWorkerActor.scala:164-183, EntryProxyActor.scala:37-49) happens inside the library
     std::vector<int32_t> dev(conf.devices.begin(), conf.devices.end());
     if (dev.empty()) dev.push_back(conf.deviceId);
-    const int32_t rc = apss_group_create(&c, (int32_t)dev.size(), dev.data(), conf.groupFlags, &g_);
+    const int32_t D = conf.rowRanges;
+    if (D < 1 || dev.size() % (size_t)D) throw std::runtime_error("rowRanges must divide the number of devices");
+    const int32_t rc = D == 1 ? apss_group_create(&c, (int32_t)dev.size(), dev.data(), conf.groupFlags, &g_)
+                              : apss_group_create_grid(&c, (int32_t)dev.size() / D, D, dev.data(), conf.groupFlags, &g_);
     if (rc != APSS_OK) throw std::runtime_error(std::string("apss_group_create: ") + apss_group_last_error(nullptr));
     return;
   }

@@ -89,6 +89,9 @@ struct Config {
   std::vector<int> devices;
   int headTerms = 0;          // cpslab.allpair.gpu.headTerms
   unsigned groupFlags = 0;    // APSS_GROUP_* (tests: the RCCL exchange with one member)
+  // cpslab.allpair.gpu.rowRanges: D > 1 = a T x D grid (apss_group_create_grid), devices = T x D entries, member (row range j,
+  // term range i) on devices[j * T + i]
+  int rowRanges = 1;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

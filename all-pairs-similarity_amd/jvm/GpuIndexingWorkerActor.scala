@@ -37,6 +37,11 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     } else Array(if (conf.hasPath("cpslab.allpair.gpu.device")) conf.getInt("cpslab.allpair.gpu.device") else 0)
   private val headTerms = if (conf.hasPath("cpslab.allpair.gpu.headTerms")) conf.getInt("cpslab.allpair.gpu.headTerms") else 0
   private val flags = if (indexThreshold > 0.0) NativeApss.FLAG_VALUE_PRUNE else 0
+  // cpslab.allpair.gpu.rowRanges = D (default 1): the listed GPUs form a T x D grid, T = devices.length / D term ranges x D row
+  // ranges -- the reference's second sharding level (EntryProxyActor.scala:37-49) as ranges of rows; member (row range j, term
+  // range i) on devices(j * T + i).  Not with adaptiveLayout (a grid is given its cuts by name or keeps the first batch's).
+  private val rowRanges = if (conf.hasPath("cpslab.allpair.gpu.rowRanges")) conf.getInt("cpslab.allpair.gpu.rowRanges") else 1
+  require(rowRanges >= 1 && devices.length % rowRanges == 0, "cpslab.allpair.gpu.rowRanges must divide the number of devices")
   private val grouped = devices.length > 1
   // cpslab.allpair.gpu.adaptiveLayout = true: the group re-decides its term cuts and shared head as the index grows
   // (APSS_GROUP_ADAPT_LAYOUT): a stream of single vectors from an empty index does not keep its first message's layout
@@ -45,7 +50,9 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
       NativeApss.GROUP_ADAPT_LAYOUT
     else 0
   private val handle =
-    if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags)
+    if (grouped && rowRanges > 1)
+      NativeApss.createGroupGrid(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, rowRanges)
+    else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags)
     else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =

@@ -35,6 +35,15 @@ object NativeApss {
   /** returns the group's handle or 0 (groupLastError(0) says why) */
   @native def createGroup(dim: Int, theta: Double, indexThreshold: Double, flags: Int, devices: Array[Int], headTerms: Int,
                           groupFlags: Int): Long
+  val GROUP_NO_SYMMETRIC_RANGES = 8 // grids: every cell meets every other row range, nothing is mirrored
+  /** A T x D grid (apss_group_create_grid): devices.length = T x rowRanges, member (row range j, term range i) lives on
+    * devices(j * T + i); a batch's rows are spread over the row ranges, every call answers as one handle would.  rowRanges
+    * (1..64) travels in bits 16..23 of createGroup's groupFlags: one native entry point creates both shapes.
+    * Returns 0 when rowRanges does not divide devices.length (and as createGroup). */
+  def createGroupGrid(dim: Int, theta: Double, indexThreshold: Double, flags: Int, devices: Array[Int], headTerms: Int,
+                      groupFlags: Int, rowRanges: Int): Long =
+    if (rowRanges < 1 || rowRanges > 64 || devices.length % rowRanges != 0) 0L
+    else createGroup(dim, theta, indexThreshold, flags, devices, headTerms, (groupFlags & 0xffff) | (rowRanges << 16))
   @native def destroyGroup(g: Long): Unit
   @native def groupLastError(g: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

@@ -151,6 +151,8 @@ JNIEXPORT jint JNICALL Java_cpslab_gpu_NativeApss_fetch(JNIEnv *env, jclass cls,
 /* ---- apss_group: the term-sharded index of one node (one member per entry of `devices`) behind one object: what the
  * reference's DataPacket fan-out to maxShardNum x maxIndexEntryActorNum workers becomes on the GPUs of one host
  * (WriteWorkerActor.scala:164-183, EntryProxyActor.scala:37-49); the members' exchange runs below this boundary (RCCL). */
+/* Row ranges: NativeApss.createGroupGrid hands D in bits 16..23 of groupFlags (0 = 1: the T x 1 group of createGroup); the
+ * library sees the APSS_GROUP_* flags of the low 16 bits and n / D term ranges x D row ranges (apss_group_create_grid). */
 JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_createGroup(JNIEnv *env, jclass cls, jint dim, jdouble theta,
                                                                jdouble indexThreshold, jint flags, jintArray devices,
                                                                jint headTerms, jint groupFlags) {
@@ -168,7 +170,11 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_createGroup(JNIEnv *env, jcla
   c.flags = (uint32_t)flags;
   c.head_terms = headTerms;
   apss_group *g = 0;
-  return apss_group_create(&c, n, (const int32_t *)dev, (uint32_t)groupFlags, &g) == APSS_OK ? (jlong)(intptr_t)g : 0;
+  const int32_t rowRanges = (groupFlags >> 16) & 0xff;
+  const uint32_t gflags = (uint32_t)groupFlags & 0xffffu;
+  if (rowRanges <= 1) return apss_group_create(&c, n, (const int32_t *)dev, gflags, &g) == APSS_OK ? (jlong)(intptr_t)g : 0;
+  if (n % rowRanges) return 0;
+  return apss_group_create_grid(&c, n / rowRanges, rowRanges, (const int32_t *)dev, gflags, &g) == APSS_OK ? (jlong)(intptr_t)g : 0;
 }
 
 JNIEXPORT void JNICALL Java_cpslab_gpu_NativeApss_destroyGroup(JNIEnv *env, jclass cls, jlong g) {

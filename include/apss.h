@@ -254,7 +254,8 @@ int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int
                                const float *d_values, const int64_t *d_ext_ids);
 
 /* =====================================================================================================================
- * apss_group: the term-sharded index of one node -- T member shards, one per GPU -- behind ONE object.
+ * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
+ * object (apss_group_create: T x 1, every member holds its slice of every row; apss_group_create_grid: T x D, below).
  *
  * The reference shards its inverted index by term inside the server: WriteWorkerActor buckets every vector by
  * dim % maxShardNum and flushes one DataPacket per shard (WriteWorkerActor.scala:164-183), EntryProxyActor fans a packet out
@@ -281,6 +282,29 @@ int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int
  * call, insert or clear.  apss_config: dim, theta, index_threshold, flags, tile_rows, head_terms and the capacity hints
  * apply to every member; device_id, term_lo, term_hi are ignored (the group sets them).  APSS_FLAG_ADMISSION is not
  * supported with more than one member and a dense-head block (as on a single shard handle).
+ *
+ * GRIDS (apss_group_create_grid): the reference shards on two levels (WriteWorkerActor.scala:164-183 by dim % maxShardNum,
+ * EntryProxyActor.scala:37-49 by dim % maxIndexEntryActorNum); the second level here is D ROW ranges.  Member (j, i) = row
+ * range j, term range i holds term range i of the rows of row range j; the T members of a row range are a term-sharded
+ * group of their own (steps 1-4 above run inside a row range, the row ranges never wait for each other), the term cuts and
+ * the dense head are shared by all row ranges.  The answer of every call is the list a single plain handle gives.
+ *   rows: a batch of n rows is cut into D contiguous spans, span k = [ceil(n k / D), ceil(n (k + 1) / D)); span k goes to row
+ *     range (first + k) mod D, first = the row range holding the fewest rows when the call starts (lowest index on ties) --
+ *     single vectors fill the ranges round-robin, equal batches divisible by D keep them exactly equal.
+ *   insert: row range j inserts its span.  query (frozen index): every row range is asked the whole batch; the lists are
+ *     disjoint by candidate and are concatenated.
+ *   insert-and-query, row range j: OWN phase = insert_and_query of its span (pairs of the span with the range's store and
+ *     itself), then OUTSIDE phase = ONE query of the other spans' whole rows, concatenated in span order, against the range's
+ *     store + span.  When every row range was empty at the start of the call (a whole-store join) the symmetry is used ACROSS
+ *     the row ranges: range j meets only the (D - 1) / 2 ranges before it (cyclically; for even D also the opposite range
+ *     when j is the lower of the two) and every pair it finds is reported in both directions -- unless
+ *     APSS_GROUP_NO_SYMMETRIC_RANGES or APSS_FLAG_NO_SYMMETRY is set.  On a non-empty store every cell meets all other spans
+ *     and nothing is mirrored.
+ *   results: (query ext id, candidate ext id, score) triples are gathered on each row range's first device after each phase;
+ *     the group's list is their concatenation over the row ranges.
+ *   exchange: RCCL (one communicator per row range) when in every row range the T members have a device each, copies
+ *     otherwise; T = 1: none, a row range's answer is final.
+ *   not supported with D > 1 (APSS_E_UNSUPPORTED): APSS_GROUP_ADAPT_LAYOUT and apss_group_relayout.
  * ===================================================================================================================== */
 typedef struct apss_group apss_group;
 
@@ -291,6 +315,8 @@ typedef struct apss_group apss_group;
 #define APSS_GROUP_ADAPT_LAYOUT 4u   /* re-decide the layout as the store grows: before an insert-type call that brings the store to
                                         max(1024, 2 x layout_rows) rows, cuts and head are decided again on the store plus the
                                         batch and the store is rebuilt in the new layout (apss_group_relayout) */
+
+#define APSS_GROUP_NO_SYMMETRIC_RANGES 8u /* grids: every cell meets every other row range (no mirroring) */
 
 #define APSS_EXCHANGE_NONE 0   /* one member, its answer is final */
 #define APSS_EXCHANGE_COPIES 1 /* device-to-device copies + summing kernel (members share a device, or APSS_GROUP_NO_RCCL) */
@@ -342,13 +368,37 @@ typedef struct apss_group_layout {
                                           balanced cuts even out), computed on the device at this call */
 } apss_group_layout;
 
-/* n_members >= 1 shards on the HIP devices device_ids[0 .. n_members) (a device may appear more than once) */
+/* what the row ranges of a grid did in the last call (apss_group_grid_get; struct_size as apss_stats).  On a grid
+ * apss_group_stats.n_members is T x D, term_cuts has T + 1 entries, the sums run over all members and both phases (a member's
+ * posting_visits as its handle reports them, the outside phase counted twice when its pairs were mirrored: what the
+ * reference's two-directional probe visits), exchange_ms is the slowest row range's; apss_group_member_stats(g, j * T + i)
+ * addresses member (j, i) */
+typedef struct apss_group_grid {
+  int32_t struct_size;        /* IN: sizeof(apss_group_grid) of the caller; OUT: bytes written */
+  int32_t n_term_ranges;      /* T */
+  int32_t n_row_ranges;       /* D */
+  int32_t symmetric_ranges;   /* 1: the last query-type call met half of the other row ranges per cell and mirrored */
+  int64_t rows_in_range[APSS_GROUP_MAX_MEMBERS]; /* rows held by row range j */
+  int64_t outside_rows_max;   /* rows of the longest outside batch a cell met in the last call */
+  int64_t mirrored_pairs;     /* results of the last call that are mirrors of a pair found in the other direction */
+  double own_ms_max;          /* wall time of the own phase, slowest row range */
+  double outside_ms_max;      /* ... of the outside phase */
+} apss_group_grid;
+
+/* n_members >= 1 shards on the HIP devices device_ids[0 .. n_members) (a device may appear more than once);
+ * = apss_group_create_grid(cfg, n_members, 1, ...) */
 int32_t apss_group_create(const apss_config *cfg, int32_t n_members, const int32_t *device_ids, uint32_t group_flags,
                           apss_group **out);
+/* T = n_term_ranges term ranges x D = n_row_ranges row ranges; member (j, i) = row range j, term range i,
+ * lives on device_ids[j * T + i]; T * D <= APSS_GROUP_MAX_MEMBERS */
+int32_t apss_group_create_grid(const apss_config *cfg, int32_t n_term_ranges, int32_t n_row_ranges,
+                               const int32_t *device_ids, uint32_t group_flags, apss_group **out);
+int32_t apss_group_grid_get(apss_group *g, apss_group_grid *out);
 void apss_group_destroy(apss_group *g);
 /* message of the last failing call ("" if none); g == NULL: last apss_group_create failure */
 const char *apss_group_last_error(const apss_group *g);
-/* Name the term ranges instead of letting the first batch decide: cuts[0] = 0 < cuts[1] < .. < cuts[n_members] = dim.
+/* Name the term ranges instead of letting the first batch decide: cuts[0] = 0 < cuts[1] < .. < cuts[T] = dim (T = n_members
+ * of apss_group_create, n_term_ranges of a grid).
  * Before the group's first insert only (the members' handles are created with their ranges then). */
 int32_t apss_group_set_term_cuts(apss_group *g, const int32_t *cuts);
 
@@ -361,7 +411,9 @@ int32_t apss_group_query(apss_group *g, int64_t n, const int64_t *rowptr, const 
 int32_t apss_group_insert_and_query(apss_group *g, int64_t n, const int64_t *rowptr, const int32_t *indices,
                                     const double *values, const int64_t *ext_ids, int64_t *n_results);
 /* device-pointer entry point: member m reads the batch from d_rowptr[m], d_indices[m], d_values[m], d_ext_ids[m], resident
- * on ITS device (members that share a device may be given the same pointers); layouts as apss_insert_and_query_dev */
+ * on ITS device (members that share a device may be given the same pointers); layouts as apss_insert_and_query_dev.  On a
+ * grid every member is handed the WHOLE batch (m = j * T + i) and cuts its row range's span and outside batch out of it on
+ * its device */
 int32_t apss_group_insert_and_query_dev(apss_group *g, int64_t n, int64_t nnz, const int64_t *const *d_rowptr,
                                         const int32_t *const *d_indices, const float *const *d_values,
                                         const int64_t *const *d_ext_ids, int64_t *n_results);
@@ -377,7 +429,8 @@ int32_t apss_group_clear(apss_group *g);
  * swapped: the members' slices are reassembled into whole rows on every device that holds a member, new member handles are
  * filled from them (apss_insert_stored_dev) and only when every member succeeded are the old ones destroyed -- so for a
  * moment each member's store exists twice.  A failure leaves the old layout and store untouched and returns the member's
- * error.  The results of the last query-type call are gone afterwards.  APSS_E_STATE on a group without rows. */
+ * error.  The results of the last query-type call are gone afterwards.  APSS_E_STATE on a group without rows;
+ * APSS_E_UNSUPPORTED on a grid with more than one row range (the group is left as it is). */
 int32_t apss_group_relayout(apss_group *g, const int32_t *cuts);
 int32_t apss_group_layout_get(apss_group *g, apss_group_layout *out);
 
