@@ -36,6 +36,12 @@ struct DevBuf {
 struct DebugCfg {
   bool build_lds = false;      // build_lds      index build with LDS cursors even for a handful of tiles
   bool build_atomic = false;   // build_atomic   index build with global atomics even for small dims
+  bool build_stream = false;   // build_stream   LDS index build with the whole-tile streaming kernels (never the run-reading ones)
+  bool build_runs = false;     // build_runs     LDS index build with the run-reading kernels whatever the number of ranges and the mean run
+  int run_range = 0;           // run_range=N    terms per range of the run-reading build (<= 16384; default kRunRange)
+  int run_lanes = 0;           // run_lanes=L    its lanes per row (4 | 8 | 16 | 32; default: from the mean run length)
+  int run_sub = -1;            // run_sub=W      run-reading build: scatter in two passes through sub-ranges of W terms (a power of two >= 64; 0: one pass)
+  bool build_trace = false;    // build_trace    one line on stderr per index build: which kernels it took
   bool chunk8 = false;         // chunk8         filter kernel with 8-posting chunks (4-step window)
   bool shard_exact = false;    // shard_exact    term-range shards run the single-pass exact kernel
   bool diag = false;           // diag           in-kernel cycle stamps of the single-pass kernel (stderr)
@@ -85,6 +91,12 @@ DebugCfg parse_debug_env() {
     const int val = eq == std::string::npos ? 1 : atoi(tok.c_str() + eq + 1);
     if (key == "build_lds") d.build_lds = val != 0;
     else if (key == "build_atomic") d.build_atomic = val != 0;
+    else if (key == "build_stream") d.build_stream = val != 0;
+    else if (key == "build_runs") d.build_runs = val != 0;
+    else if (key == "run_range") d.run_range = val;
+    else if (key == "run_lanes") d.run_lanes = val;
+    else if (key == "run_sub") d.run_sub = val;
+    else if (key == "build_trace") d.build_trace = val != 0;
     else if (key == "chunk8") d.chunk8 = val != 0;
     else if (key == "shard_exact") d.shard_exact = val != 0;
     else if (key == "diag") d.diag = val != 0;
@@ -194,6 +206,8 @@ struct apss_handle {
   DevBuf<int32_t> bk_idx;             //   and the entries partitioned by (tile, range): term, store row, value
   DevBuf<uint32_t> bk_erow;
   DevBuf<float> bk_val;
+  DevBuf<uint32_t> run_cut;           // run-reading LDS build: per-row range cuts of the rows being built (k_row_cuts)
+  DevBuf<uint2> run_ent;              //   ... and the entries partitioned by (tile, sub-range) for its two-pass scatter
   DevBuf<uint2> app_seg;             // append build: the last tile's segment table and postings before the append
   DevBuf<char> app_post;
   DevBuf<int32_t> vq_first, vrow_q;  // virtual-row table of the last query batch (queries of > 512 terms)
@@ -524,6 +538,8 @@ void fill_build_args(apss_handle *h, apss_handle::IndexSet &ix, BuildArgs &b, bo
   b.tile_post_base = ix.base.p;
   b.post = ix.post.p;
   b.post_c = ix.post_c.p;
+  b.term_lo = h->cfg.term_lo;
+  b.term_hi = h->cfg.term_hi;
 }
 
 // segment lengths -> segment starts for tiles [tile0, tile0 + n): k_tile_scan_part + k_tile_scan_place
@@ -602,6 +618,20 @@ int32_t append_tile(apss_handle *h, apss_handle::IndexSet &ix, int64_t tile, int
   return APSS_OK;
 }
 
+// run-reading LDS build: the mean row length (entries the handle keeps of a row) below which the streaming kernels are kept --
+// the cut table and the second pass are paid per row and per (tile, sub-range), the re-reads they remove per entry.  Measured on
+// term shards of C3 (profiles/build_runs.md): T = 2 (50 entries per row) build 3.42 -> 2.67 ms, T = 4 (25) 2.09 -> 1.94,
+// T = 8 (12.5) 1.36 -> 1.78.  And the launch of k_tile_runs with L lanes per row.
+constexpr double kRunMinMeanRow = 20.0;
+constexpr int kRunSub = 256;  // terms per sub-range of the two-pass scatter
+template <int SCATTER>
+void launch_tile_runs(int lanes, dim3 grid, size_t lds, hipStream_t stream, const BuildArgs &b, int64_t tile0, int32_t n_ranges) {
+  if (lanes == 4) hipLaunchKernelGGL((k_tile_runs<SCATTER, 4>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
+  else if (lanes == 8) hipLaunchKernelGGL((k_tile_runs<SCATTER, 8>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
+  else if (lanes == 16) hipLaunchKernelGGL((k_tile_runs<SCATTER, 16>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
+  else hipLaunchKernelGGL((k_tile_runs<SCATTER, 32>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
+}
+
 // ---- index build for rows [row0, n_rows): rebuild every tile of `ix` that contains one of them ----
 int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
   const int64_t cb = ix.cb;
@@ -661,10 +691,58 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
                                           ((n_tiles - tile0) * n_ranges >= 48 || h->dbgcfg.build_lds));
   if (!lds_build)
     HIPCHK(h, hipMemsetAsync(ix.seg.p + tile0 * stride, 0, (size_t)((n_tiles - tile0) * stride) * sizeof(uint2), h->stream));
+  // Run-reading LDS build (k_row_cuts + k_tile_runs): wherever the streaming LDS build would re-read the tile's entries -- two
+  // term ranges or more -- and the rows are long enough to be worth a cut table (kRunMinMeanRow).  With one range
+  // the streaming kernels read every entry exactly once, coalesced: nothing to save.  32-bit cut points: (longest row) x (rows
+  // per tile) < 2^31.
+  const double mean_row = h->idx_rows > 0 ? (double)build_nnz / (double)h->idx_rows : 0.0;
+  int32_t run_rt = h->dbgcfg.run_range > 0 ? std::min(h->dbgcfg.run_range, kBuildRange) : kRunRange;
+  const int64_t t_lo = h->cfg.term_lo, t_hi = h->cfg.term_hi;
+  const int64_t run_active = std::max<int64_t>(1, ceil_div(t_hi, run_rt) - t_lo / run_rt);  // ranges that hold terms of this handle
+  const double mean_run = mean_row / (double)run_active;
+  const bool run_build = lds_build && !bucket_build && !h->dbgcfg.build_stream && std::max<int64_t>(h->store_max_nnz, 1) * cb < (1LL << 31) &&
+                         ceil_div(h->cfg.dim, run_rt) <= 64 &&
+                         (h->dbgcfg.build_runs || (n_ranges >= 2 && mean_row >= kRunMinMeanRow));
+  if (run_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, run_rt);
   BuildArgs b{};
   fill_build_args(h, ix, b, scaled);
   b.row0 = r0;
   b.row1 = h->idx_rows;
+  // ... and its scatter in two passes (BuildArgs::sub_shift) when the scratch copy of the entries is affordable
+  int32_t run_sub = h->dbgcfg.run_sub >= 0 ? h->dbgcfg.run_sub : kRunSub;
+  if (run_sub < 64 || run_sub > kPlaceMaxTerms || (run_sub & (run_sub - 1)) || run_rt % run_sub || !ix.coarse || build_nnz > (int64_t)6e8 || build_nnz <= 0)
+    run_sub = 0;
+  const int32_t n_sub = run_sub ? (int32_t)ceil_div(h->cfg.dim, run_sub) : 0;
+  const int64_t n_bk = (n_tiles - tile0) * n_sub;
+  // lanes per row, a power of two in 4 .. 32 (measured at C3, mean run 14.3: profiles/build_runs.md): about the mean run where the
+  // scatter's 4-B stores go straight to memory (one pass: 16), half of it where they are 8-B stores into a handful of streams
+  // (two passes: 8) -- there more rows in flight per workgroup pay more than lanes that never wait for a second chunk
+  const double run_want = run_sub ? mean_run * 0.5 : mean_run;
+  int run_lanes = h->dbgcfg.run_lanes;
+  if (run_lanes != 4 && run_lanes != 8 && run_lanes != 16 && run_lanes != 32)
+    run_lanes = run_want <= 4.0 ? 4 : (run_want <= 8.0 ? 8 : (run_want <= 16.0 ? 16 : 32));
+  if (h->dbgcfg.build_trace)
+    fprintf(stderr, "[apss] build %s tiles [%lld, %lld): %s, %d ranges of %d terms, %d lanes per row (mean run %.2f)\n", ix.coarse ? "coarse" : "exact",
+            (long long)tile0, (long long)n_tiles, bucket_build ? "bucketed" : (run_build ? "runs" : (lds_build ? "stream" : "atomic")), (int)n_ranges,
+            run_build ? run_rt : (bucket_build ? bucket_rt : kBuildRange), run_build ? run_lanes : 0, mean_run);
+  if (h->dbgcfg.build_trace && run_build) fprintf(stderr, "[apss]   scatter through sub-ranges of %d terms\n", (int)run_sub);
+  if (run_build) {
+    APSS_TRY(ensure(h, h->run_cut, (size_t)((h->idx_rows - r0) * (n_ranges + 1))));
+    b.range_terms = run_rt;
+    b.run_cut = h->run_cut.p;
+    if (run_sub) {
+      APSS_TRY(ensure(h, h->bk_cnt, (size_t)n_bk + 2));
+      APSS_TRY(ensure(h, h->bk_base, (size_t)n_bk + 2));
+      APSS_TRY(ensure(h, h->run_ent, (size_t)build_nnz));
+      int sh = 0;
+      while ((1 << sh) < run_sub) ++sh;
+      b.sub_shift = sh;
+      b.n_sub = n_sub;
+      b.sub_cnt = h->bk_cnt.p;
+      b.sub_base = h->bk_base.p;
+      b.o_ent = h->run_ent.p;
+    }
+  }
   const int threads = 256;
   const int64_t blocks = ceil_div((h->idx_rows - r0) * kWave, threads);
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
@@ -737,8 +815,17 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
     HIPCHK(h, hipGetLastError());
   }
   const dim3 lds_grid((unsigned)((n_tiles - tile0) * n_ranges));
+  const size_t run_lds = (size_t)run_rt * sizeof(uint32_t);
   if (bucket_build) {}  // (counted above, group by group)
-  else if (lds_build) hipLaunchKernelGGL(k_tile_hist_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
+  else if (run_build) {
+    hipLaunchKernelGGL(k_row_cuts, dim3((unsigned)ceil_div((h->idx_rows - r0) * kGroup, threads)), dim3(threads), 0, h->stream, b, n_ranges,
+                       h->run_cut.p);
+    launch_tile_runs<kRunHist>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
+    if (run_sub) {
+      APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, n_bk));
+      launch_tile_runs<kRunPartition>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
+    }
+  } else if (lds_build) hipLaunchKernelGGL(k_tile_hist_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
   else hipLaunchKernelGGL(k_tile_hist, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);
   APSS_TRY(launch_tile_scan(h, ix, tile0, n_tiles - tile0, lds_build ? 1u : 0u, tile0 == 0 ? ix.chunkw.p : nullptr, 1u));
   HIPCHK(h, hipGetLastError());
@@ -772,7 +859,10 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
       if (group_tiles < n_tiles) APSS_TRY(bucket_group(g0, gt));  // (a single group's buckets are still there)
       hipLaunchKernelGGL(k_tile_scatter_lds, dim3((unsigned)(gt * n_ranges)), dim3(1024), 0, h->stream, b, g0, n_ranges);
     }
-  } else if (lds_build) hipLaunchKernelGGL(k_tile_scatter_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
+  } else if (run_build && run_sub) {
+    hipLaunchKernelGGL(k_tile_place_sub, dim3((unsigned)n_bk), dim3(kPlaceBlock), 0, h->stream, b, tile0);  // the partitioned entries, sub-range by sub-range
+  } else if (run_build) launch_tile_runs<kRunScatter>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
+  else if (lds_build) hipLaunchKernelGGL(k_tile_scatter_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
   else hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);
   if (ix.coarse && ix.cb <= 32768 && h->dbgcfg.bank_order)
     hipLaunchKernelGGL(k_seg_bank_order, dim3((unsigned)ceil_div((n_tiles - tile0) * stride * kWave, 256)), dim3(256), 0, h->stream,
@@ -2652,7 +2742,7 @@ void apss_destroy(apss_handle *h) {
   release(h->head_pos); release(h->W);
   for (apss_handle::TailView *v : {&h->tv, &h->qtv}) { release(v->rowptr); release(v->idx); release(v->val); release(v->erow); }
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
-  release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val);
+  release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);

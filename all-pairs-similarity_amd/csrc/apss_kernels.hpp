@@ -359,6 +359,15 @@ struct BuildArgs {
   const int64_t *ent_base;        // LDS build over BUCKETED entries (dims of more than kBuildMaxRanges ranges): workgroup w = (tile, range)
                                   //   reads entries [ent_base[w], ent_base[w + 1]) of idx / erow / val, which then point at the
                                   //   bucketed copies (k_bucket_scatter); null: the tile's entries as they lie in the store
+  const uint32_t *run_cut;        // run-reading LDS build (k_row_cuts): [row1 - row0][n_ranges + 1], see there
+  int32_t term_lo, term_hi;       // the handle's term range: a (tile, range) workgroup outside it has nothing to read
+  // ... in two passes (k_tile_runs<kRunPartition>): the entries of a (tile, range) are first partitioned into SUB-ranges of
+  // 2^sub_shift terms -- bucket (tile - tile0) * n_sub + term >> sub_shift of o_ent, sizes from the histogram (sub_cnt),
+  // starts from their scan (sub_base) -- and k_tile_place_sub then places them sub-range by sub-range
+  int32_t sub_shift, n_sub;
+  unsigned long long *sub_cnt;
+  const int64_t *sub_base;
+  uint2 *o_ent;                   // {term, finished posting word}: one 8-B store per entry (coarse renderings)
 };
 
 // one wave per row: coalesced reads of the row's entries
@@ -530,6 +539,9 @@ __global__ void k_tile_shift(ShiftArgs a) {
 // streams the tile's entries and keeps the range's counters / cursors in LDS, so the 2 x 1e8 global atomics of
 // k_tile_hist / k_tile_scatter (2.7e10/s on this part, whatever their scope) become LDS atomics.  Each range re-reads
 // the tile's entries, which is why large dims (C5: 1M terms = 31 ranges) stay with the global-atomic kernels.
+// These STREAMING kernels are what a build of ONE range takes (every entry is read once, coalesced), what the bucketed
+// build of large dims runs over its buckets, and what APSS_DEBUG=build_stream keeps; with two ranges or more the
+// run-reading kernels below read a tile's entries once instead of once per range.
 constexpr int kBuildRange = 16384;    // 64 KB of LDS counters: two workgroups per CU (C3: 217 workgroups instead of 124; build 5.0 -> 3.8 ms)
 constexpr int kBuildMaxRanges = 16;
 
@@ -605,6 +617,260 @@ __global__ __launch_bounds__(1024) void k_tile_scatter_lds(BuildArgs a, int64_t 
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// RUN-READING LDS build.  The streaming kernels above read a tile's entries once per term range (C3: 7 ranges -- idx, erow
+// and val of 1e8 entries seven times over, 11 GB to place 0.4 GB of postings).  But the rows of the store are sorted by term
+// (k_ingest_count rejects a batch whose indices are not strictly increasing, k_ingest_write and the tail view compact in
+// order), so the entries of row r that belong to range g are ONE contiguous run of the row.  k_row_cuts reads idx once and
+// leaves, per row, where each range's run starts; a (tile, range) workgroup of k_tile_runs then reads exactly its runs: the
+// row of an entry comes from the loop (erow is not read), row_scale[row] is read once per row, and a workgroup's time is
+// proportional to its own entries -- which makes narrower ranges (more workgroups for the 512 slots) affordable, and lets a
+// term shard's workgroups outside [term_lo, term_hi) leave at once.  Counters / cursors, tile_seg, tile_post_base, segment
+// alignment and padding are those of the streaming kernels; order inside a segment stays arbitrary.
+//
+// run_cut[(row - row0) * (n_ranges + 1) + g] = offset, from the first entry of the row's TILE, of the row's first entry whose
+// term is >= g * range_terms (g = n_ranges: the row's end, or its first term outside [0, dim)).  32 bits: the host takes this
+// build only while (longest row) x (rows per tile) < 2^32.  One 16-lane group per row.
+constexpr int kRunRange = 16384;  // terms per range of the run-reading build (8192: twice the workgroups, half the run per row -- C3 build
+                                  //   3.1 ms against 2.5, profiles/build_runs.md)
+constexpr int kRunRows = 4;       // rows in flight per lane group
+
+__global__ void k_row_cuts(BuildArgs a, int32_t n_ranges, uint32_t *cut) {
+  const int64_t row = a.row0 + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGroup;
+  const int gl = threadIdx.x % kGroup;
+  if (row >= a.row1) return;
+  const int64_t tb = a.rowptr[row / a.cb * a.cb], b = a.rowptr[row], e = a.rowptr[row + 1];
+  uint32_t *c = cut + (row - a.row0) * (n_ranges + 1);
+  const uint32_t rt = (uint32_t)a.range_terms;
+  auto range_of = [&](int32_t t) { return (uint32_t)t < (uint32_t)a.dim ? (int32_t)((uint32_t)t / rt) : n_ranges; };  // (a term outside [0, dim) ends the last run)
+  // entry k opens every range after its predecessor's up to its own (ranges without an entry: empty runs that start here)
+  for (int64_t k = b + gl; k < e; k += kGroup) {
+    const int32_t g = range_of(a.idx[k]);
+    const int32_t gp = k > b ? range_of(a.idx[k - 1]) : -1;
+    for (int32_t j = gp + 1; j <= g; ++j) c[j] = (uint32_t)(k - tb);
+  }
+  if (gl == 0) {
+    const int32_t gp = e > b ? range_of(a.idx[e - 1]) : -1;
+    for (int32_t j = gp + 1; j <= n_ranges; ++j) c[j] = (uint32_t)(e - tb);
+  }
+}
+
+// MODE kRunHist: the histogram (tile_seg[.].y = segment lengths; with sub_cnt also the entries per sub-range); kRunScatter: the
+// scatter (cursors start at tile_seg[.].x); kRunPartition: the first pass of the two-pass scatter (cursors per sub-range).
+// L lanes per row (the host picks it from the mean run length), kRunRows rows in flight per lane group: the chain
+// cut -> idx / val -> LDS atomic -> scattered store of one row overlaps that of the next three.  Runs longer than L are
+// finished kRunRows chunks at a time.  The one-pass scatter costs what its 4-B stores cost (C3: 2.4 ms, 3.1 GB of 32-B
+// partial writes for 0.45 GB of postings, whatever L, kRunRows or the range width); coarse renderings take the partition
+// pass + k_tile_place_sub instead (0.9 + 0.3 ms).
+constexpr int kRunHist = 0, kRunScatter = 1, kRunPartition = 2;
+template <int MODE, int L>
+__global__ __launch_bounds__(1024) void k_tile_runs(BuildArgs a, int64_t tile0, int32_t n_ranges) {
+  extern __shared__ uint32_t run_lds[];  // [range_terms] counters / cursors
+  constexpr bool SCATTER = MODE == kRunScatter, PART = MODE == kRunPartition, VALS = MODE != kRunHist;
+  constexpr int U = kRunRows, GR = 1024 / L;
+  const int tid = threadIdx.x;
+  const int64_t tile = tile0 + blockIdx.x / n_ranges;
+  const int32_t g = (int32_t)(blockIdx.x % n_ranges);
+  const int32_t lo = g * a.range_terms;
+  const uint32_t span = (uint32_t)(min(a.dim, lo + a.range_terms) - lo);
+  uint2 *sg = a.tile_seg + tile * a.seg_stride + lo;
+  if (lo >= a.term_hi || lo + (int32_t)span <= a.term_lo) {  // not a term of this handle in the range: every run is empty
+    if (MODE == kRunHist) {
+      for (uint32_t i = tid; i < span; i += 1024) sg[i] = make_uint2(0u, 0u);
+      if (a.sub_cnt)
+        for (uint32_t i = tid; i <= (span - 1) >> a.sub_shift; i += 1024) a.sub_cnt[(tile - tile0) * a.n_sub + (lo >> a.sub_shift) + i] = 0ull;
+    }
+    return;
+  }
+  // (partition: bucket starts relative to the workgroup's first bucket -- a tile's entries fit 32 bits)
+  const int64_t sub0 = PART ? (tile - tile0) * a.n_sub + (lo >> a.sub_shift) : 0;
+  const int64_t part_base = PART ? a.sub_base[sub0] : 0;
+  if (PART) {
+    for (uint32_t i = tid; i <= (span - 1) >> a.sub_shift; i += 1024) run_lds[i] = (uint32_t)(a.sub_base[sub0 + i] - part_base);
+  } else {
+    for (uint32_t i = tid; i < span; i += 1024) run_lds[i] = SCATTER ? sg[i].x : 0u;
+  }
+  __syncthreads();
+  const int64_t rA = tile * a.cb, rB = min(a.row1, rA + (int64_t)a.cb);
+  const int64_t eA = a.rowptr[rA];
+  const uint32_t tile_e = (uint32_t)(a.rowptr[rB] - eA);  // no cut points beyond the tile's entries, whatever the table holds
+  const int32_t *idx = a.idx + eA;
+  const float *val = a.val + eA;
+  const int32_t cw = n_ranges + 1;
+  const uint32_t *cut = a.run_cut + (rA - a.row0) * cw + g;
+  const int32_t nrows = (int32_t)(rB - rA);
+  const int64_t pbase = SCATTER ? a.tile_post_base[tile] : 0;
+  const bool scaled = VALS && a.coarse && a.row_scale;
+  const int gi = tid / L, gl = tid % L;
+
+  // U entries at once: every LDS atomic is issued before the first store waits for its position
+  auto emit = [&](const int32_t (&t)[U], const float (&v)[U], const uint32_t (&local)[U], const float (&sc)[U]) {
+    uint32_t pos[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if ((uint32_t)(t[u] - lo) < span) pos[u] = atomicAdd(&run_lds[PART ? (t[u] - lo) >> a.sub_shift : t[u] - lo], 1u);
+    if (MODE == kRunHist) return;
+    if (PART) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if ((uint32_t)(t[u] - lo) < span) {
+          const float wv_ = sc[u] > 0.f ? v[u] / sc[u] : v[u];
+          a.o_ent[part_base + pos[u]] =
+              make_uint2((uint32_t)t[u], a.coarse_wide ? pack_coarse_wide(local[u], wv_) : pack_coarse(local[u] << a.coarse_shift, wv_));
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if ((uint32_t)(t[u] - lo) < span) {
+        if (a.coarse) {
+          const float wv_ = sc[u] > 0.f ? v[u] / sc[u] : v[u];
+          a.post_c[pbase + pos[u]] = a.coarse_wide ? pack_coarse_wide(local[u], wv_) : pack_coarse(local[u] << a.coarse_shift, wv_);
+        } else {
+          Posting p;
+          p.slot = local[u];
+          p.w = v[u];
+          a.post[pbase + pos[u]] = p;
+        }
+      }
+    }
+  };
+  auto load_cuts = [&](int32_t r0, uint32_t (&clo)[U], uint32_t (&chi)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int32_t r = r0 + u * GR;
+      const bool in = r < nrows;
+      clo[u] = in ? min(cut[(int64_t)r * cw], tile_e) : 0u;
+      chi[u] = in ? min(cut[(int64_t)r * cw + 1], tile_e) : 0u;
+    }
+  };
+
+  // the first chunk (L entries) of every run of an iteration's rows; the scale of a row travels with its entries
+  auto load_heads = [&](int32_t r0, const uint32_t (&clo)[U], const uint32_t (&chi)[U], int32_t (&t)[U], float (&v)[U], float (&sc)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t k = clo[u] + gl;
+      const bool in = k < chi[u];
+      t[u] = in ? idx[k] : -1;
+      v[u] = VALS && in ? val[k] : 0.f;
+      sc[u] = scaled && in ? a.row_scale[rA + r0 + u * GR] : 1.0f;
+    }
+  };
+  // Software pipeline, two iterations deep: the entries of the NEXT iteration's rows and the cuts of the one after are
+  // requested before this iteration's atomics and stores.  Memory instructions retire in order (vmcnt): a load issued
+  // behind a scattered store would be waited for only once that store has reached memory, a load issued ahead of it is not.
+  uint32_t nlo[U], nhi[U], clo[U], chi[U];
+  int32_t nt[U];
+  float nv[U], nsc[U];
+  load_cuts(gi, clo, chi);
+  load_cuts(gi + GR * U, nlo, nhi);
+  load_heads(gi, clo, chi, nt, nv, nsc);
+  for (int32_t r0 = gi; r0 < nrows; r0 += GR * U) {
+    uint32_t lo_c[U], hi_c[U], local[U];
+    int32_t t[U];
+    float v[U], sc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      lo_c[u] = clo[u];
+      hi_c[u] = chi[u];
+      t[u] = nt[u];
+      v[u] = nv[u];
+      sc[u] = nsc[u];
+      local[u] = (uint32_t)(r0 + u * GR);
+      clo[u] = nlo[u];
+      chi[u] = nhi[u];
+    }
+    load_heads(r0 + GR * U, clo, chi, nt, nv, nsc);
+    load_cuts(r0 + 2 * GR * U, nlo, nhi);
+    emit(t, v, local, sc);
+    // what is left of runs longer than L
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      uint32_t loc1[U];
+      float sc1[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        loc1[j] = local[u];
+        sc1[j] = sc[u];
+      }
+      for (uint32_t k0 = lo_c[u] + L + gl; k0 < hi_c[u]; k0 += L * U) {
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+          const uint32_t k = k0 + j * L;
+          const bool in = k < hi_c[u];
+          t[j] = in ? idx[k] : -1;
+          v[j] = VALS && in ? val[k] : 0.f;
+        }
+        emit(t, v, loc1, sc1);
+      }
+    }
+  }
+  if (MODE != kRunHist) return;
+  __syncthreads();
+  for (uint32_t i = tid; i < span; i += 1024) sg[i] = make_uint2(0u, run_lds[i]);
+  if (a.sub_cnt) {  // entries per sub-range: one wave per sub-range at a time (sub-ranges are multiples of 64 terms)
+    const uint32_t n_sub_wg = ((span - 1) >> a.sub_shift) + 1;
+    for (uint32_t sb = tid / kWave; sb < n_sub_wg; sb += 1024 / kWave) {
+      uint32_t sum = 0;
+      for (uint32_t i = (sb << a.sub_shift) + tid % kWave; i < min(span, (sb + 1) << a.sub_shift); i += kWave) sum += run_lds[i];
+      for (int o = kWave / 2; o; o >>= 1) sum += (uint32_t)__shfl_xor((int)sum, o);
+      if (tid % kWave == 0) a.sub_cnt[(tile - tile0) * a.n_sub + (lo >> a.sub_shift) + sb] = (unsigned long long)sum;
+    }
+  }
+}
+
+// Second pass of the two-pass scatter: workgroup (tile, sub-range) reads its bucket of {term, posting word} in one stream and
+// places the words through LDS cursors.  Its corner of the posting array (C3: 256 terms x ~56 slots x 4 B = 57 KB) stays in
+// the L2 while it is written, so memory sees whole lines: the one-pass scatter's 4-B stores land all over a 3.6-MB region
+// per workgroup and reach memory as 32-B partial writes, 3.1 GB for 0.45 GB of postings (profiles/build_runs.md).
+constexpr int kPlaceBlock = 512;
+constexpr int kPlaceMaxTerms = 1024;
+constexpr int kPlaceStage = 15360;  // words of the posting array a workgroup assembles in LDS (with the cursors: 64 KB, two workgroups per CU)
+__global__ __launch_bounds__(kPlaceBlock) void k_tile_place_sub(BuildArgs a, int64_t tile0) {
+  __shared__ uint32_t cur[kPlaceMaxTerms];
+  __shared__ uint32_t stage[kPlaceStage];
+  const int tid = threadIdx.x;
+  const int64_t tile = tile0 + blockIdx.x / a.n_sub;
+  const int32_t lo = (int32_t)(blockIdx.x % a.n_sub) << a.sub_shift;
+  const uint32_t span = (uint32_t)(min(a.dim, lo + (1 << a.sub_shift)) - lo);
+  const int64_t eA = a.sub_base[blockIdx.x], eB = a.sub_base[blockIdx.x + 1];
+  if (eA >= eB) return;
+  const uint2 *sg = a.tile_seg + tile * a.seg_stride + lo;
+  // the sub-range's corner of the posting array: [first segment's start, the start of the segment behind the last one)
+  const int64_t pbase = a.tile_post_base[tile];
+  const uint32_t w0 = sg[0].x;
+  const uint32_t w1 = lo + (int32_t)span < a.dim ? sg[span].x : (uint32_t)(a.tile_post_base[tile + 1] - pbase);
+  // assembled in LDS (padding between the segments included: zero words) and written out in whole lines; a corner too large
+  // for that (skewed terms) is written posting by posting
+  const bool staged = w1 >= w0 && w1 - w0 <= (uint32_t)kPlaceStage;
+  const uint32_t rel = staged ? w0 : 0u;
+  for (uint32_t i = tid; i < span; i += kPlaceBlock) cur[i] = sg[i].x - rel;
+  if (staged)
+    for (uint32_t i = tid; i < w1 - w0; i += kPlaceBlock) stage[i] = 0u;
+  __syncthreads();
+  uint32_t *out = a.post_c + pbase;
+  for (int64_t k = eA + tid; k < eB; k += 4 * kPlaceBlock) {
+    uint2 e[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = k + kPlaceBlock * j < eB ? a.o_ent[k + kPlaceBlock * j] : make_uint2(0xffffffffu, 0u);
+    uint32_t pos[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e[j].x - (uint32_t)lo < span) pos[j] = atomicAdd(&cur[e[j].x - (uint32_t)lo], 1u);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (e[j].x - (uint32_t)lo < span) {
+        if (!staged) out[pos[j]] = e[j].y;
+        else if (pos[j] < w1 - w0) stage[pos[j]] = e[j].y;
+      }
+    }
+  }
+  if (!staged) return;
+  __syncthreads();
+  for (uint32_t i = tid; i < w1 - w0; i += kPlaceBlock) out[w0 + i] = stage[i];
 }
 
 // ---------------------------------------------------------------------------------------------------------
