@@ -21,6 +21,13 @@
 //  * NO TRIPS THROUGH THE SCALAR UNIT ON THE HOT PATH.  Idle lanes add to spare LDS words / write spare strip entries
 //    (selects on the address, no exec masks); first touches and crossings are counted per lane; one branch per round takes
 //    everything unusual.  Loaded values are used a round after their load, by the next stage.
+//  * FEW VECTOR INSTRUCTIONS PER POSTING SLOT (LEAN: every instantiation with non-negative weights; the kernel is bound by the
+//    vector instructions it issues).  A batch's crossings are found by the MAXIMUM of old + product over its postings, one
+//    compare per batch; an idle lane's spare word is kept small and non-zero (set to 1 in every round's clear phase), so its
+//    returned value needs no replacing -- it is never a first touch and its sum is far below any real threshold; first touches
+//    are counted through their complement, min(old, 1) summed per lane, against the slots tested per round; and an adding
+//    wave INVALIDATES the window entries of a strip it has just read (offset kStale), so that an entry the staging waves do
+//    not rewrite two rounds later sends its load out of range by itself -- no slot-against-count test per window step.
 //
 // Pipeline (round v of a workgroup = one query against the tile's accumulators):
 //   round v - 5 : staging waves load the row's extent                  (load_R)
@@ -64,6 +71,10 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   constexpr int kLongLen = kLongLenW;
   constexpr int CBMAX = WIDE ? 131072 : (BLOCK <= 512 && !ACC8 ? 32768 : 65536);
   constexpr int APW = 32 / (int)ABITS;
+  constexpr bool LEAN = !SIGNED;  // (signed sums are not monotone: a maximum of old + product says nothing about a crossing)
+  // an idle lane adds 1 to the low accumulator of its spare word, which the NW - 1 adding waves' lanes of that number share:
+  // set to 1 every round, it stays non-zero inside its ABITS bits
+  static_assert(1 + (NW - 1) * 2 * U < (1 << (ACC8 ? 8 : 16)), "the spare words' low accumulators must not wrap within a round");
   __shared__ __attribute__((aligned(16))) uint32_t acc[CBMAX / APW + kWave];  // (+ one spare word per lane: idle lanes add there)
   __shared__ __attribute__((aligned(16))) uint2 strips[3 * NS * SSZ + kWave];  // [3][NS][GPW][GS] {byte offset of the chunk's first posting, weight bits} (+ one spare entry per lane)
   __shared__ uint2 longs[3 * LONGCAP];
@@ -125,6 +136,11 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   const __amdgpu_buffer_rsrc_t rs_po =
       __builtin_amdgcn_make_buffer_rsrc((void *)(a.post_c + pbase), 0, (int)((pend - pbase) * 4), 0x00020000);
   constexpr uint32_t kOob = 0xfffffff0u;
+  // LEAN: the offset of an invalidated strip entry, and what a round flagged for the direct sweep adds to every offset of its
+  // window (its strips hold what was staged before the flag went up).  A tile's postings are < 2^29 bytes (apss_hip.hip takes
+  // the two-pass path below 2^27 postings per tile), so with the lane's part (< 64) on top: kStale + .. in [2^31, 2^31 + 64),
+  // valid + kSwept + .. in [2^30, 2^30 + 2^29 + 64), kStale + kSwept + .. in [3 * 2^30, 3 * 2^30 + 64) -- all out of range.
+  constexpr uint32_t kStale = 0x80000000u, kSwept = 0x40000000u;
   constexpr uint32_t kRare = 0x80000000u;  // WaveWork::info: the round needs more than the register window (see strip_loads)
   constexpr uint32_t kCountMask = 0xffffu;  // WaveWork::info bits 16..19: window steps that hold chunks of this wave
   // SKIP: a wave skips the window steps behind its last chunk (adds, tests, clears).  A wave otherwise issues all U steps
@@ -135,10 +151,15 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   // (the 1024-thread kernel only ever skips its LAST step: with every step behind a branch C5's shape measured 245 vs 219 ms)
   constexpr int kFirstSkippable = BLOCK > 512 ? U - 1 : 0;
 
-  for (int i = tid * 4; i < cb / APW + kWave; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
+  for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
+  if (tid < kWave) acc[CBMAX / APW + tid] = 1u;  // the spare words (LEAN: never zero in their low accumulator)
+  if (LEAN) {  // no strip entry is valid before it is staged
+    for (int i = tid; i < 3 * NS * SSZ; i += BLOCK) strips[i].x = kStale;
+  }
   if (tid < 8) facts_w[tid] = 0;
   unsigned long long my_visits = 0;
   uint32_t my_cands = 0;
+  uint32_t n_seen = 0;  // LEAN: window slots that were NOT a first touch, minus the window slots tested (mod 2^32)
 
   struct RowExt { int qb; int nnz; };  // as loaded: the low halves of the row's rowptr entries
   struct TermW { uint32_t term; float w, qs; bool valid; };
@@ -254,6 +275,12 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) sr.it[u] = st[u];
     }
+    if (LEAN) {
+      // read: now invalid.  Lane i < WIN takes window slot i (entry (i % 8) * GS + i / 8, as the staging waves place it), the
+      // others their spare entry; the staging of two rounds on rewrites the slots it fills, behind two barriers
+      uint2 *const own = strips + (ring * NS + rank) * SSZ + (ln & 7) * GS + (ln >> 3);
+      (ln < WIN ? own : spare_item)->x = kStale;
+    }
   };
   // second half: every LPC lanes take one chunk of the strip and start its posting load.  VALU only -- the one value the
   // next round branches on (is it more than a register window?) goes to the scalar unit here, a round before its use.
@@ -267,12 +294,15 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
     f.flags = sr.fc.y;
 #pragma unroll
     for (int u = 0; u < U; ++u) asm volatile("" : "+v"(sr.it[u].x), "+v"(sr.it[u].y));
+    const uint32_t lane_off = lo * 8u + (LEAN && (sr.fc.y & 1u) ? kSwept : 0u);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       // a posting word of zero is no posting (segments are zero-padded to whole chunks; out-of-range reads return zero);
-      // a strip slot past the wave's last chunk holds a stale descriptor: its load is sent out of range
+      // a strip slot past the wave's last chunk holds a stale descriptor: its load is sent out of range (LEAN: it was
+      // invalidated when it was read, see strip_read)
       f.wq[u] = __uint_as_float(sr.it[u].y);
-      f.pc[u] = __builtin_amdgcn_raw_buffer_load_b64(rs_po, (uint32_t)(u * GPW + ln / LPC) < mine ? sr.it[u].x + lo * 8u : kOob, 0, 0);
+      const uint32_t off = LEAN ? sr.it[u].x + lane_off : ((uint32_t)(u * GPW + ln / LPC) < mine ? sr.it[u].x + lo * 8u : kOob);
+      f.pc[u] = __builtin_amdgcn_raw_buffer_load_b64(rs_po, off, 0, 0);
     }
   };
 
@@ -375,6 +405,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
       // being masked off: an exec mask around each atomic is a trip VALU -> scalar unit -> VALU (compare, s_and_saveexec,
       // s_or) that cost ~64 cycles of the wave's serial issue per posting slot (profiles/microbench/issue_rate.hip).  Its
       // "old value" is replaced by thr1 + 1 afterwards: never a first touch (not 0), never a crossing (thr1 - old wraps).
+      // (LEAN, window path: not replaced -- the spare word's low accumulator is in [1, 2 U (NW - 1)], see check_batch)
       const uint32_t spare = (uint32_t)(CBMAX / APW) * 4u + (uint32_t)ln * 4u;
       auto add_or_spare = [&](const uint32_t pcw, const uint32_t p) -> uint32_t {
         const uint32_t addr = WIDE ? (pcw >> 15) & 0x1fffcu : (SLOT2 ? pcw & 0xfffcu : ((pcw & 0xffffu) >> 1) * 4u);
@@ -384,7 +415,8 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
       // two postings of a sweep the same way: no masks around the atomics, one (rare, divergent) branch for both crossings
       auto visit2 = [&](const uint32_t x, const uint32_t y, const float wqs) {
         const uint32_t px = prod(x, wqs), py = prod(y, wqs);
-        uint32_t ox = add_or_spare(x, px), oy = add_or_spare(y, py);
+        // (LEAN: a sweep's idle lanes add nothing -- the spare words' bound is the window's)
+        uint32_t ox = add_or_spare(x, LEAN && x == 0u ? 0u : px), oy = add_or_spare(y, LEAN && y == 0u ? 0u : py);
         ox = x ? half_of(ox, x) : thr1 + 1u;
         oy = y ? half_of(oy, y) : thr1 + 1u;
         my_cands += (ox == 0u ? 1u : 0u) + (oy == 0u ? 1u : 0u);
@@ -394,6 +426,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
         }
       };
       const int n_steps = SKIP ? (int)((w0.info >> 16) & 0xfu) : U;  // (scalar: a branch on it costs no trip from the VALU)
+      if (LEAN) n_seen -= 2u * (uint32_t)(SKIP ? max(n_steps, kFirstSkippable) : U);  // the slots the batches below test
       auto issue_batch = [&](const int u0, uint32_t (&p0)[BATCH], uint32_t (&p1)[BATCH], uint32_t (&o0)[BATCH], uint32_t (&o1)[BATCH]) {
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) {
@@ -408,6 +441,41 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
         }
       };
       auto check_batch = [&](const int u0, uint32_t (&p0)[BATCH], uint32_t (&p1)[BATCH], uint32_t (&o0)[BATCH], uint32_t (&o1)[BATCH]) {
+        if constexpr (LEAN) {
+          // one add per posting and one max per pair: the largest old + product of the batch passes thr1 iff some add of it
+          // crossed or landed on a sum that had crossed before (true pairs only; the exact test is below, where it is rare).
+          // An idle lane's old value is its spare word's: >= 1, so it counts itself as seen, and its sum is a few hundred at
+          // the most -- below it, a threshold merely sends the batch through the exact test.
+          uint32_t top = 0;
+#pragma unroll
+          for (int j = 0; j < BATCH; ++j) {
+            const int u = u0 + j;
+            if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+            if (u < U) {
+              o0[j] = half_of(o0[j], w0.pc[u].x);
+              o1[j] = half_of(o1[j], w0.pc[u].y);
+              // (written out: the compiler turns min(old, 1) back into a compare, a select and a carry chain with its waits)
+              uint32_t s0, s1;
+              asm("v_min_u32 %0, 1, %1" : "=v"(s0) : "v"(o0[j]));
+              asm("v_min_u32 %0, 1, %1" : "=v"(s1) : "v"(o1[j]));
+              n_seen += s0 + s1;
+              top = max(max(top, o0[j] + p0[j]), o1[j] + p1[j]);
+            }
+          }
+          if (__any(top > thr1)) {
+#pragma unroll
+            for (int j = 0; j < BATCH; ++j) {
+              const int u = u0 + j;
+              if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+              if (u < U) {
+                const uint32_t a0 = w0.pc[u].x ? o0[j] : thr1 + 1u, a1 = w0.pc[u].y ? o1[j] : thr1 + 1u;  // (an idle lane never crosses)
+                report(thr1 - a0 < p0[j], slot_of(w0.pc[u].x), a0 + p0[j]);
+                report(thr1 - a1 < p1[j], slot_of(w0.pc[u].y), a1 + p1[j]);
+              }
+            }
+          }
+          return;
+        }
         // first touches and crossings are counted per lane (VALU only); one trip to the scalar unit per batch decides
         // whether any lane crossed
         uint32_t n_cross = 0;
@@ -495,6 +563,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
       }
       __syncthreads();  // every add of the round has landed
 
+      if (LEAN) *reinterpret_cast<uint32_t *>(smem_raw + spare) = 1u;  // the idle lanes' word starts every round at 1
       if (rare) {  // (long or direct sweeps, or chunks past the window: their postings are not in registers) whole-tile clear
         for (int i = atid * 4; i < cb / APW; i += ABLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
       } else {
@@ -533,7 +602,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   if (tid < 3) stat[tid] = 0;
   __syncthreads();
   atomicAdd(&stat[0], my_visits);
-  atomicAdd(&stat[1], (unsigned long long)my_cands);
+  atomicAdd(&stat[1], (unsigned long long)(my_cands - n_seen));
   __syncthreads();
   if (tid == 0) {
     const unsigned long long twice = a.tri && tile < qtile ? 2ull : 1ull;  // (both counts are symmetric in the two tiles)
