@@ -25,12 +25,15 @@ SYMBOLS = [
     "apss_group_relayout", "apss_group_layout_get",
     # T x D grids of term ranges x row ranges
     "apss_group_create_grid", "apss_group_grid_get",
+    # per-query top-k (csrc/apss_topk.hpp)
+    "apss_set_top_k", "apss_topk_get", "apss_group_set_top_k", "apss_group_topk_get",
 ]
 GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
 GROUP_NO_SYMMETRIC_RANGES = 8
 EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
 GROUP_MAX_MEMBERS = 64
 DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
+TOP_K_MAX = 1024
 SYM_RAN, SYM_FLAG, SYM_NOT_WHOLE, SYM_PATH, SYM_LONG_ROWS, SYM_ONE_TILE, SYM_CHUNK = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -76,6 +79,12 @@ class GroupGrid(C.Structure):
                 ("symmetric_ranges", C.c_int32), ("rows_in_range", C.c_int64 * GROUP_MAX_MEMBERS),
                 ("outside_rows_max", C.c_int64), ("mirrored_pairs", C.c_int64), ("own_ms_max", C.c_double),
                 ("outside_ms_max", C.c_double)]
+
+
+class TopkInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("pairs_over_theta", C.c_int64), ("kept", C.c_int64),
+                ("queries_cut", C.c_int64), ("longest_segment", C.c_int64), ("select_ms", C.c_double),
+                ("select_launches", C.c_int32), ("reserved0", C.c_int32)]
 
 
 def build_sources():
@@ -222,5 +231,13 @@ def lib():
     L.apss_group_relayout.argtypes = [vp, vp]
     L.apss_group_layout_get.restype = i32
     L.apss_group_layout_get.argtypes = [vp, C.POINTER(GroupLayout)]
+    for name in ("apss_set_top_k", "apss_group_set_top_k"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i32]
+    for name in ("apss_topk_get", "apss_group_topk_get"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, C.POINTER(TopkInfo)]
     _lib = L
     return L

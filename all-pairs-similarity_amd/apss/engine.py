@@ -26,7 +26,7 @@ def _ptr(a):
 
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
-                 capacity_rows=0, capacity_nnz=0, head_terms=0):
+                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -47,6 +47,12 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
+        if top_k:
+            try:
+                self.set_top_k(top_k)
+            except ApssError:
+                self.close()
+                raise
 
     # -- lifetime
     def close(self):
@@ -125,6 +131,18 @@ class ApssIndex:
         d = {k: getattr(st, k) for k, _ in _lib.Stats._fields_}
         d["probe_kernel"] = d["probe_kernel"].decode()
         return d
+
+    def set_top_k(self, k):
+        """per-query top-k for the query-type calls made from now on (0: off); the list then comes grouped by query row, in
+        rank order (score descending, candidate id ascending, slot ascending)"""
+        self._chk(self._L.apss_set_top_k(self._h, int(k)))
+
+    def topk_info(self):
+        """what the per-query top-k did in the last query-type call (apss_topk_info)"""
+        ti = _lib.TopkInfo()
+        ti.struct_size = C.sizeof(_lib.TopkInfo)
+        self._chk(self._L.apss_topk_get(self._h, C.byref(ti)))
+        return {k: getattr(ti, k) for k, _ in _lib.TopkInfo._fields_}
 
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`
@@ -205,7 +223,7 @@ class ApssGroup:
     (j, i) = row range j, term range i on devices[j * T + i]; every call answers as one plain handle would."""
 
     def __init__(self, dim, theta, devices, flags=0, index_threshold=0.0, tile_rows=0, head_terms=0, group_flags=0,
-                 term_cuts=None, capacity_rows=0, capacity_nnz=0, row_ranges=1):
+                 term_cuts=None, capacity_rows=0, capacity_nnz=0, row_ranges=1, top_k=0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -230,6 +248,12 @@ class ApssGroup:
             if cuts.size != self.term_ranges + 1:
                 raise ValueError("term_cuts must have one entry more than there are term ranges")
             self._chk(L.apss_group_set_term_cuts(self._g, _ptr(cuts)))
+        if top_k:
+            try:
+                self.set_top_k(top_k)
+            except ApssError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_g", None):
@@ -304,6 +328,16 @@ class ApssGroup:
         d = {k: getattr(st, k) for k, _ in _lib.GroupStats._fields_}
         d["term_cuts"] = list(st.term_cuts[: self.term_ranges + 1])
         return d
+
+    def set_top_k(self, k):
+        """per-query top-k of the group's answers (apss_group_set_top_k; not on a grid with more than one row range)"""
+        self._chk(self._L.apss_group_set_top_k(self._g, int(k)))
+
+    def topk_info(self):
+        ti = _lib.TopkInfo()
+        ti.struct_size = C.sizeof(_lib.TopkInfo)
+        self._chk(self._L.apss_group_topk_get(self._g, C.byref(ti)))
+        return {k: getattr(ti, k) for k, _ in _lib.TopkInfo._fields_}
 
     def grid(self):
         """the grid's shape and what its row ranges did in the last call (apss_group_grid_get)"""

@@ -36,6 +36,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/apss.h"
+#include "apss_topk.hpp"
 
 namespace {
 
@@ -379,6 +380,11 @@ struct apss_group {
   DevBuf<int64_t> ext_q, ext_c;
   int64_t n_res = -1;
   bool results_in_handle = false;  // one member, no exchange: the handle's own result list
+  // per-query top-k (apss_topk.hpp; D = 1 only).  One member without an exchange: its handle holds the setting and cuts its own
+  // list.  Exchange modes: the pass runs on member 0's device behind k_threshold_compact, with these buffers
+  int32_t top_k = 0;
+  apss::TopkWork topk;
+  apss_topk_info tk{};
   apss_group_stats st{};
 };
 
@@ -590,6 +596,9 @@ int32_t decide_layout(apss_group *g, std::vector<uint32_t> &df, int64_t n_rows, 
   return APSS_OK;
 }
 
+// the group's answer is its one member's own list (no exchange): that handle applies the per-query top-k itself
+inline bool topk_in_handle(const apss_group *g) { return g->T == 1 && g->D == 1 && !(g->flags & APSS_GROUP_FORCE_EXCHANGE); }
+
 // member m's shard handle for a layout (term range m % T), on the member's stream (*out stays NULL on failure; the message
 // is in err)
 int32_t create_member_handle(apss_group *g, int m, const Layout &L, apss_handle **out, std::string &err) {
@@ -612,6 +621,8 @@ int32_t create_member_handle(apss_group *g, int m, const Layout &L, apss_handle 
     err = apss_last_error(h);
   } else if (!L.head.empty() && (rc = apss_set_head_terms(h, (int32_t)L.head.size(), L.head.data(), i, T)) != APSS_OK) {
     err = std::string("member head block: ") + apss_last_error(h);
+  } else if (topk_in_handle(g) && (rc = apss_set_top_k(h, g->top_k)) != APSS_OK) {
+    err = std::string("member top-k: ") + apss_last_error(h);
   }
   if (rc != APSS_OK) {
     apss_destroy(h);
@@ -1062,6 +1073,29 @@ bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirro
       GHIP(nullptr, M, hipStreamSynchronize(M.stream));
       R.n_phase = (int64_t)nres;
       R.union_pairs += nu;
+      g->tk = apss_topk_info{};
+      g->tk.pairs_over_theta = g->tk.kept = R.n_phase;
+      if (g->top_k > 0 && g->D == 1) {  // the per-query cut of the group's final list (the members are term shards: no k of their own)
+        const int64_t *d_store = nullptr, *d_query = nullptr;
+        int64_t store_rows = 0;
+        if (apss_ext_ids_dev(M.h, &d_store, &d_query) != APSS_OK || apss_size(M.h, &store_rows, nullptr) != APSS_OK || (nres > 0 && !d_store)) {
+          M.err = "per-query top-k: the member's external ids are gone";
+          return APSS_E_STATE;
+        }
+        const hipError_t e = apss::topk_run(g->topk, M.stream, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, b.n, d_store, store_rows, g->top_k, &g->tk);
+        if (e != hipSuccess) {
+          M.err = std::string("per-query top-k: ") + hipGetErrorString(e);
+          return e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
+        }
+        if (R.n_phase > 0) {  // (kept <= n_phase: the selected list fits the buffers it replaces)
+          const size_t kept = (size_t)g->tk.kept;
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_q.p, g->topk.out_q, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_c.p, g->topk.out_c, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_s.p, g->topk.out_s, kept * sizeof(float), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+          R.n_phase = g->tk.kept;
+        }
+      }
       if (g->D > 1) return append_triples(M, R, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, mirrored);
       return APSS_OK;
     };
@@ -1692,6 +1726,10 @@ void apss_group_destroy(apss_group *g) {
       release(M.sp_rowptr[k]); release(M.sp_ext[k]); release(M.sp_idx[k]); release(M.sp_val[k]);
     }
   }
+  if (!g->m.empty()) {
+    (void)hipSetDevice(g->m[0].dev);
+    apss::topk_release(g->topk);
+  }
   for (size_t j = 0; j < g->rr.size() && j * (size_t)g->T < g->m.size(); ++j) {
     apss_group::Range &R = g->rr[j];
     (void)hipSetDevice(g->m[j * (size_t)g->T].dev);
@@ -1901,6 +1939,41 @@ int32_t apss_group_fetch_results(apss_group *g, int64_t offset, int64_t count, i
   const int32_t rc = body();
   if (rc != APSS_OK) g->err = M.err;
   return rc;
+}
+
+int32_t apss_group_set_top_k(apss_group *g, int32_t k) {
+  if (!g) return APSS_E_INVALID;
+  // (a refusal is also left where apss_group_last_error(NULL) finds it: a wrapper that applies k right after the create and
+  // destroys the group when it is refused reports it as a failed create)
+  if (k < 0 || k > APSS_TOP_K_MAX) return gfail(g, APSS_E_INVALID, g_group_create_error = "apss_group_set_top_k: k must be in [0, 1024] (0: off)");
+  if (k > 0 && g->D > 1)
+    return gfail(g, APSS_E_UNSUPPORTED, g_group_create_error = "apss_group_set_top_k: a grid keeps its results as triples per row range on different "
+                                                               "devices; per-query top-k is not available with more than one row range");
+  if (g->created && topk_in_handle(g)) {
+    const int32_t rc = apss_set_top_k(g->m[0].h, k);
+    if (rc != APSS_OK) return gfail(g, rc, apss_last_error(g->m[0].h));
+  }
+  g->top_k = k;
+  return APSS_OK;
+}
+
+int32_t apss_group_topk_get(apss_group *g, apss_topk_info *out) {
+  if (!g || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return gfail(g, APSS_E_INVALID, "apss_topk_info.struct_size must be set to sizeof(apss_topk_info) before the call");
+  if (g->results_in_handle) {
+    const int32_t rc = apss_topk_get(g->m[0].h, out);
+    if (rc != APSS_OK) g->err = apss_last_error(g->m[0].h);
+    return rc;
+  }
+  apss_topk_info t = g->tk;
+  if (g->D > 1 || g->n_res < 0) t = apss_topk_info{};
+  if (g->D > 1 && g->n_res >= 0) t.pairs_over_theta = t.kept = g->n_res;
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_topk_info));
+  t.struct_size = n;
+  std::memcpy(out, &t, (size_t)n);
+  return APSS_OK;
 }
 
 int32_t apss_group_stats_get(apss_group *g, apss_group_stats *out) {

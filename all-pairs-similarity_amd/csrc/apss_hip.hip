@@ -18,6 +18,7 @@
 #include "apss_kernels.hpp"
 #include "apss_head.hpp"
 #include "apss_even.hpp"
+#include "apss_topk.hpp"
 
 using namespace apss;
 
@@ -273,6 +274,10 @@ struct apss_handle {
   int64_t head_nonempty = 0, last_batch_head_nonempty = 0;
   double head_sample_frac = 0.0;      // fraction of sampled pairs the dense filter passed when the policy last looked
   hipEvent_t ev2 = nullptr, ev3 = nullptr;
+  // per-query top-k (apss_topk.hpp): the setting, the pass's buffers, what the last query-type call did
+  int32_t top_k = 0;
+  TopkWork topk;
+  apss_topk_info tk{};
   // stats
   apss_stats st{};
   size_t bytes_reserved = 0;
@@ -1878,9 +1883,9 @@ int32_t exact_pass(apss_handle *h, bool hybrid, double theta, int64_t nq, const 
 int32_t pack_query_head(apss_handle *h, const int64_t *rowptr, const int32_t *idx, const float *val, int64_t nq);
 
 // q_slot_first: slot of query row 0 when the batch is rows of the store (self-join, insert-and-query), else -1.
-int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-              int64_t q_nnz_end, int64_t *n_results) {
+int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+                    int64_t q_nnz_end, int64_t *n_results) {
   const DebugCfg &dbg = h->dbgcfg;
   h->res_q_ext = q_ext;
   h->last_q_rowptr = q_rowptr;
@@ -1983,7 +1988,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     h->no_acc8 = true;
     h->downgrades |= APSS_DOWNGRADE_ACC8;
     APSS_TRY(build_index(h, 0));
-    return probe(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
   }
   if (a8_scale > 0) {
     cx_scale = a8_scale;
@@ -1998,7 +2003,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
   const int64_t tail_n = h->n_rows - h->idx_rows;
   if (tail_n > 0 && (!(coarse_path && !h->sharded) || nq * tail_n > kTailMaxPairs)) {
     APSS_TRY(build_index(h, h->idx_rows));
-    return probe(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
   }
   // a stored batch that still waits in the tail is not in the index: for the join over the index it is an outside batch
   const int64_t q_slot_base = q_slot_first >= 0 && q_slot_first < h->idx_rows ? q_slot_first : -1;
@@ -2011,7 +2016,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     h->head_blocked = true;
     h->downgrades |= APSS_DOWNGRADE_HEAD;
     APSS_TRY(build_index(h, 0));
-    return probe(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
   }
   const bool hybrid = hybrid_wanted;
   // the batch's rows of the dense-head block and its tail ratios: the store's were packed when it was indexed; an outside
@@ -2443,7 +2448,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
       h->no_acc8 = true;
       h->downgrades |= APSS_DOWNGRADE_ACC8;
       APSS_TRY(build_index(h, 0));
-      return probe(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+      return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
     }
     if (std::max(c[kCtrResults], c[kCtrOver]) > a.res_cap) {
       // the result list overflowed (or a list on the way to it did: kCtrOver): grow to what the run asked for and repeat the (idempotent) probe
@@ -2485,6 +2490,34 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     return APSS_OK;
   }
   return fail(h, APSS_E_STATE, "result buffer kept overflowing");
+}
+
+// A query-type call: the join (probe_inner re-enters itself after a downgrade or a rebuild; what it leaves is the call's final
+// list), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp).
+int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+              int64_t q_nnz_end, int64_t *n_results) {
+  h->tk = apss_topk_info{};
+  APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
+  h->tk.pairs_over_theta = h->tk.kept = h->n_res;
+  if (h->top_k <= 0 || h->sharded) return APSS_OK;
+  const size_t before = h->topk.bytes;
+  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, &h->tk);
+  h->bytes_reserved += h->topk.bytes - before;
+  if (e != hipSuccess) {
+    h->n_res = -1;
+    h->err = std::string("per-query top-k: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
+  }
+  if (h->n_res > 0) {
+    h->out_q = h->topk.out_q;
+    h->out_c = h->topk.out_c;
+    h->out_s = h->topk.out_s;
+    h->n_res = h->tk.kept;
+  }
+  h->st.result_pairs = h->n_res;
+  if (n_results) *n_results = h->n_res;
+  return APSS_OK;
 }
 
 int32_t validate_host_csr(apss_handle *h, int64_t n, const int64_t *rowptr, const int32_t *indices,
@@ -2743,6 +2776,7 @@ void apss_destroy(apss_handle *h) {
   for (apss_handle::TailView *v : {&h->tv, &h->qtv}) { release(v->rowptr); release(v->idx); release(v->val); release(v->erow); }
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
   release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent);
+  topk_release(h->topk);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3020,6 +3054,28 @@ int32_t apss_get_head_terms(apss_handle *h, int32_t capacity, int32_t *out_terms
   *n_terms = n;
   if (out_terms)
     for (int32_t i = 0; i < std::min(n, capacity); ++i) out_terms[i] = h->head_terms[(size_t)i];
+  return APSS_OK;
+}
+
+int32_t apss_set_top_k(apss_handle *h, int32_t k) {
+  APSS_TRY(enter(h));
+  // (a refusal is also left where apss_last_error(NULL) finds it: a wrapper that applies k right after apss_create and destroys
+  // the handle when it is refused reports it as a failed create)
+  if (k < 0 || k > APSS_TOP_K_MAX) return fail(h, APSS_E_INVALID, g_create_error = "apss_set_top_k: k must be in [0, 1024] (0: off)");
+  if (k > 0 && h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k: a term shard reports candidates with partial scores; the group cuts behind its exchange");
+  h->top_k = k;
+  return APSS_OK;
+}
+
+int32_t apss_topk_get(apss_handle *h, apss_topk_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_topk_info.struct_size must be set to sizeof(apss_topk_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_topk_info));
+  h->tk.struct_size = n;
+  std::memcpy(out, &h->tk, (size_t)n);
   return APSS_OK;
 }
 

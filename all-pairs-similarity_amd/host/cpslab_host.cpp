@@ -221,11 +221,29 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
     const int32_t rc = D == 1 ? apss_group_create(&c, (int32_t)dev.size(), dev.data(), conf.groupFlags, &g_)
                               : apss_group_create_grid(&c, (int32_t)dev.size() / D, D, dev.data(), conf.groupFlags, &g_);
     if (rc != APSS_OK) throw std::runtime_error(std::string("apss_group_create: ") + apss_group_last_error(nullptr));
+    if (conf.topK != 0) {
+      const int32_t rk = apss_group_set_top_k(g_, conf.topK);
+      if (rk == APSS_E_UNSUPPORTED) {  // a grid: the worker keeps answering with every pair
+        last_error_ = std::string("cpslab.allpair.gpu.topK ignored: ") + apss_group_last_error(g_);
+        conf_.topK = 0;
+      } else if (rk != APSS_OK) {
+        const std::string msg = std::string("apss_group_set_top_k: ") + apss_group_last_error(g_);
+        apss_group_destroy(g_);
+        g_ = nullptr;
+        throw std::runtime_error(msg);
+      }
+    }
     return;
   }
   if (conf.devices.size() == 1) c.device_id = conf.devices[0];
   const int32_t rc = apss_create(&c, &h_);
   if (rc != APSS_OK) throw std::runtime_error(std::string("apss_create: ") + apss_last_error(nullptr));
+  if (conf.topK != 0 && apss_set_top_k(h_, conf.topK) != APSS_OK) {
+    const std::string msg = std::string("apss_set_top_k: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
 }
 
 GpuIndexingWorker::~GpuIndexingWorker() {

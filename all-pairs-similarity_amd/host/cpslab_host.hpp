@@ -92,6 +92,11 @@ struct Config {
   // cpslab.allpair.gpu.rowRanges: D > 1 = a T x D grid (apss_group_create_grid), devices = T x D entries, member (row range j,
   // term range i) on devices[j * T + i]
   int rowRanges = 1;
+  // cpslab.allpair.gpu.topK: 0 (default) = every pair >= similarityThreshold, as the reference; 1 .. 1024 = each query's inner
+  // map holds at most that many candidates, the best by (score descending, candidate id ascending) -- apss_set_top_k /
+  // apss_group_set_top_k.  A grid (rowRanges > 1) does not support it: the refusal is reported through lastError() and the
+  // worker runs with 0
+  int topK = 0;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

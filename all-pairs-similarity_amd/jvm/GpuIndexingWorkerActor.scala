@@ -49,11 +49,19 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     if (conf.hasPath("cpslab.allpair.gpu.adaptiveLayout") && conf.getBoolean("cpslab.allpair.gpu.adaptiveLayout"))
       NativeApss.GROUP_ADAPT_LAYOUT
     else 0
+  // cpslab.allpair.gpu.topK = k (default 0: every pair >= similarityThreshold, as the reference): each query's reply holds at
+  // most k candidates, the best by (score descending, candidate id ascending).  A grid (rowRanges > 1) does not support it: the
+  // worker says so and runs with 0
+  private val topKConf = if (conf.hasPath("cpslab.allpair.gpu.topK")) conf.getInt("cpslab.allpair.gpu.topK") else 0
+  private val topK = if (grouped && rowRanges > 1 && topKConf != 0) {
+    System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.topK is not supported with cpslab.allpair.gpu.rowRanges > 1; running with 0")
+    0
+  } else topKConf
   private val handle =
     if (grouped && rowRanges > 1)
-      NativeApss.createGroupGrid(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, rowRanges)
-    else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags)
-    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms)
+      NativeApss.createGroupGrid(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, rowRanges, topK)
+    else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, topK)
+    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms, topK)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =
     if (grouped) NativeApss.groupSubmit(handle, mode, rowptr, indices, values, ids)

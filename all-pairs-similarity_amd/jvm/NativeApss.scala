@@ -8,8 +8,12 @@ object NativeApss {
   val FLAG_ADMISSION = 2
   val FLAG_NORMALIZE = 4
   val FLAG_NO_SYMMETRY = 64 // a batch that is the whole store is probed in both directions, as IndexingWorkerActor does (include/apss.h)
-  /** headTerms: dense-head block of the library (0 = it decides from the term distribution, -1 = never) */
-  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, headTerms: Int): Long
+  val TOP_K_MAX = 1024
+  /** headTerms: dense-head block of the library (0 = it decides from the term distribution, -1 = never).
+    * topK: 0 = every pair >= theta; 1 .. TOP_K_MAX = at most that many candidates per query, the best by (score descending,
+    * candidate id ascending), the results grouped by query in rank order (apss_set_top_k).  A topK the library refuses
+    * fails the create: 0 is returned and lastError(0) says why */
+  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, headTerms: Int, topK: Int): Long
   @native def destroy(h: Long): Unit
   @native def lastError(h: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */
@@ -32,18 +36,19 @@ object NativeApss {
   val GROUP_FORCE_EXCHANGE = 1
   val GROUP_NO_RCCL = 2
   val GROUP_ADAPT_LAYOUT = 4 // re-decide term cuts and shared head as the store grows (include/apss.h)
-  /** returns the group's handle or 0 (groupLastError(0) says why) */
+  /** returns the group's handle or 0 (groupLastError(0) says why).  topK as for `create` (apss_group_set_top_k: the cut runs
+    * behind the members' exchange); a grid (rowRanges > 1) supports only topK = 0 */
   @native def createGroup(dim: Int, theta: Double, indexThreshold: Double, flags: Int, devices: Array[Int], headTerms: Int,
-                          groupFlags: Int): Long
+                          groupFlags: Int, topK: Int): Long
   val GROUP_NO_SYMMETRIC_RANGES = 8 // grids: every cell meets every other row range, nothing is mirrored
   /** A T x D grid (apss_group_create_grid): devices.length = T x rowRanges, member (row range j, term range i) lives on
     * devices(j * T + i); a batch's rows are spread over the row ranges, every call answers as one handle would.  rowRanges
     * (1..64) travels in bits 16..23 of createGroup's groupFlags: one native entry point creates both shapes.
     * Returns 0 when rowRanges does not divide devices.length (and as createGroup). */
   def createGroupGrid(dim: Int, theta: Double, indexThreshold: Double, flags: Int, devices: Array[Int], headTerms: Int,
-                      groupFlags: Int, rowRanges: Int): Long =
+                      groupFlags: Int, rowRanges: Int, topK: Int = 0): Long =
     if (rowRanges < 1 || rowRanges > 64 || devices.length % rowRanges != 0) 0L
-    else createGroup(dim, theta, indexThreshold, flags, devices, headTerms, (groupFlags & 0xffff) | (rowRanges << 16))
+    else createGroup(dim, theta, indexThreshold, flags, devices, headTerms, (groupFlags & 0xffff) | (rowRanges << 16), topK)
   @native def destroyGroup(g: Long): Unit
   @native def groupLastError(g: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

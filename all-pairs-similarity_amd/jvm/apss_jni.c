@@ -23,7 +23,8 @@
 #define H(x) ((apss_handle *)(intptr_t)(x))
 
 JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cls, jint dim, jdouble theta,
-                                                          jdouble indexThreshold, jint flags, jint device, jint headTerms) {
+                                                          jdouble indexThreshold, jint flags, jint device, jint headTerms,
+                                                          jint topK) {
   (void)env; (void)cls;
   apss_config c = {0};
   c.struct_size = (int32_t)sizeof(c);
@@ -34,7 +35,12 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cl
   c.device_id = device;
   c.head_terms = headTerms;
   apss_handle *h = 0;
-  return apss_create(&c, &h) == APSS_OK ? (jlong)(intptr_t)h : 0;
+  if (apss_create(&c, &h) != APSS_OK) return 0;
+  if (apss_set_top_k(h, topK) != APSS_OK) { /* refused: as a failed create (the text stays readable through lastError(0)) */
+    apss_destroy(h);
+    return 0;
+  }
+  return (jlong)(intptr_t)h;
 }
 
 JNIEXPORT void JNICALL Java_cpslab_gpu_NativeApss_destroy(JNIEnv *env, jclass cls, jlong h) {
@@ -155,7 +161,7 @@ JNIEXPORT jint JNICALL Java_cpslab_gpu_NativeApss_fetch(JNIEnv *env, jclass cls,
  * library sees the APSS_GROUP_* flags of the low 16 bits and n / D term ranges x D row ranges (apss_group_create_grid). */
 JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_createGroup(JNIEnv *env, jclass cls, jint dim, jdouble theta,
                                                                jdouble indexThreshold, jint flags, jintArray devices,
-                                                               jint headTerms, jint groupFlags) {
+                                                               jint headTerms, jint groupFlags, jint topK) {
   (void)cls;
   const jsize n = (*env)->GetArrayLength(env, devices);
   if (n < 1 || n > APSS_GROUP_MAX_MEMBERS) return 0;
@@ -172,9 +178,14 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_createGroup(JNIEnv *env, jcla
   apss_group *g = 0;
   const int32_t rowRanges = (groupFlags >> 16) & 0xff;
   const uint32_t gflags = (uint32_t)groupFlags & 0xffffu;
-  if (rowRanges <= 1) return apss_group_create(&c, n, (const int32_t *)dev, gflags, &g) == APSS_OK ? (jlong)(intptr_t)g : 0;
-  if (n % rowRanges) return 0;
-  return apss_group_create_grid(&c, n / rowRanges, rowRanges, (const int32_t *)dev, gflags, &g) == APSS_OK ? (jlong)(intptr_t)g : 0;
+  if (rowRanges > 1 && n % rowRanges) return 0;
+  if (apss_group_create_grid(&c, rowRanges <= 1 ? n : n / rowRanges, rowRanges <= 1 ? 1 : rowRanges, (const int32_t *)dev, gflags, &g) != APSS_OK)
+    return 0;
+  if (apss_group_set_top_k(g, topK) != APSS_OK) { /* refused (a grid with topK > 0, k out of range): as a failed create */
+    apss_group_destroy(g);
+    return 0;
+  }
+  return (jlong)(intptr_t)g;
 }
 
 JNIEXPORT void JNICALL Java_cpslab_gpu_NativeApss_destroyGroup(JNIEnv *env, jclass cls, jlong g) {

@@ -174,7 +174,7 @@ int32_t apss_insert_and_query(apss_handle *h, int64_t n, const int64_t *rowptr, 
 /* query every stored vector against the whole index (single-batch self-join, the benchmark driver) */
 int32_t apss_self_join(apss_handle *h, int64_t *n_results);
 
-/* results of the last query-type call: (query ext id, candidate ext id, score); order unspecified */
+/* results of the last query-type call: (query ext id, candidate ext id, score); order unspecified (apss_set_top_k specifies one) */
 int32_t apss_result_count(const apss_handle *h, int64_t *n_results);
 int32_t apss_fetch_results(apss_handle *h, int64_t offset, int64_t count, int64_t *out_q, int64_t *out_c,
                            float *out_score);
@@ -252,6 +252,36 @@ int32_t apss_get_store_dev(apss_handle *h, const int64_t **d_rowptr, const int32
  * takes its sub-norms and dense-head rows from the whole rows it is handed */
 int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_indices,
                                const float *d_values, const int64_t *d_ext_ids);
+
+/* ---- per-query top-k ----
+ * k = 0 (the default): off -- every query-type call returns every pair with score >= theta, in no specified order.
+ * k in 1 .. APSS_TOP_K_MAX: the final list of every query-type call made afterwards (apss_query[_dev], apss_insert_and_query[_dev],
+ * apss_self_join) holds, for each query row of the batch, at most k of that row's pairs >= theta -- the first k in the order
+ *   1. fp32 score descending, as the device reports it (-0.0f counts as +0.0f and is reported as +0.0f);
+ *   2. candidate external id ascending;
+ *   3. candidate slot ascending (two stored rows may carry the same external id)
+ * -- and its order is specified: grouped by query row ascending, in rank order inside a row.  Everything that reads the
+ * results of the last call (n_results, apss_result_count, apss_fetch_results, apss_results_dev, apss_results_copy_dev,
+ * apss_stats.result_pairs) sees the selected list; apss_topk_get reports the count before the cut.  The setting may be changed
+ * at any time (it takes effect at the next query-type call, leaves the last call's results alone and survives apss_clear).
+ * The cut is one device pass over the call's final list on the handle's stream (k_topk_*: count, scan, scatter, select).
+ * APSS_E_INVALID: k < 0 or k > APSS_TOP_K_MAX.  APSS_E_UNSUPPORTED: k > 0 on a term shard (its candidates carry partial scores;
+ * apss_group_set_top_k cuts behind the group's exchange). */
+#define APSS_TOP_K_MAX 1024
+typedef struct apss_topk_info {
+  int32_t struct_size;       /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t k;                 /* the setting the last query-type call ran with (0: off) */
+  int64_t pairs_over_theta;  /* pairs >= theta of the last call before the cut (== result_pairs when k == 0) */
+  int64_t kept;              /* pairs in the final list */
+  int64_t queries_cut;       /* query rows that had more than k pairs (0 when k == 0) */
+  int64_t longest_segment;   /* most pairs >= theta any one query row had (0 when k == 0: nothing counts them) */
+  double select_ms;          /* device time of the k_topk_* kernels, HIP events (0 when k == 0) */
+  int32_t select_launches;   /* k_topk_* launches of the last call (0 when k == 0) */
+  int32_t reserved0;
+} apss_topk_info;
+int32_t apss_set_top_k(apss_handle *h, int32_t k);
+int32_t apss_topk_get(apss_handle *h, apss_topk_info *out);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
@@ -441,6 +471,14 @@ int32_t apss_group_fetch_results(apss_group *g, int64_t offset, int64_t count, i
 int32_t apss_group_stats_get(apss_group *g, apss_group_stats *out);
 /* the shard handle's own statistics (out->struct_size set by the caller, as apss_stats_get) */
 int32_t apss_group_member_stats(apss_group *g, int32_t member, apss_stats *out);
+
+/* Per-query top-k for the group's query-type calls (semantics: apss_set_top_k).  One member without an exchange: the member's
+ * handle cuts its own final list.  T x 1 with an exchange: the cut runs on member 0's device behind the `>= theta` compaction
+ * of step 4 (the members are term shards and never get a k).  GRIDS with D > 1 row ranges keep (ext, ext, score) triples per
+ * row range on different devices: k > 0 answers APSS_E_UNSUPPORTED there and the group keeps working with k = 0.  May be called
+ * before the first insert (the members' handles do not exist yet: the setting is applied when they are created). */
+int32_t apss_group_set_top_k(apss_group *g, int32_t k);
+int32_t apss_group_topk_get(apss_group *g, apss_topk_info *out);
 
 #ifdef __cplusplus
 }

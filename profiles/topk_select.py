@@ -1,0 +1,75 @@
+"""Per-query top-k (apss_set_top_k): device time of the pass beside the join it follows, per call.
+
+Shapes: the reference's server template at similarityThreshold = 0 (N = 60,000, dim 1024, nnz 40: profiles/r04_theta0.json) and
+BASELINE config 2's shape at theta = 0.5, both with k = 10.  Each shape: one handle, a warm-up self-join per setting (sizes the
+buffers), then `--reps` self-joins alternating k = 0 and k = 10.  Times are HIP events inside the library (apss_stats.probe_ms /
+rescore_ms, apss_topk_info.select_ms).  Beside them the floors the pass cannot beat: one read of the list (12 B x
+pairs_over_theta) at the 6.29 TB/s copy peak, and the bytes this design moves --
+  count    4 B per pair (query row)
+  scatter  12 B read + 8 B written per pair
+  select   a segment of <= 1024 pairs: 8 B read + an 8-B external id gathered per pair; a longer one: 4 B per pair and digit pass
+           (four score digits at most, fewer when a digit already separates the k-th pair from the next) + 4 B for the collect
+  output   12 B per kept pair
+-- computed from the shapes (every segment taken as long when the mean segment is above 1024, four digit passes: an upper
+estimate for data without ties at the cut).
+Usage: python profiles/topk_select.py [--reps 3] [--shape template|c2|all] > profiles/topk_select.json"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "all-pairs-similarity_amd"))
+from apss import synth  # noqa: E402
+from apss.engine import ApssIndex  # noqa: E402
+
+COPY_PEAK = 6.29e12  # B/s, plain device copy on the MI355X
+SHAPES = {"template": ("template_dim1024_theta0", 60_000, 1024, 40, 0.0, 0.0), "c2": ("c2_shape_theta0.5", 30_000, 10_000, 50, 1.0, 0.5)}
+
+
+def design_bytes(pairs, kept, nq, passes=4):
+    mean = pairs / max(nq, 1)
+    select = pairs * (4 * (passes + 1)) if mean > 1024 else pairs * 16
+    return pairs * 4 + pairs * 20 + select + kept * 12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--shape", default="all")
+    a = ap.parse_args()
+    out = {}
+    for key, (name, n, dim, nnz, zipf, theta) in SHAPES.items():
+        if a.shape not in ("all", key):
+            continue
+        rp, idx, val = synth.make_vectors(n, dim, nnz, zipf, seed=11)
+        row = {"n": n, "dim": dim, "nnz": nnz, "zipf_s": zipf, "theta": theta, "k": a.k, "calls": []}
+        with ApssIndex(dim, theta) as ix:
+            ix.insert(np.arange(n), rp, idx, val)
+            ix.self_join(fetch=False)  # warm-up, k = 0
+            row["hbm_bytes_k0"] = ix.stats()["hbm_bytes"]
+            ix.set_top_k(a.k)
+            ix.self_join(fetch=False)  # warm-up, k > 0: sizes the pass's buffers
+            row["hbm_bytes_k"] = ix.stats()["hbm_bytes"]
+            for rep in range(a.reps):
+                for k in (0, a.k):
+                    ix.set_top_k(k)
+                    ix.self_join(fetch=False)
+                    st, ti = ix.stats(), ix.topk_info()
+                    call = {"k": k, "probe_ms": st["probe_ms"], "rescore_ms": st["rescore_ms"], "select_ms": ti["select_ms"],
+                            "pairs_over_theta": ti["pairs_over_theta"], "kept": ti["kept"], "queries_cut": ti["queries_cut"],
+                            "longest_segment": ti["longest_segment"], "select_launches": ti["select_launches"]}
+                    if k:
+                        call["floor_read_list_ms"] = 12.0 * ti["pairs_over_theta"] / COPY_PEAK * 1e3
+                        moved = design_bytes(ti["pairs_over_theta"], ti["kept"], n)
+                        call["design_bytes"] = moved
+                        call["floor_design_bytes_ms"] = moved / COPY_PEAK * 1e3
+                    row["calls"].append(call)
+        out[name] = row
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()
