@@ -12,7 +12,9 @@
 //  * FIXED ROLES.  Waves 0 .. F-1 STAGE every round and never add; waves F .. NW-1 ADD every round and never stage;
 //    each kind runs its own loop with the same two barriers per round.  F = ceil(longest query / (64 / G)), G = 1, 2 or 4
 //    staging lanes per term.  A staging wave scans the round's chunk counts once, two rounds ahead, and deals the chunks
-//    out EVENLY over the A = NW - F adding waves: chunk j -> adding wave j % A, strip slot j / A.
+//    out over the A = NW - F adding waves in WHOLE WINDOW STEPS: chunk j -> step j / 8A, and inside the step adding wave
+//    (j % 8A) / 8, lane group j % 8.  A round of `tot` chunks costs ceil(tot / 8) wave-steps, not A ceil(tot / 8A): the waves
+//    behind the last chunk are one step short and skip it.
 //  * NOTHING IS READ AFTER THE FIRST BARRIER.  Everything a round needs to know about itself is a fact of its staging
 //    (chunks per wave, long segments, whether the window overflows -> whole-tile clear): an adding wave reads it one round
 //    ahead, in the same LDS round trip as its next strip and the current adds.  A crossing is reported by the wave that
@@ -20,7 +22,10 @@
 //    So an adding wave's round is: strip read + adds (one LDS round trip) -> next loads, tests -> barrier -> clears -> barrier.
 //  * NO TRIPS THROUGH THE SCALAR UNIT ON THE HOT PATH.  Idle lanes add to spare LDS words / write spare strip entries
 //    (selects on the address, no exec masks); first touches and crossings are counted per lane; one branch per round takes
-//    everything unusual.  Loaded values are used a round after their load, by the next stage.
+//    everything unusual.  Loaded values are used a round after their load, by the next stage.  (The one deliberate
+//    exception: the round's two fact words go to the scalar unit as loaded, two v_readfirstlane per round, and this wave's
+//    chunks and steps are worked out there -- used a round later, so nothing waits for the hand-over; it took 18 vector
+//    instructions off the round for 25 scalar ones, see strip_loads.)
 //  * FEW VECTOR INSTRUCTIONS PER POSTING SLOT (LEAN: every instantiation with non-negative weights; the kernel is bound by the
 //    vector instructions it issues).  A batch's crossings are found by the MAXIMUM of old + product over its postings, one
 //    compare per batch; an idle lane's spare word is kept small and non-zero (set to 1 in every round's clear phase), so its
@@ -90,7 +95,9 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   const int F = a.flat_waves;   // waves that stage a round
   const int A = NW - F;         // waves that add a round (those not staging in it)
   const int CAP = A * SLOTS;    // chunks per round
-  const float rcpA = 1.0f / (float)A;
+  const uint32_t A8 = (uint32_t)A * (uint32_t)GPW;  // chunks of one window step of the whole round: 8 per adding wave
+  const float rcpA8 = 1.0f / (float)A8;
+  const uint32_t magicA8 = 0xffffffffu / A8 + 1u;  // x / 8A = umulhi(x, magic) for x < 2^16: magic x 8A - 2^32 is in [0, 8A]
   // lanes per term in a staging wave (1, 2 or 4): a staging lane writes the chunks k = sub, sub + G, ... of its term, so a
   // term of <= 2 G chunks costs every lane two strip writes and no loop (a wave issues its instructions one after another
   // whatever the number of live lanes: the staging wave's instruction count is on the round's critical path)
@@ -143,13 +150,15 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   constexpr uint32_t kStale = 0x80000000u, kSwept = 0x40000000u;
   constexpr uint32_t kRare = 0x80000000u;  // WaveWork::info: the round needs more than the register window (see strip_loads)
   constexpr uint32_t kCountMask = 0xffffu;  // WaveWork::info bits 16..19: window steps that hold chunks of this wave
-  // SKIP: a wave skips the window steps behind its last chunk (adds, tests, clears).  A wave otherwise issues all U steps
-  // whether or not their slots hold postings, and the LDS pipeline pays for each; the windows of shards and of the sparse
-  // regime are sized for the upper end of a varying term count.  Measured: C5's shape 244.5 -> 218.5 ms; where nearly every
-  // step is needed the branches cost more than they save (C3, plain 512-thread handle: 101.1 -> 102.4 ms): not there.
-  constexpr bool SKIP = BLOCK > 512 || SHARD;
-  // (the 1024-thread kernel only ever skips its LAST step: with every step behind a branch C5's shape measured 245 vs 219 ms)
-  constexpr int kFirstSkippable = BLOCK > 512 ? U - 1 : 0;
+  // A wave skips the window steps behind its last chunk (adds, tests, clears).  A wave otherwise issues all U steps whether
+  // or not their slots hold postings, and the LDS pipeline pays for each; the windows of shards and of the sparse regime are
+  // sized for the upper end of a varying term count (C5's shape: 244.5 -> 218.5 ms), and chunks are dealt in whole steps (see
+  // put()), so the waves behind a round's last chunk are a step short of the others in every round.
+  // The 1024-thread kernel and the plain handles only ever skip their LAST step (with every step behind a branch C5's shape
+  // measured 245 vs 219 ms, C3 101.1 vs 102.4 ms); shard-rule launches any.
+  // (Tried: logical wave = (rank + round) mod A, so that the waves of a round's extra step are not always those of the same
+  // SIMDs.  C3: 49.3 vs 49.1 ms with it -- profiles/even_steps.md; not kept.)
+  constexpr int kFirstSkippable = BLOCK > 512 || !SHARD ? U - 1 : 0;
 
   for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
   if (tid < kWave) acc[CBMAX / APW + tid] = 1u;  // the spare words (LEAN: never zero in their low accumulator)
@@ -228,11 +237,14 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
     const uint32_t wbits = __float_as_uint(cxs * g.w);
     uint2 *const st = strips + ring * (NS * SSZ);
     auto put = [&](const uint32_t k) {
-      // chunk j of the round -> adding wave j % A, slot j / A ((j + 0.5) / A is at least 1 / 2A away from an integer:
-      // the float quotient truncates exactly for j < 2^16)
+      // chunk j of the round -> window step u = j / 8A; inside the step r = j % 8A: adding wave r / 8, lane group r % 8
+      // ((j + 0.5) / 8A is at least 1 / 16A away from an integer: the float quotient truncates exactly for j < 2^16).
+      // A function of j alone -- the staging lanes do not know the round's total -- and a wave's chunks are a prefix of
+      // its slot order (slot = 8 u + group), as strip_loads, the invalidation and the rare path expect.
       const uint32_t j = min(j0 + k, (uint32_t)CAP - 1u);  // (a round that does not fit is flagged below; keep the store inside the strips)
-      const uint32_t sl = (uint32_t)(((float)j + 0.5f) * rcpA);
-      uint2 *const dst = k < nch ? st + (j - sl * (uint32_t)A) * SSZ + (sl & 7u) * GS + (sl >> 3) : spare_item;
+      const uint32_t u = (uint32_t)(((float)j + 0.5f) * rcpA8);
+      const uint32_t r = j - u * A8;
+      uint2 *const dst = k < nch ? st + (r >> 3) * SSZ + (r & 7u) * GS + u : spare_item;
       *dst = make_uint2((g.s + k * CH) * 4u, wbits);
     };
     // chunks per term written without the loop: 8 with four lanes per term (two writes each), 6 with two, 3 with one
@@ -282,19 +294,25 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
       (ln < WIN ? own : spare_item)->x = kStale;
     }
   };
-  // second half: every LPC lanes take one chunk of the strip and start its posting load.  VALU only -- the one value the
-  // next round branches on (is it more than a register window?) goes to the scalar unit here, a round before its use.
+  // second half: every LPC lanes take one chunk of the strip and start its posting load.  What the next round branches on
+  // (its steps; is it more than a register window?) is worked out on the scalar unit here, a round before its use.
   auto strip_loads = [&](WaveWork &f, StripRead &sr, const int rank) {
-    const uint32_t tot = (sr.fc.y & 1u) ? 0u : sr.fc.x;  // (a round flagged for the direct sweep has no chunks)
-    // chunks j < tot with j % A == rank: ceil((tot - rank) / A)
-    const uint32_t mine = (int)tot > rank ? (uint32_t)(((float)((int)tot - rank + A - 1) + 0.5f) * rcpA) : 0u;
-    const bool rare = sr.fc.y != 0u || tot > (uint32_t)(A * WIN);
-    const uint32_t steps = min((mine + (uint32_t)GPW - 1u) / (uint32_t)GPW, (uint32_t)U);
-    f.info = (uint32_t)__builtin_amdgcn_readfirstlane((int)(mine | (rare ? kRare : 0u) | (steps << 16)));
+    // the facts are the same in every lane: they go to the scalar unit as they are, and what this wave makes of them costs
+    // the vector unit nothing (C3, with the counts below on the VALU: 49.6 vs 49.1 ms)
+    const uint32_t fx = (uint32_t)__builtin_amdgcn_readfirstlane((int)sr.fc.x), fy = (uint32_t)__builtin_amdgcn_readfirstlane((int)sr.fc.y);
+    const uint32_t tot = (fy & 1u) ? 0u : fx;  // (a round flagged for the direct sweep has no chunks)
+    // the round's `full` whole steps hold 8 chunks of every wave; the `rem` chunks of the step behind them go to the waves
+    // of rank 0, 1, .. eight at a time: the waves behind the last of them are a step short
+    const uint32_t full = __umulhi(tot, magicA8);
+    const int rem = (int)(tot - full * A8) - GPW * rank;  // ... from this wave's place on
+    const uint32_t mine = (uint32_t)GPW * full + (uint32_t)min(max(rem, 0), GPW);
+    const bool rare = fy != 0u || tot > (uint32_t)(A * WIN);
+    const uint32_t steps = min(full + (rem > 0 ? 1u : 0u), (uint32_t)U);
+    f.info = mine | (rare ? kRare : 0u) | (steps << 16);
     f.flags = sr.fc.y;
 #pragma unroll
     for (int u = 0; u < U; ++u) asm volatile("" : "+v"(sr.it[u].x), "+v"(sr.it[u].y));
-    const uint32_t lane_off = lo * 8u + (LEAN && (sr.fc.y & 1u) ? kSwept : 0u);
+    const uint32_t lane_off = lo * 8u + (LEAN && (fy & 1u) ? kSwept : 0u);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       // a posting word of zero is no posting (segments are zero-padded to whole chunks; out-of-range reads return zero);
@@ -425,13 +443,13 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
           if (thr1 - oy < py) report_lane(slot_of(y), oy + py);
         }
       };
-      const int n_steps = SKIP ? (int)((w0.info >> 16) & 0xfu) : U;  // (scalar: a branch on it costs no trip from the VALU)
-      if (LEAN) n_seen -= 2u * (uint32_t)(SKIP ? max(n_steps, kFirstSkippable) : U);  // the slots the batches below test
+      const int n_steps = (int)((w0.info >> 16) & 0xfu);  // (scalar: a branch on it costs no trip from the VALU)
+      if (LEAN) n_seen -= 2u * (uint32_t)max(n_steps, kFirstSkippable);  // the slots the batches below test
       auto issue_batch = [&](const int u0, uint32_t (&p0)[BATCH], uint32_t (&p1)[BATCH], uint32_t (&o0)[BATCH], uint32_t (&o1)[BATCH]) {
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) {
           const int u = u0 + j;
-          if (SKIP && u >= kFirstSkippable && u >= n_steps) break;  // (one forward exit: the steps behind this wave's last chunk)
+          if (u >= kFirstSkippable && u >= n_steps) break;  // (one forward exit: the steps behind this wave's last chunk)
           if (u < U) {
             p0[j] = prod(w0.pc[u].x, w0.wq[u]);
             p1[j] = prod(w0.pc[u].y, w0.wq[u]);
@@ -450,7 +468,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
 #pragma unroll
           for (int j = 0; j < BATCH; ++j) {
             const int u = u0 + j;
-            if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+            if (u >= kFirstSkippable && u >= n_steps) break;
             if (u < U) {
               o0[j] = half_of(o0[j], w0.pc[u].x);
               o1[j] = half_of(o1[j], w0.pc[u].y);
@@ -466,7 +484,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
 #pragma unroll
             for (int j = 0; j < BATCH; ++j) {
               const int u = u0 + j;
-              if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+              if (u >= kFirstSkippable && u >= n_steps) break;
               if (u < U) {
                 const uint32_t a0 = w0.pc[u].x ? o0[j] : thr1 + 1u, a1 = w0.pc[u].y ? o1[j] : thr1 + 1u;  // (an idle lane never crosses)
                 report(thr1 - a0 < p0[j], slot_of(w0.pc[u].x), a0 + p0[j]);
@@ -482,7 +500,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
 #pragma unroll
         for (int j = 0; j < BATCH; ++j) {
           const int u = u0 + j;
-          if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+          if (u >= kFirstSkippable && u >= n_steps) break;
           if (u < U) {
             o0[j] = w0.pc[u].x ? half_of(o0[j], w0.pc[u].x) : thr1 + 1u;
             o1[j] = w0.pc[u].y ? half_of(o1[j], w0.pc[u].y) : thr1 + 1u;
@@ -494,7 +512,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
 #pragma unroll
           for (int j = 0; j < BATCH; ++j) {
             const int u = u0 + j;
-            if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+            if (u >= kFirstSkippable && u >= n_steps) break;
             if (u < U) {
               report(thr1 - o0[j] < p0[j], slot_of(w0.pc[u].x), o0[j] + p0[j]);
               report(thr1 - o1[j] < p1[j], slot_of(w0.pc[u].y), o1[j] + p1[j]);
@@ -570,7 +588,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
         unsigned short *acc16w = reinterpret_cast<unsigned short *>(acc);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          if (SKIP && u >= kFirstSkippable && u >= n_steps) break;
+          if (u >= kFirstSkippable && u >= n_steps) break;
           // unconditional: an idle lane (zero word) clears slot 0, which is zero at the end of a query either way
           if (WIDE) {
             smem_raw[w0.pc[u].x >> 15] = 0;
