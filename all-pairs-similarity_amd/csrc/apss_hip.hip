@@ -75,6 +75,7 @@ struct DebugCfg {
   bool no_merge_prune = false; // no_merge_prune merged rounds hand every expanded pair to the exchange (no exact shard-rule test behind k_expand_merged)
   int merge_u = 0;             // merge_u=U      ... as long as the merged round fits a window of U steps (default 7)
   int merge_single = 0;        // merge_single=U ... and a single row's round takes a window of at most U steps (default 4)
+  bool no_fused_ingest = false; // no_fused_ingest a plain batch is ingested by k_ingest_count + k_ingest_write too (never the one-pass k_ingest_plain)
 };
 
 DebugCfg parse_debug_env() {
@@ -130,6 +131,7 @@ DebugCfg parse_debug_env() {
     else if (key == "merge_u") d.merge_u = (int)val;
     else if (key == "no_merge_prune") d.no_merge_prune = val != 0;
     else if (key == "merge_single") d.merge_single = (int)val;
+    else if (key == "no_fused_ingest") d.no_fused_ingest = val != 0;
     else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
@@ -209,6 +211,19 @@ struct apss_handle {
   DevBuf<float> bk_val;
   DevBuf<uint32_t> run_cut;           // run-reading LDS build: per-row range cuts of the rows being built (k_row_cuts)
   DevBuf<uint2> run_ent;              //   ... and the entries partitioned by (tile, sub-range) for its two-pass scatter
+  // the same cuts as k_ingest_plain leaves them while it stores a plain batch: [store row][cut_ranges + 1], valid for the store
+  // rows [cut_lo, cut_hi) of a rendering with cut_cb rows per tile and ranges of cut_rt terms (build_tiles takes them when they
+  // cover the rows it builds, and computes its own otherwise)
+  // (indexed by ABSOLUTE store row on purpose: build_tiles hands k_tile_runs `ing_cut + r0 * (ranges + 1)` whatever cut_lo is,
+  // and an appended batch extends the table in place; a table that starts over at row cut_lo > 0 leaves the rows below unused --
+  // (ranges + 1) x 4 B per store row, 32 MB at C3 -- and like every buffer of the handle it only grows)
+  DevBuf<uint32_t> ing_cut;
+  int64_t cut_lo = 0, cut_hi = 0;
+  int32_t cut_cb = 0, cut_rt = 0, cut_ranges = 0;
+  // ... and the sampled document frequencies of a batch that went into an empty store: valid for a head policy that looks at
+  // exactly the store rows [0, df_rows) with this stride (choose_head)
+  std::vector<uint32_t> df_host;
+  int64_t df_rows = -1, df_stride = 0;
   DevBuf<uint2> app_seg;             // append build: the last tile's segment table and postings before the append
   DevBuf<char> app_post;
   DevBuf<int32_t> vq_first, vrow_q;  // virtual-row table of the last query batch (queries of > 512 terms)
@@ -367,6 +382,126 @@ int32_t head_setup_rendering(apss_handle *h);
 int32_t head_fit_scale(apss_handle *h, double norm2, unsigned char *W, int64_t packed_bytes);
 inline void head_pack_rendering(const apss_handle *h, HeadPackArgs &p);
 
+bool ingest_wants_cuts(const apss_handle *h, int64_t dst_row0, int64_t n, int64_t nnz, int32_t *cb, int32_t *rt, int32_t *n_ranges);
+bool head_policy_due(const apss_handle *h, int64_t n_rows);
+
+// what the flag words of an ingest kernel say about the batch: the error of a rejected batch (nothing of the handle has
+// changed by then), or the batch's summaries folded into the handle's
+int32_t take_ingest_flags(apss_handle *h, const unsigned int *flags_host, bool to_store) {
+  if (flags_host[0] & 1u)
+    return fail(h, APSS_E_INVALID, "malformed vector: indices must be strictly increasing and in [0, dim) "
+                                   "(SparseVector.scala:75; vectorDim mismatch is the require of CommonUtils.scala:99)");
+  if (flags_host[0] & 2u) return fail(h, APSS_E_INVALID, "non-finite value in a vector");
+  if (to_store) h->nonneg = h->nonneg && !(flags_host[0] & 4u);
+  else h->q_nonneg = !(flags_host[0] & 4u);
+  float norm2;
+  std::memcpy(&norm2, &flags_host[2], sizeof(float));
+  if (to_store) {
+    h->store_max_nnz = std::max<int64_t>(h->store_max_nnz, flags_host[1]);
+    h->store_max_norm2 = std::max(h->store_max_norm2, norm2);
+    h->store_nonempty += flags_host[3];
+    h->last_batch_nonempty = flags_host[3];
+  } else {
+    h->q_max_nnz = flags_host[1];
+    h->q_max_norm2 = norm2;
+  }
+  return APSS_OK;
+}
+
+// A PLAIN batch (no term range, normalise, prune or admission) in one pass, k_ingest_plain: every row and entry is kept, so the
+// destination is sized before the launch and the flag word is read once, behind it.  A store batch also leaves the range cuts
+// of its rows when the index build is expected to read runs, and the df sample when it is the store's first rows and the head
+// policy will look at them.
+int32_t ingest_plain(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_idx, const float *d_val,
+                     const int64_t *d_ext, bool to_store, int64_t *n_out, int64_t *nnz_out) {
+  APSS_TRY(ensure(h, h->flagword, 4));
+  const int64_t dst_row0 = to_store ? h->n_rows : 0, dst_nnz0 = to_store ? h->nnz : 0;
+  DevBuf<int64_t> &o_rowptr = to_store ? h->rowptr : h->q_rowptr;
+  DevBuf<int64_t> &o_ext = to_store ? h->ext : h->q_ext;
+  DevBuf<int32_t> &o_idx = to_store ? h->idx : h->q_idx;
+  DevBuf<float> &o_val = to_store ? h->val : h->q_val;
+  APSS_TRY(ensure(h, o_rowptr, (size_t)(dst_row0 + n + 1), (size_t)(to_store ? dst_row0 + 1 : 0)));
+  APSS_TRY(ensure(h, o_ext, (size_t)(dst_row0 + n), (size_t)dst_row0));
+  APSS_TRY(ensure(h, o_idx, (size_t)(dst_nnz0 + nnz), (size_t)dst_nnz0));
+  APSS_TRY(ensure(h, o_val, (size_t)(dst_nnz0 + nnz), (size_t)dst_nnz0));
+  if (to_store) APSS_TRY(ensure(h, h->erow, (size_t)(dst_nnz0 + nnz), (size_t)dst_nnz0));
+  HIPCHK(h, hipMemsetAsync(h->flagword.p, 0, 4 * sizeof(unsigned int), h->stream));
+  if (dst_row0 == 0) HIPCHK(h, hipMemsetAsync(o_rowptr.p, 0, sizeof(int64_t), h->stream));
+
+  IngestPlainArgs p{};
+  IngestArgs &a = p.w.in;
+  a.n = n;
+  a.nnz = nnz;
+  a.rowptr = d_rowptr;
+  a.idx = d_idx;
+  a.val = d_val;
+  a.dim = h->cfg.dim;
+  a.flags_out = h->flagword.p;
+  p.w.dst_row0 = dst_row0;
+  p.w.dst_nnz0 = dst_nnz0;
+  p.w.o_rowptr = o_rowptr.p;
+  p.w.o_idx = o_idx.p;
+  p.w.o_val = o_val.p;
+  p.w.o_ext = o_ext.p;
+  p.w.o_erow = to_store ? h->erow.p : nullptr;
+  p.w.ext = d_ext;
+  // range cuts: appended to the table when it ends where this batch starts, in the same form; otherwise the table starts over
+  int32_t cut_cb = 0, cut_rt = 0, cut_ranges = 0;
+  const bool cuts = to_store && ingest_wants_cuts(h, dst_row0, n, nnz, &cut_cb, &cut_rt, &cut_ranges);
+  bool cuts_extend = false;
+  if (cuts) {
+    cuts_extend = h->cut_hi > h->cut_lo && h->cut_hi == dst_row0 && h->cut_cb == cut_cb && h->cut_rt == cut_rt && h->cut_ranges == cut_ranges;
+    if (!cuts_extend) h->cut_lo = h->cut_hi = 0;  // (the rows written below overwrite it)
+    const size_t cw = (size_t)cut_ranges + 1;
+    APSS_TRY(ensure(h, h->ing_cut, (size_t)(dst_row0 + n) * cw, cuts_extend ? (size_t)dst_row0 * cw : 0));
+    p.cut = h->ing_cut.p;
+    p.n_ranges = cut_ranges;
+    p.range_terms = cut_rt;
+    p.cb = cut_cb;
+  }
+  // df sample: the head policy would look at exactly this batch (choose_head: rows [0, n), the same stride)
+  const bool sample = to_store && dst_row0 == 0 && head_policy_due(h, n);
+  const int32_t dim = h->cfg.dim;
+  if (to_store) h->df_rows = -1;
+  if (sample) {
+    APSS_TRY(ensure(h, h->df, (size_t)dim));
+    HIPCHK(h, hipMemsetAsync(h->df.p, 0, (size_t)dim * sizeof(uint32_t), h->stream));
+    p.df = h->df.p;
+    p.df_stride = std::max<int64_t>(1, n / 65536);
+    h->df_host.resize((size_t)dim);
+  }
+  const int threads = 256;
+  const int64_t blocks = ceil_div(n * kGroup, threads);
+  // (the workgroups loop over their rows: few workgroups = few same-address atomics on the batch summaries)
+  hipLaunchKernelGGL(k_ingest_plain, dim3((unsigned)std::min<int64_t>(blocks, 4096)), dim3(threads), 0, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  unsigned int flags_stack[4] = {0, 0, 0, 0};
+  unsigned int *flags_host = h->pin ? reinterpret_cast<unsigned int *>(h->pin + kPinBytes) : flags_stack;
+  HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));  // (pinned or stack)
+  if (sample) HIPCHK(h, hipMemcpyAsync(h->df_host.data(), h->df.p, (size_t)dim * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->dbgcfg.diag)
+    fprintf(stderr, "[apss diag] ingest fused: %lld %s rows at %lld, cuts %s, df sample %s\n", (long long)n, to_store ? "store" : "query",
+            (long long)dst_row0, cuts ? (cuts_extend ? "appended" : "written") : "none", sample ? "taken" : "none");
+  // a rejected batch commits nothing: the store's extent, its summaries and the cut table's are what they were, and what the
+  // kernel wrote beyond them is dead
+  APSS_TRY(take_ingest_flags(h, flags_host, to_store));
+  if (cuts) {
+    if (!cuts_extend) h->cut_lo = dst_row0;
+    h->cut_hi = dst_row0 + n;
+    h->cut_cb = cut_cb;
+    h->cut_rt = cut_rt;
+    h->cut_ranges = cut_ranges;
+  }
+  if (sample) {
+    h->df_rows = n;
+    h->df_stride = p.df_stride;
+  }
+  *n_out = n;
+  *nnz_out = nnz;
+  return APSS_OK;
+}
+
 int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_idx,
                const float *d_val, const int64_t *d_ext, bool to_store, int64_t *n_out, int64_t *nnz_out) {
   *n_out = 0;
@@ -376,6 +511,10 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   // would change them (a pruned row re-normalised) or drop them (admission on the pruned sum)
   const uint32_t in_flags = h->stored_rows ? h->cfg.flags & ~(APSS_FLAG_VALUE_PRUNE | APSS_FLAG_ADMISSION | APSS_FLAG_NORMALIZE) : h->cfg.flags;
   const bool transform = h->sharded || (in_flags & (APSS_FLAG_VALUE_PRUNE | APSS_FLAG_ADMISSION | APSS_FLAG_NORMALIZE));
+  if (!transform && !h->dbgcfg.no_fused_ingest) return ingest_plain(h, n, nnz, d_rowptr, d_idx, d_val, d_ext, to_store, n_out, nnz_out);
+  if (h->dbgcfg.diag)
+    fprintf(stderr, "[apss diag] ingest unfused: %lld %s rows at %lld (%s)\n", (long long)n, to_store ? "store" : "query",
+            (long long)(to_store ? h->n_rows : 0), transform ? "transform" : "no_fused_ingest");
   APSS_TRY(ensure(h, h->s_keep, (size_t)n + 1));
   APSS_TRY(ensure(h, h->s_cnt, (size_t)n + 1));
   APSS_TRY(ensure(h, h->s_inv, (size_t)n));
@@ -425,23 +564,7 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   }
   HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));  // (pinned or stack)
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (flags_host[0] & 1u)
-    return fail(h, APSS_E_INVALID, "malformed vector: indices must be strictly increasing and in [0, dim) "
-                                   "(SparseVector.scala:75; vectorDim mismatch is the require of CommonUtils.scala:99)");
-  if (flags_host[0] & 2u) return fail(h, APSS_E_INVALID, "non-finite value in a vector");
-  if (to_store) h->nonneg = h->nonneg && !(flags_host[0] & 4u);
-  else h->q_nonneg = !(flags_host[0] & 4u);
-  float norm2;
-  std::memcpy(&norm2, &flags_host[2], sizeof(float));
-  if (to_store) {
-    h->store_max_nnz = std::max<int64_t>(h->store_max_nnz, flags_host[1]);
-    h->store_max_norm2 = std::max(h->store_max_norm2, norm2);
-    h->store_nonempty += flags_host[3];
-    h->last_batch_nonempty = flags_host[3];
-  } else {
-    h->q_max_nnz = flags_host[1];
-    h->q_max_norm2 = norm2;
-  }
+  APSS_TRY(take_ingest_flags(h, flags_host, to_store));
 
   DevBuf<int64_t> &o_rowptr = to_store ? h->rowptr : h->q_rowptr;
   DevBuf<int64_t> &o_ext = to_store ? h->ext : h->q_ext;
@@ -637,6 +760,47 @@ void launch_tile_runs(int lanes, dim3 grid, size_t lds, hipStream_t stream, cons
   else hipLaunchKernelGGL((k_tile_runs<SCATTER, 32>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
 }
 
+// Which kernels the build of tiles [tile0, n_tiles) of `cb` rows takes, and in which form: decided from the shape of what is built
+// -- `rows` rows of `build_nnz` entries, the longest of `max_nnz`.  build_tiles decides with it; ingest_plain asks it beforehand
+// whether the rows it stores will be read by runs (ingest_wants_cuts), so that the two cannot drift apart.
+struct BuildForm {
+  int32_t n_ranges, bucket_rt, run_rt;
+  bool bucket_build, lds_build, run_build;
+  double mean_run;
+};
+BuildForm build_form(const apss_handle *h, int64_t cb, int64_t tile0, int64_t n_tiles, int64_t rows, int64_t build_nnz, int64_t max_nnz) {
+  // small dims: counters and cursors of a (tile, term range) live in one workgroup's LDS (no global atomics)
+  int32_t n_ranges = (int32_t)ceil_div(h->cfg.dim, kBuildRange);
+  // (one workgroup per (tile, range): with fewer than ~48 of them -- a small batch, a rebuilt tail tile, a 1/8 candidate
+  // range -- the row-parallel global-atomic kernels are faster; APSS_BUILD_LDS / APSS_BUILD_ATOMIC force either)
+  // large dims (more than kBuildMaxRanges ranges: vectorDim = 2^20): a build from the first tile partitions the entries by
+  // term range first (k_bucket_pass), so that the LDS build's workgroups read their bucket instead of the whole tile
+  // (terms per range of a bucketed build, measured on C5's shape, build ms per step: 1024: 28.3, 2048: 23.9, 4096: 20.4, 8192: 15.6,
+  // 16384: 17.4 -- against 37.5 with the global-atomic kernels; narrow ranges multiply the workgroups' fixed work)
+  int32_t bucket_rt = h->dbgcfg.bucket_range > 0 ? h->dbgcfg.bucket_range : 8192;
+  while (ceil_div(h->cfg.dim, bucket_rt) > kBucketMaxRanges && bucket_rt < kBuildRange) bucket_rt *= 2;
+  const bool bucket_build = n_ranges > kBuildMaxRanges && ceil_div(h->cfg.dim, bucket_rt) <= kBucketMaxRanges && !h->dbgcfg.build_atomic &&
+                            !h->dbgcfg.no_bucket && tile0 == 0 && n_tiles * n_ranges >= 48 && build_nnz > 0 && build_nnz <= (1LL << 32) &&
+                            n_tiles * (int64_t)kBucketSlices < (1LL << 31);
+  if (bucket_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, bucket_rt);
+  const bool lds_build = bucket_build || (n_ranges <= kBuildMaxRanges && !h->dbgcfg.build_atomic &&
+                                          ((n_tiles - tile0) * n_ranges >= 48 || h->dbgcfg.build_lds));
+  // Run-reading LDS build (k_row_cuts + k_tile_runs): wherever the streaming LDS build would re-read the tile's entries -- two
+  // term ranges or more -- and the rows are long enough to be worth a cut table (kRunMinMeanRow).  With one range
+  // the streaming kernels read every entry exactly once, coalesced: nothing to save.  32-bit cut points: (longest row) x (rows
+  // per tile) < 2^31.
+  const double mean_row = rows > 0 ? (double)build_nnz / (double)rows : 0.0;
+  int32_t run_rt = h->dbgcfg.run_range > 0 ? std::min(h->dbgcfg.run_range, kBuildRange) : kRunRange;
+  const int64_t t_lo = h->cfg.term_lo, t_hi = h->cfg.term_hi;
+  const int64_t run_active = std::max<int64_t>(1, ceil_div(t_hi, run_rt) - t_lo / run_rt);  // ranges that hold terms of this handle
+  const double mean_run = mean_row / (double)run_active;
+  const bool run_build = lds_build && !bucket_build && !h->dbgcfg.build_stream && std::max<int64_t>(max_nnz, 1) * cb < (1LL << 31) &&
+                         ceil_div(h->cfg.dim, run_rt) <= 64 &&
+                         (h->dbgcfg.build_runs || (n_ranges >= 2 && mean_row >= kRunMinMeanRow));
+  if (run_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, run_rt);
+  return BuildForm{n_ranges, bucket_rt, run_rt, bucket_build, lds_build, run_build, mean_run};
+}
+
 // ---- index build for rows [row0, n_rows): rebuild every tile of `ix` that contains one of them ----
 int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
   const int64_t cb = ix.cb;
@@ -677,38 +841,13 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
   if (ix.h_base.empty()) ix.h_base.push_back(0);
   ix.h_base.resize((size_t)tile0 + 1);  // bases of the tiles that stay
   const int64_t r0 = tile0 * cb;
-  // small dims: counters and cursors of a (tile, term range) live in one workgroup's LDS (no global atomics)
-  int32_t n_ranges = (int32_t)ceil_div(h->cfg.dim, kBuildRange);
-  // (one workgroup per (tile, range): with fewer than ~48 of them -- a small batch, a rebuilt tail tile, a 1/8 candidate
-  // range -- the row-parallel global-atomic kernels are faster; APSS_BUILD_LDS / APSS_BUILD_ATOMIC force either)
-  // large dims (more than kBuildMaxRanges ranges: vectorDim = 2^20): a build from the first tile partitions the entries by
-  // term range first (k_bucket_pass), so that the LDS build's workgroups read their bucket instead of the whole tile
   const int64_t build_nnz = h->head_k ? h->tv.nnz : h->nnz;  // entries of the rows [0, idx_rows) the index is built from
-  // (terms per range of a bucketed build, measured on C5's shape, build ms per step: 1024: 28.3, 2048: 23.9, 4096: 20.4, 8192: 15.6,
-  // 16384: 17.4 -- against 37.5 with the global-atomic kernels; narrow ranges multiply the workgroups' fixed work)
-  int32_t bucket_rt = h->dbgcfg.bucket_range > 0 ? h->dbgcfg.bucket_range : 8192;
-  while (ceil_div(h->cfg.dim, bucket_rt) > kBucketMaxRanges && bucket_rt < kBuildRange) bucket_rt *= 2;
-  const bool bucket_build = n_ranges > kBuildMaxRanges && ceil_div(h->cfg.dim, bucket_rt) <= kBucketMaxRanges && !h->dbgcfg.build_atomic &&
-                            !h->dbgcfg.no_bucket && tile0 == 0 && n_tiles * n_ranges >= 48 && build_nnz > 0 && build_nnz <= (1LL << 32) &&
-                            n_tiles * (int64_t)kBucketSlices < (1LL << 31);
-  if (bucket_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, bucket_rt);
-  const bool lds_build = bucket_build || (n_ranges <= kBuildMaxRanges && !h->dbgcfg.build_atomic &&
-                                          ((n_tiles - tile0) * n_ranges >= 48 || h->dbgcfg.build_lds));
+  const BuildForm form = build_form(h, cb, tile0, n_tiles, h->idx_rows, build_nnz, h->store_max_nnz);
+  const int32_t n_ranges = form.n_ranges, bucket_rt = form.bucket_rt, run_rt = form.run_rt;
+  const bool bucket_build = form.bucket_build, lds_build = form.lds_build, run_build = form.run_build;
+  const double mean_run = form.mean_run;
   if (!lds_build)
     HIPCHK(h, hipMemsetAsync(ix.seg.p + tile0 * stride, 0, (size_t)((n_tiles - tile0) * stride) * sizeof(uint2), h->stream));
-  // Run-reading LDS build (k_row_cuts + k_tile_runs): wherever the streaming LDS build would re-read the tile's entries -- two
-  // term ranges or more -- and the rows are long enough to be worth a cut table (kRunMinMeanRow).  With one range
-  // the streaming kernels read every entry exactly once, coalesced: nothing to save.  32-bit cut points: (longest row) x (rows
-  // per tile) < 2^31.
-  const double mean_row = h->idx_rows > 0 ? (double)build_nnz / (double)h->idx_rows : 0.0;
-  int32_t run_rt = h->dbgcfg.run_range > 0 ? std::min(h->dbgcfg.run_range, kBuildRange) : kRunRange;
-  const int64_t t_lo = h->cfg.term_lo, t_hi = h->cfg.term_hi;
-  const int64_t run_active = std::max<int64_t>(1, ceil_div(t_hi, run_rt) - t_lo / run_rt);  // ranges that hold terms of this handle
-  const double mean_run = mean_row / (double)run_active;
-  const bool run_build = lds_build && !bucket_build && !h->dbgcfg.build_stream && std::max<int64_t>(h->store_max_nnz, 1) * cb < (1LL << 31) &&
-                         ceil_div(h->cfg.dim, run_rt) <= 64 &&
-                         (h->dbgcfg.build_runs || (n_ranges >= 2 && mean_row >= kRunMinMeanRow));
-  if (run_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, run_rt);
   BuildArgs b{};
   fill_build_args(h, ix, b, scaled);
   b.row0 = r0;
@@ -731,10 +870,16 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
             (long long)tile0, (long long)n_tiles, bucket_build ? "bucketed" : (run_build ? "runs" : (lds_build ? "stream" : "atomic")), (int)n_ranges,
             run_build ? run_rt : (bucket_build ? bucket_rt : kBuildRange), run_build ? run_lanes : 0, mean_run);
   if (h->dbgcfg.build_trace && run_build) fprintf(stderr, "[apss]   scatter through sub-ranges of %d terms\n", (int)run_sub);
+  // the cuts k_ingest_plain left while it stored the rows, when they are in this build's form and cover its rows
+  const bool cuts_on_hand = run_build && !h->head_k && h->cut_cb == (int32_t)cb && h->cut_rt == run_rt && h->cut_ranges == n_ranges &&
+                            h->cut_lo <= r0 && h->cut_hi >= h->idx_rows && h->cut_hi > h->cut_lo;
+  if (h->dbgcfg.diag && run_build)
+    fprintf(stderr, "[apss diag] build %s rows [%lld, %lld): cuts %s\n", ix.coarse ? "coarse" : "exact", (long long)r0, (long long)h->idx_rows,
+            cuts_on_hand ? "reused" : "computed");
   if (run_build) {
-    APSS_TRY(ensure(h, h->run_cut, (size_t)((h->idx_rows - r0) * (n_ranges + 1))));
+    if (!cuts_on_hand) APSS_TRY(ensure(h, h->run_cut, (size_t)((h->idx_rows - r0) * (n_ranges + 1))));
     b.range_terms = run_rt;
-    b.run_cut = h->run_cut.p;
+    b.run_cut = cuts_on_hand ? h->ing_cut.p + r0 * (n_ranges + 1) : h->run_cut.p;
     if (run_sub) {
       APSS_TRY(ensure(h, h->bk_cnt, (size_t)n_bk + 2));
       APSS_TRY(ensure(h, h->bk_base, (size_t)n_bk + 2));
@@ -823,8 +968,9 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
   const size_t run_lds = (size_t)run_rt * sizeof(uint32_t);
   if (bucket_build) {}  // (counted above, group by group)
   else if (run_build) {
-    hipLaunchKernelGGL(k_row_cuts, dim3((unsigned)ceil_div((h->idx_rows - r0) * kGroup, threads)), dim3(threads), 0, h->stream, b, n_ranges,
-                       h->run_cut.p);
+    if (!cuts_on_hand)
+      hipLaunchKernelGGL(k_row_cuts, dim3((unsigned)ceil_div((h->idx_rows - r0) * kGroup, threads)), dim3(threads), 0, h->stream, b, n_ranges,
+                         h->run_cut.p);
     launch_tile_runs<kRunHist>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
     if (run_sub) {
       APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, n_bk));
@@ -906,6 +1052,47 @@ double acc8_scale(double bound, double shared, double theta) {
   return 0.0;
 }
 
+// rows per tile of the coarse rendering when the handle chooses them (no tile_rows, no cx_tile), from the store's shape: `rows`
+// rows of `nnz` entries, the longest of `max_nnz`, the largest squared norm `max_norm2`
+int32_t pick_cx_tile(const apss_handle *h, int64_t rows, int64_t nnz, int64_t max_nnz, float max_norm2) {
+  // a round's cost is mostly fixed, so what matters is how many postings a (tile, term) segment holds:
+  // rows_per_tile * nnz_per_row / dim.  Below ~16 at 32768 rows (C5 shape: 6.5) the 65536-row tile with one
+  // 1024-thread workgroup per CU wins (C5 shape at N=2M: 647 vs 790 ms); at C3 (33) two workgroups per CU win.
+  const double seg32 = 32768.0 * ((double)nnz / (double)rows) / (double)h->cfg.dim;
+  int32_t cb = seg32 < 16.0 && !h->sharded && !h->head_k ? 65536 : 32768;  // (the 1024-thread kernel has no shard variant)
+  // sparser still (C5: 6.5): 131072-row tiles with 8-bit accumulators (k_probe_coarse<1024, .., ACC8>) when the norms and
+  // row lengths leave room for them: half the segment-descriptor look-ups and half the half-empty posting lines
+  if (cb == 65536 && seg32 < 8.0 && h->nonneg && !h->dbgcfg.no_acc8 && !h->no_acc8 && max_nnz <= 512 &&
+      acc8_scale((double)max_norm2 * 1.0001 + 1e-6, (double)max_nnz, h->cfg.theta) > 0)
+    cb = 131072;
+  // a term shard's rounds are thin (1/T of every query's terms): 8-bit accumulators hold 65536 candidates in the same
+  // 64 KB, i.e. half the rounds at the same two workgroups per CU -- when the norms and row lengths leave room for them
+  // (with a dense-head block: only while the tail has no long segments -- the prefetched long-segment sweeps exist for
+  // 16-bit accumulators over 32768-row tiles only; known after the build, so an optimistic first build may be repeated)
+  if ((h->sharded || h->head_k) && !(h->head_k && h->head_longseg) && !h->dbgcfg.no_acc8 && !h->no_acc8 &&
+      acc8_scale((double)max_norm2 * 1.0001 + 1e-6, (double)max_nnz, h->cfg.theta) > 0)
+    cb = 65536;
+  return cb;
+}
+
+// Will the index build that follows a plain store batch of n rows / nnz entries at row dst_row0 read runs (build_tiles), and in
+// which form?  Decided before the batch's own summaries are known, so it is a forecast: build_tiles compares the form of the
+// cuts on hand with the one it takes and computes its own when they differ.
+bool ingest_wants_cuts(const apss_handle *h, int64_t dst_row0, int64_t n, int64_t nnz, int32_t *cb, int32_t *rt, int32_t *n_ranges) {
+  if (h->head_k) return false;  // (the build reads the tail view, not the store)
+  const int64_t rows = dst_row0 + n, entries = h->nnz + nnz;
+  const apss_handle::IndexSet &ix = h->use_coarse ? h->cx : h->ex;
+  *cb = ix.cb;
+  if (h->use_coarse && ix.n_tiles == 0 && h->cfg.tile_rows == 0 && !h->dbgcfg.cx_tile)
+    *cb = pick_cx_tile(h, rows, entries, h->store_max_nnz, h->store_max_norm2);
+  if (*cb <= 0) return false;
+  // build_tiles' own decision, for the tiles this batch is expected to (re)build and the store as it will be
+  const BuildForm form = build_form(h, *cb, std::min(h->idx_rows, dst_row0) / *cb, ceil_div(rows, *cb), rows, entries, h->store_max_nnz);
+  *rt = form.run_rt;
+  *n_ranges = form.n_ranges;
+  return form.run_build && form.n_ranges <= 2 * kGroup - 1;  // (k_ingest_plain: two cut counts per lane)
+}
+
 // ---- dense-head block (apss_head.hpp) ----
 constexpr int64_t kTailMaxRows = 1024;   // rows that may wait outside the tile index (scored pair by pair by k_tail_score; 4096 until the append build made folding them in cheap)
 constexpr int64_t kTailMaxBatch = 64;    // a batch larger than this extends the index right away (256 until the append build)
@@ -936,6 +1123,10 @@ constexpr double kHeadSurvivorCost = 2.5e-9;  // seconds per element the dense f
 inline bool head_allowed(const apss_handle *h) {
   return h->use_coarse && (!h->sharded || h->head_fixed) && (h->cfg.head_terms >= 0 || h->head_fixed) && h->cfg.theta > 0.0 &&
          !h->head_blocked && h->nonneg;
+}
+// the policy looks at the term distribution when the store has doubled since it last did (build_index)
+bool head_policy_due(const apss_handle *h, int64_t n_rows) {
+  return head_allowed(h) && !h->head_fixed && n_rows >= std::max<int64_t>(h->cfg.head_terms > 0 ? 1 : kHeadMinRows, 2 * h->head_eval_rows);
 }
 
 // Which rendering the block's rows take.  INT8 (rounded up: a sound filter for the non-negative weights a block needs anyway)
@@ -1167,14 +1358,23 @@ int32_t choose_head(apss_handle *h, bool *changed) {
   h->head_eval_rows = n;
   const int64_t stride = std::max<int64_t>(1, n / 65536);
   const int64_t sampled = ceil_div(n, stride);
-  APSS_TRY(ensure(h, h->df, (size_t)dim));
-  HIPCHK(h, hipMemsetAsync(h->df.p, 0, (size_t)dim * sizeof(uint32_t), h->stream));
-  hipLaunchKernelGGL(k_df_sample, dim3((unsigned)ceil_div(sampled * kWave, 256)), dim3(256), 0, h->stream,
-                     (const int64_t *)h->rowptr.p, (const int32_t *)h->idx.p, n, stride, h->df.p);
-  HIPCHK(h, hipGetLastError());
-  std::vector<uint32_t> df((size_t)dim);
-  HIPCHK(h, hipMemcpyAsync(df.data(), h->df.p, (size_t)dim * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  std::vector<uint32_t> df;
+  // the sample k_ingest_plain took while it stored these very rows, or one taken now
+  const bool delivered = h->df_rows == n && h->df_stride == stride && h->df_host.size() == (size_t)dim;
+  if (delivered) {
+    df.swap(h->df_host);
+  } else {
+    APSS_TRY(ensure(h, h->df, (size_t)dim));
+    HIPCHK(h, hipMemsetAsync(h->df.p, 0, (size_t)dim * sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(k_df_sample, dim3((unsigned)ceil_div(sampled * kWave, 256)), dim3(256), 0, h->stream,
+                       (const int64_t *)h->rowptr.p, (const int32_t *)h->idx.p, n, stride, h->df.p);
+    HIPCHK(h, hipGetLastError());
+    df.resize((size_t)dim);
+    HIPCHK(h, hipMemcpyAsync(df.data(), h->df.p, (size_t)dim * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  h->df_rows = -1;
+  if (h->dbgcfg.diag) fprintf(stderr, "[apss diag] head policy: df sample of %lld rows %s\n", (long long)n, delivered ? "reused" : "computed");
   std::vector<int32_t> order((size_t)dim);
   for (int32_t t = 0; t < dim; ++t) order[(size_t)t] = t;
   const size_t top = (size_t)std::min<int32_t>(dim, kHeadMaxTerms);
@@ -1277,7 +1477,7 @@ int32_t build_index(apss_handle *h, int64_t row0) {
   row0 = std::min(row0, h->idx_rows);  // rows waiting in the tail are folded in with this batch
   h->idx_rows = h->n_rows;
   if (head_allowed(h)) {
-    if (!h->head_fixed && h->n_rows >= std::max<int64_t>(h->cfg.head_terms > 0 ? 1 : kHeadMinRows, 2 * h->head_eval_rows)) {
+    if (head_policy_due(h, h->n_rows)) {
       bool changed = false;
       APSS_TRY(choose_head(h, &changed));
       if (changed) {  // every tile's posting lists change with the term set: rebuild from the first row
@@ -1305,23 +1505,7 @@ int32_t build_index(apss_handle *h, int64_t row0) {
   }
   if (h->use_coarse) {
     if (h->cx.n_tiles == 0 && h->cfg.tile_rows == 0 && !h->dbgcfg.cx_tile && h->idx_rows > 0) {
-      // a round's cost is mostly fixed, so what matters is how many postings a (tile, term) segment holds:
-      // rows_per_tile * nnz_per_row / dim.  Below ~16 at 32768 rows (C5 shape: 6.5) the 65536-row tile with one
-      // 1024-thread workgroup per CU wins (C5 shape at N=2M: 647 vs 790 ms); at C3 (33) two workgroups per CU win.
-      const double seg32 = 32768.0 * ((double)h->nnz / (double)h->n_rows) / (double)h->cfg.dim;
-      h->cx.cb = seg32 < 16.0 && !h->sharded && !h->head_k ? 65536 : 32768;  // (the 1024-thread kernel has no shard variant)
-      // sparser still (C5: 6.5): 131072-row tiles with 8-bit accumulators (k_probe_coarse<1024, .., ACC8>) when the norms and
-      // row lengths leave room for them: half the segment-descriptor look-ups and half the half-empty posting lines
-      if (h->cx.cb == 65536 && seg32 < 8.0 && h->nonneg && !h->dbgcfg.no_acc8 && !h->no_acc8 && h->store_max_nnz <= 512 &&
-          acc8_scale((double)h->store_max_norm2 * 1.0001 + 1e-6, (double)h->store_max_nnz, h->cfg.theta) > 0)
-        h->cx.cb = 131072;
-      // a term shard's rounds are thin (1/T of every query's terms): 8-bit accumulators hold 65536 candidates in the same
-      // 64 KB, i.e. half the rounds at the same two workgroups per CU -- when the norms and row lengths leave room for them
-      // (with a dense-head block: only while the tail has no long segments -- the prefetched long-segment sweeps exist for
-      // 16-bit accumulators over 32768-row tiles only; known after the build, so an optimistic first build may be repeated)
-      if ((h->sharded || h->head_k) && !(h->head_k && h->head_longseg) && !h->dbgcfg.no_acc8 && !h->no_acc8 &&
-          acc8_scale((double)h->store_max_norm2 * 1.0001 + 1e-6, (double)h->store_max_nnz, h->cfg.theta) > 0)
-        h->cx.cb = 65536;
+      h->cx.cb = pick_cx_tile(h, h->n_rows, h->nnz, h->store_max_nnz, h->store_max_norm2);
     }
     APSS_TRY(build_tiles(h, h->cx, row0));
     h->st.build_ms += h->cx.build_ms;
@@ -2653,6 +2837,15 @@ int32_t pack_query_head(apss_handle *h, const int64_t *rowptr, const int32_t *id
 
 int32_t query_dev_impl(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_idx,
                        const float *d_val, const int64_t *d_ext, int64_t *n_results) {
+  // the results and the query batch of the last call live until the next query-type call: this one restages q_* (a plain
+  // batch is written there before its flags are known, and the buffers may be reallocated), so they are gone from here on --
+  // also when this batch is rejected (the result calls then answer APSS_E_STATE, as after an insert)
+  h->n_res = -1;
+  h->res_q_ext = nullptr;
+  h->last_q_rowptr = nullptr;
+  h->last_q_idx = nullptr;
+  h->last_q_val = nullptr;
+  h->last_nq = 0;
   int64_t kept_rows = 0, kept_nnz = 0;
   APSS_TRY(ingest(h, n, nnz, d_rowptr, d_idx, d_val, d_ext, false, &kept_rows, &kept_nnz));
   // the batch's rows of the dense-head block and its tail ratios (the store's were packed when it was indexed)
@@ -2775,7 +2968,7 @@ void apss_destroy(apss_handle *h) {
   release(h->head_pos); release(h->W);
   for (apss_handle::TailView *v : {&h->tv, &h->qtv}) { release(v->rowptr); release(v->idx); release(v->val); release(v->erow); }
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
-  release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent);
+  release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2994,6 +3187,8 @@ int32_t apss_clear(apss_handle *h) {
   h->head_eval_rows = 0;
   h->head_blocked = false;
   h->head_nonempty = 0;
+  h->cut_lo = h->cut_hi = 0;
+  h->df_rows = -1;
   return APSS_OK;
 }
 

@@ -115,14 +115,18 @@ __global__ void k_ingest_count(IngestArgs a) {
   auto account = [&](const float v, const int32_t t) {
     sum += v;  // EPA:89 with max-weight 1.0
     const bool keep_v = !(a.flags & 1u) || v > a.index_threshold;  // WWA:192: the pruned vector is what is scored
-    if (keep_v) full += v * v;
+    // (the product rounded, then the sum, spelled out: k_ingest_plain sums a plain batch's squares the same way, and the bits of
+    // the largest squared norm -- the accumulators' scale -- must not depend on which of the two kernels saw the batch, nor on
+    // whether a compiler fuses this line)
+    const float sq = __fmul_rn(v, v);
+    if (keep_v) full += sq;
     const bool keep = keep_v && t >= a.term_lo && t < a.term_hi;
     if (keep) {
       cnt++;
       // (a shard with a dense-head block: the block's terms are a part of their own in the {H, T_1 .. T_T} partition of the
       // shard rule; an entry of the block that lies in this range is stored for the exact partial score, but |x_g| is the
       // norm of the range WITHOUT it)
-      if (!a.head_pos || a.head_pos[t] < 0) sub += v * v;
+      if (!a.head_pos || a.head_pos[t] < 0) sub += sq;
       if (v < 0.f) bad |= 4;
     }
   };
@@ -224,6 +228,140 @@ __global__ void k_ingest_write(IngestWriteArgs w) {
     w.o_rowptr[dr + 1] = w.dst_nnz0 + w.nnz_dst[row] + a.row_cnt[row];
     w.o_ext[dr] = w.ext[row];
     if (w.o_sub) w.o_sub[dr] = a.row_sub[row];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// PLAIN batch (no term range, normalise, prune or admission: every row and every entry is kept, values as they came) in ONE
+// pass: the checks and batch summaries of k_ingest_count, the copy of k_ingest_write (placement = the batch's own rowptr), and
+// -- while the terms are in registers -- the per-row range cuts of the run-reading index build (k_row_cuts) and the sampled
+// document frequencies of the head policy (k_df_sample).  Nothing the checks find is needed to place an entry, so the host
+// reads the flag word once, behind this kernel: on a rejected batch it commits nothing and what was written beyond the
+// store's extent is dead.
+struct IngestPlainArgs {
+  IngestWriteArgs w;     // in.{n, nnz, rowptr, idx, val, dim, flags_out}, the destination and ext; the per-row arrays are not used
+  uint32_t *cut;         // cut table of the destination, [dst row][n_ranges + 1] (k_row_cuts' values; null: none)
+  int32_t n_ranges;      //   <= 2 * kGroup - 1: a lane holds the counts of ranges gl and gl + kGroup
+  int32_t range_terms;
+  int32_t cb;            //   rows per tile: a cut counts from the first entry of the row's tile
+  uint32_t *df;          // [dim] document frequencies over the destination rows r % df_stride == 0 (zeroed by the host; null: none)
+  int64_t df_stride;
+};
+
+// one kGroup-lane group per row; lane grouping, per-lane summation order and the __shfl_xor reduction are those of
+// k_ingest_count<kGroup>, so the batch summaries (the largest squared norm above all: it scales the accumulators) keep their bits
+__global__ void k_ingest_plain(IngestPlainArgs p) {
+  const IngestWriteArgs &w = p.w;
+  const IngestArgs &a = w.in;
+  constexpr int G = kGroup;
+  __shared__ unsigned sh[4];
+  if (threadIdx.x < 4) sh[threadIdx.x] = 0;
+  __syncthreads();
+  const int gl = threadIdx.x % G;
+  const int gshift = __lane_id() & ~(G - 1);  // first lane of this group in its wave
+  const int64_t rows_per_sweep = (int64_t)gridDim.x * (blockDim.x / G);
+  const uint32_t rt = (uint32_t)p.range_terms;
+  // Software pipeline, as in k_tile_runs: memory instructions retire in order, so a load issued behind this iteration's stores
+  // waits for them.  The next row's extents and the next two chunks of the row are requested BEFORE the stores of this one.
+  int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  int64_t b_next = 0, e_next = 0;
+  if (row < a.n) {
+    b_next = a.rowptr[row];
+    e_next = a.rowptr[row + 1];
+  }
+  for (; row < a.n; row += rows_per_sweep) {
+    int64_t b = b_next, e = e_next;
+    if (row + rows_per_sweep < a.n) {
+      b_next = a.rowptr[row + rows_per_sweep];
+      e_next = a.rowptr[row + rows_per_sweep + 1];
+    }
+    unsigned bad = 0;
+    const bool extents_ok = !(b < 0 || e < b || e > a.nnz || (row == 0 && b != 0));
+    if (!extents_ok) {  // malformed extents: flag the batch, read and write nothing of this row
+      bad |= 1;
+      b = e = 0;
+    }
+    const int64_t dr = w.dst_row0 + row;
+    const int64_t out = w.dst_nnz0 + b;
+    const bool sampled = p.df && (uint32_t)dr % (uint32_t)p.df_stride == 0;  // (a handle holds fewer than 2^31 rows)
+    float full = 0.f;
+    uint32_t below0 = 0, below1 = 0;  // entries of the row in ranges < gl / < gl + G
+    int32_t t_prev = -1;              // term of the entry before this chunk's first (strictly increasing: > -1)
+    // two chunks of G entries per iteration, the two of the next iteration in flight
+    int32_t tA = 0, tB = 0, tA_next = 0, tB_next = 0;
+    float vA = 0.f, vB = 0.f, vA_next = 0.f, vB_next = 0.f;
+    auto load = [&](const int64_t k0, int32_t &t0, float &v0, int32_t &t1, float &v1) {
+      const int64_t k = k0 + gl;
+      t0 = k < e ? a.idx[k] : 0;
+      v0 = k < e ? a.val[k] : 0.f;
+      t1 = k + G < e ? a.idx[k + G] : 0;
+      v1 = k + G < e ? a.val[k + G] : 0.f;
+    };
+    if (b < e) load(b, tA_next, vA_next, tB_next, vB_next);
+    for (int64_t k0 = b; k0 < e; k0 += 2 * G) {
+      const int64_t kA = k0 + gl, kB = kA + G;
+      const bool inA = kA < e, inB = kB < e;
+      tA = tA_next, vA = vA_next, tB = tB_next, vB = vB_next;
+      if (k0 + 2 * G < e) load(k0 + 2 * G, tA_next, vA_next, tB_next, vB_next);
+      auto chunk = [&](const int64_t k, const bool in, const int32_t t, const float v) {
+        int32_t tp = __shfl_up(t, 1, G);
+        if (gl == 0) tp = t_prev;
+        t_prev = __shfl(t, G - 1, G);
+        const bool in_dim = in && (uint32_t)t < (uint32_t)a.dim;
+        if (in) {
+          if (!in_dim || tp >= t) bad |= 1;  // SV:75 strictly increasing, < size
+          if (!isfinite(v)) bad |= 2;
+          if (v < 0.f) bad |= 4;
+          full += __fmul_rn(v, v);  // (rounded product, then the sum: as k_ingest_count spells it out)
+          const int64_t o = out + (k - b);
+          w.o_idx[o] = t;
+          w.o_val[o] = v;
+          if (w.o_erow) w.o_erow[o] = (uint32_t)dr;
+          // (a term outside [0, dim) never indexes anything: the batch is rejected, but only behind this kernel)
+          if (sampled && in_dim) atomicAdd(&p.df[t], 1u);
+        }
+        if (p.cut) {
+          // terms increase along the row: the entries below the boundary of range j are a prefix of it, counted by a ballot
+          for (int32_t j = 1; j <= p.n_ranges; ++j) {
+            const uint32_t c = (uint32_t)__popc((unsigned)((__ballot(in_dim && (uint32_t)t < (uint32_t)j * rt) >> gshift) & 0xffffu));
+            if (j == gl) below0 += c;
+            if (j == gl + G) below1 += c;
+          }
+        }
+      };
+      chunk(kA, inA, tA, vA);
+      if (k0 + G < e) chunk(kB, inB, tB, vB);
+    }
+    for (int o = G / 2; o; o >>= 1) {
+      full += __shfl_xor(full, o, G);
+      bad |= __shfl_xor(bad, o, G);
+    }
+    if (extents_ok && p.cut) {
+      // first entry of the row's tile: a row of this batch, or one the store already holds
+      const int64_t tr = (int64_t)((uint32_t)dr / (uint32_t)p.cb) * p.cb;
+      const int64_t tb = tr >= w.dst_row0 ? w.dst_nnz0 + a.rowptr[tr - w.dst_row0] : w.o_rowptr[tr];
+      uint32_t *c = p.cut + dr * (p.n_ranges + 1);
+      const uint32_t first = (uint32_t)(out - tb);
+      if (gl <= p.n_ranges) c[gl] = first + below0;
+      if (gl + G <= p.n_ranges) c[gl + G] = first + below1;
+    }
+    if (gl == 0) {
+      if (extents_ok) {
+        w.o_rowptr[dr + 1] = w.dst_nnz0 + e;
+        w.o_ext[dr] = w.ext[row];
+      }
+      if (bad) atomicOr(&sh[0], bad);
+      atomicMax(&sh[1], (unsigned)(e - b));      // (the summaries of k_ingest_count: every row is admitted, every entry kept)
+      atomicMax(&sh[2], __float_as_uint(full));
+      if (e > b) atomicAdd(&sh[3], 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (sh[0]) atomicOr(a.flags_out, sh[0]);
+    if (sh[1]) atomicMax(a.flags_out + 1, sh[1]);
+    if (sh[2]) atomicMax(a.flags_out + 2, sh[2]);
+    if (sh[3]) atomicAdd(a.flags_out + 3, sh[3]);
   }
 }
 
