@@ -27,6 +27,8 @@ SYMBOLS = [
     "apss_group_create_grid", "apss_group_grid_get",
     # per-query top-k (csrc/apss_topk.hpp)
     "apss_set_top_k", "apss_topk_get", "apss_group_set_top_k", "apss_group_topk_get",
+    # ... in windows of query rows (csrc/apss_window.hpp)
+    "apss_set_top_k_window", "apss_topk_window_get", "apss_topk_window_cuts",
 ]
 GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
 GROUP_NO_SYMMETRIC_RANGES = 8
@@ -85,6 +87,13 @@ class TopkInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("pairs_over_theta", C.c_int64), ("kept", C.c_int64),
                 ("queries_cut", C.c_int64), ("longest_segment", C.c_int64), ("select_ms", C.c_double),
                 ("select_launches", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class TopkWindowInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("windows", C.c_int32), ("max_pairs", C.c_int64), ("bound_total", C.c_int64),
+                ("bound_window_max", C.c_int64), ("pairs_window_max", C.c_int64), ("rows_window_min", C.c_int64),
+                ("rows_window_max", C.c_int64), ("single_row_over", C.c_int64), ("overflow_reruns", C.c_int32),
+                ("plan_launches", C.c_int32), ("plan_ms", C.c_double)]
 
 
 def build_sources():
@@ -239,5 +248,11 @@ def lib():
         f = getattr(L, name)
         f.restype = i32
         f.argtypes = [vp, C.POINTER(TopkInfo)]
+    L.apss_set_top_k_window.restype = i32
+    L.apss_set_top_k_window.argtypes = [vp, i64]
+    L.apss_topk_window_get.restype = i32
+    L.apss_topk_window_get.argtypes = [vp, C.POINTER(TopkWindowInfo)]
+    L.apss_topk_window_cuts.restype = i32
+    L.apss_topk_window_cuts.argtypes = [vp, i64, vp, pi64]
     _lib = L
     return L

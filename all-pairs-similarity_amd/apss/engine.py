@@ -26,7 +26,7 @@ def _ptr(a):
 
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
-                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0):
+                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -47,9 +47,12 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
-        if top_k:
+        if top_k or top_k_window:
             try:
-                self.set_top_k(top_k)
+                if top_k_window:
+                    self.set_top_k_window(top_k_window)
+                if top_k:
+                    self.set_top_k(top_k)
             except ApssError:
                 self.close()
                 raise
@@ -143,6 +146,27 @@ class ApssIndex:
         ti.struct_size = C.sizeof(_lib.TopkInfo)
         self._chk(self._L.apss_topk_get(self._h, C.byref(ti)))
         return {k: getattr(ti, k) for k, _ in _lib.TopkInfo._fields_}
+
+    def set_top_k_window(self, pairs):
+        """with top-k on: join and cut the query-type calls made from now on in windows of consecutive query rows, so that the
+        handle never holds more than about `pairs` uncut pairs (0: off).  Same list, element by element"""
+        self._chk(self._L.apss_set_top_k_window(self._h, int(pairs)))
+
+    def topk_window_info(self):
+        """how the last query-type call was windowed (apss_topk_window_info; windows = 0: it was not)"""
+        wi = _lib.TopkWindowInfo()
+        wi.struct_size = C.sizeof(_lib.TopkWindowInfo)
+        self._chk(self._L.apss_topk_window_get(self._h, C.byref(wi)))
+        return {k: getattr(wi, k) for k, _ in _lib.TopkWindowInfo._fields_}
+
+    def topk_window_cuts(self):
+        """the last call's windows as windows + 1 ascending row offsets of its batch (empty: it was not windowed)"""
+        n = C.c_int64(0)
+        self._chk(self._L.apss_topk_window_cuts(self._h, 0, None, C.byref(n)))
+        cuts = np.zeros(n.value, dtype=np.int64)
+        if n.value:
+            self._chk(self._L.apss_topk_window_cuts(self._h, n.value, _ptr(cuts), C.byref(n)))
+        return cuts
 
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`

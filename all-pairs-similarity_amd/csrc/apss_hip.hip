@@ -19,6 +19,7 @@
 #include "apss_head.hpp"
 #include "apss_even.hpp"
 #include "apss_topk.hpp"
+#include "apss_window.hpp"
 
 using namespace apss;
 
@@ -293,6 +294,18 @@ struct apss_handle {
   int32_t top_k = 0;
   TopkWork topk;
   apss_topk_info tk{};
+  // ... in windows of query rows (apss_window.hpp): the budget, the plan's buffers, the call's own output arrays (probe_inner may
+  // rebuild or regrow anything else while earlier windows' kept lists wait there), what the last query-type call did
+  int64_t top_k_window = 0;
+  DevBuf<unsigned int> win_df;  // [dim] exact term counts of the store, recomputed at every windowed call
+  DevBuf<int32_t> win_b;        // [nq] b(q), and behind it [nq] the rows' non-empty bits (stored batch of a handle with a head)
+  DevBuf<int32_t> win_q, win_c;
+  DevBuf<float> win_s;
+  std::vector<int64_t> win_cuts;
+  apss_topk_window_info tw{};
+  // a windowed call's self-touch corrections: non-empty rows of the window being probed (-1: not in a window)
+  int64_t win_nonempty = -1, win_head_nonempty = -1;
+  int64_t probe_reruns = 0;     // probes that ran again because a list overflowed, since create
   // stats
   apss_stats st{};
   size_t bytes_reserved = 0;
@@ -2205,7 +2218,12 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   const bool hybrid = hybrid_wanted;
   // the batch's rows of the dense-head block and its tail ratios: the store's were packed when it was indexed; an outside
   // batch (or one waiting in the tail) is packed here
-  if (hybrid && q_slot_base < 0 && !h->sharded) APSS_TRY(pack_query_head(h, q_rowptr, q_idx, q_val, nq));  // (a shard's ingest packed them)
+  // A stored batch meets the block's candidates as a TRIANGLE (k_head_gemm skips the tiles above a query block; the block that
+  // owns them reports the mirrored pair): right only when the batch is the store's last rows.  A window of a windowed call
+  // (apss_window.hpp) has stored rows behind it that are no queries of its own: its rows are packed and multiplied as an
+  // outside batch's, against every candidate tile (the pair of a row with itself is dropped by external id there)
+  const bool head_outside = hybrid && h->win_nonempty >= 0 && q_slot_base >= 0 && !h->sharded;
+  if (hybrid && (q_slot_base < 0 || head_outside) && !h->sharded) APSS_TRY(pack_query_head(h, q_rowptr, q_idx, q_val, nq));  // (a shard's ingest packed them)
   const float *q_sub = !shard_rule ? nullptr : (q_slot_base >= 0 ? h->sub.p + q_slot_base : h->q_sub.p);
 
   ProbeArgs a{};
@@ -2588,8 +2606,8 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
       HIPCHK(h, hipMemcpyAsync(&sparse_results, h->counters.p + kCtrResults, sizeof(sparse_results), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipMemsetAsync(h->head_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
       HIPCHK(h, hipEventRecord(h->ev2, h->stream));
-      const bool stored = q_slot_base >= 0;
-      APSS_TRY(run_head(h, a, nq, q_slot_base, stored ? h->W.p : h->q_W.p, stored ? (int64_t)(h->W.cap / h->head_k) : ceil_div(nq, kHeadCTile) * kHeadCTile, head_thr, bound, h->idx_rows));
+      const bool stored = q_slot_base >= 0 && !head_outside;
+      APSS_TRY(run_head(h, a, nq, stored ? q_slot_base : -1, stored ? h->W.p : h->q_W.p, stored ? (int64_t)(h->W.cap / h->head_k) : ceil_div(nq, kHeadCTile) * kHeadCTile, head_thr, bound, h->idx_rows));
       HIPCHK(h, hipEventRecord(h->ev3, h->stream));
       HIPCHK(h, hipMemcpyAsync(head_c, h->head_ctr.p, sizeof(head_c), hipMemcpyDeviceToHost, h->stream));
     }
@@ -2606,14 +2624,17 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     h->st.candidate_pairs = (int64_t)c[kCtrCands];
     // the speed paths count a stored query's touch of its own slot; it is not a (q, c != q) pair
     if ((wave_path || coarse_path) && q_slot_base >= 0)
-      h->st.candidate_pairs -= h->head_k > 0 ? ((q_slot_base == 0 && nq == h->n_rows) ? h->tv.nonempty : h->tv.last_nonempty)
-                                             : ((q_slot_base == 0 && nq == h->n_rows) ? h->store_nonempty : h->last_batch_nonempty);
+      h->st.candidate_pairs -= h->win_nonempty >= 0 ? h->win_nonempty  // (a window of the batch: its own non-empty rows)
+                               : h->head_k > 0 ? ((q_slot_base == 0 && nq == h->n_rows) ? h->tv.nonempty : h->tv.last_nonempty)
+                                               : ((q_slot_base == 0 && nq == h->n_rows) ? h->store_nonempty : h->last_batch_nonempty);
     if (hybrid) {
       HIPCHK(h, hipEventElapsedTime(&ms, h->ev2, h->ev3));
       h->st.head_ms += ms;
       // positive elements of the contraction, minus a stored query's product with itself
       int64_t self = 0;
-      if (q_slot_base >= 0) self = (q_slot_base == 0 && nq == h->n_rows) ? h->head_nonempty : h->last_batch_head_nonempty;
+      if (q_slot_base >= 0)
+        self = h->win_head_nonempty >= 0 ? h->win_head_nonempty
+                                         : (q_slot_base == 0 && nq == h->n_rows) ? h->head_nonempty : h->last_batch_head_nonempty;
       h->st.head_pairs = (int64_t)head_c[1] - self;
       h->st.head_survivors = (int64_t)(c[kCtrResults] - sparse_results);
       // a pair sharing head AND tail terms is scored by both filters; the distinct count lies between max and sum
@@ -2649,6 +2670,7 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
       APSS_TRY(ensure(h, h->res_q, need, 0, true));
       APSS_TRY(ensure(h, h->res_c, need, 0, true));
       APSS_TRY(ensure(h, h->res_s, need, 0, true));
+      ++h->probe_reruns;
       continue;
     }
     if (chain) {  // the exact pass has run already: its list is final
@@ -2676,17 +2698,10 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   return fail(h, APSS_E_STATE, "result buffer kept overflowing");
 }
 
-// A query-type call: the join (probe_inner re-enters itself after a downgrade or a rebuild; what it leaves is the call's final
-// list), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp).
-int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-              int64_t q_nnz_end, int64_t *n_results) {
-  h->tk = apss_topk_info{};
-  APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
-  h->tk.pairs_over_theta = h->tk.kept = h->n_res;
-  if (h->top_k <= 0 || h->sharded) return APSS_OK;
+// The cut of one final list (the call's, or a window's): h->out_* / h->n_res become the kept list, *info says what was done.
+int32_t cut_final_list(apss_handle *h, int64_t nq, apss_topk_info *info) {
   const size_t before = h->topk.bytes;
-  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, &h->tk);
+  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info);
   h->bytes_reserved += h->topk.bytes - before;
   if (e != hipSuccess) {
     h->n_res = -1;
@@ -2697,10 +2712,195 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     h->out_q = h->topk.out_q;
     h->out_c = h->topk.out_c;
     h->out_s = h->topk.out_s;
-    h->n_res = h->tk.kept;
+    h->n_res = info->kept;
   }
-  h->st.result_pairs = h->n_res;
-  if (n_results) *n_results = h->n_res;
+  return APSS_OK;
+}
+
+// Windows of a query-type call (apss_window.hpp): b(q) on the device, the greedy cuts on the host.  Fills h->win_cuts and the
+// planning fields of h->tw; b (and, with `bits`, the rows' non-empty bits behind it) is left in `hb`.
+int32_t plan_windows(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const int64_t *sv_rowptr,
+                     std::vector<int32_t> &hb) {
+  const int32_t dim = h->cfg.dim;
+  APSS_TRY(ensure(h, h->win_df, (size_t)dim));
+  APSS_TRY(ensure(h, h->win_b, (size_t)(2 * nq)));
+  HIPCHK(h, hipMemsetAsync(h->win_df.p, 0, (size_t)dim * sizeof(unsigned int), h->stream));
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  if (h->nnz >= (1LL << 40)) return fail(h, APSS_E_UNSUPPORTED, "windowed top-k: more than 2^40 stored entries");  // (k_win_df's grid)
+  if (h->nnz > 0) {
+    hipLaunchKernelGGL(k_win_df, dim3((unsigned)ceil_div(h->nnz, kTopkBlock)), dim3(kTopkThreads), 0, h->stream, (const int32_t *)h->idx.p, h->nnz, dim,
+                       h->win_df.p);
+    ++h->tw.plan_launches;
+  }
+  hipLaunchKernelGGL(k_win_bound, dim3((unsigned)ceil_div(nq * kWinWave, kWinThreads)), dim3(kWinThreads), 0, h->stream, q_rowptr, q_idx, nq,
+                     (const unsigned int *)h->win_df.p, dim, h->n_rows, sv_rowptr, h->win_b.p, h->win_b.p + nq);
+  ++h->tw.plan_launches;
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  hb.resize((size_t)(sv_rowptr ? 2 * nq : nq));
+  HIPCHK(h, hipMemcpyAsync(hb.data(), h->win_b.p, hb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->tw.plan_ms = ms;
+  // a window: the longest run of rows from its start whose bounds sum to <= max_pairs; a row over the budget is a window of one
+  const int64_t budget = h->top_k_window;
+  h->win_cuts.assign(1, 0);
+  int64_t sum = 0;
+  for (int64_t q = 0; q < nq; ++q) {
+    const int64_t b = hb[(size_t)q];
+    h->tw.bound_total += b;
+    if (q > h->win_cuts.back() && sum + b > budget) {
+      h->win_cuts.push_back(q);
+      sum = 0;
+    }
+    sum += b;
+    h->tw.bound_window_max = std::max(h->tw.bound_window_max, sum);
+    if (b > budget) ++h->tw.single_row_over;
+  }
+  h->win_cuts.push_back(nq);
+  h->tw.windows = (int32_t)(h->win_cuts.size() - 1);
+  h->tw.rows_window_min = nq;
+  for (size_t w = 0; w + 1 < h->win_cuts.size(); ++w) {
+    const int64_t rows = h->win_cuts[w + 1] - h->win_cuts[w];
+    h->tw.rows_window_min = std::min(h->tw.rows_window_min, rows);
+    h->tw.rows_window_max = std::max(h->tw.rows_window_max, rows);
+  }
+  return APSS_OK;
+}
+
+// A query-type call: the join (probe_inner re-enters itself after a downgrade or a rebuild; what it leaves is the call's final
+// list), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
+// apss_set_top_k_window, join and pass window by window over the query rows (apss_window.hpp), the kept lists concatenated.
+int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+              int64_t q_nnz_end, int64_t *n_results) {
+  h->tk = apss_topk_info{};
+  h->tw = apss_topk_window_info{};
+  h->tw.max_pairs = h->top_k_window;
+  h->win_cuts.clear();
+  const bool windowed = h->top_k > 0 && h->top_k_window > 0 && !h->sharded && nq <= 0x7fffffffLL && nq * h->n_rows > h->top_k_window;
+  if (!windowed) {
+    APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
+    h->tk.pairs_over_theta = h->tk.kept = h->n_res;
+    if (h->top_k <= 0 || h->sharded) return APSS_OK;
+    APSS_TRY(cut_final_list(h, nq, &h->tk));
+    h->st.result_pairs = h->n_res;
+    if (n_results) *n_results = h->n_res;
+    return APSS_OK;
+  }
+  // ---- the plan.  A stored batch of a handle with a dense-head block: the rows' tail view tells which of them the sparse
+  // filter / the block see at all (the per-window self-touch corrections); a batch the view does not cover (it waits outside the
+  // index) is corrected by its rows with any entry at all, should a window fold it in: candidate_pairs stays a lower bound
+  h->n_res = -1;  // (the last call's list may live in buffers the windows reuse: gone from here on, also when the plan fails)
+  const bool bits = h->head_k > 0 && q_slot_first >= 0 && q_slot_first + nq <= h->tv.rows && h->tv.rowptr.p;
+  std::vector<int32_t> hb;
+  APSS_TRY(plan_windows(h, nq, q_rowptr, q_idx, bits ? h->tv.rowptr.p + q_slot_first : nullptr, hb));
+  const int64_t kept_max = [&] {
+    int64_t s = 0;
+    for (int64_t q = 0; q < nq; ++q) s += std::min<int64_t>(hb[(size_t)q], h->top_k);
+    return s;
+  }();
+  APSS_TRY(ensure(h, h->win_q, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
+  APSS_TRY(ensure(h, h->win_c, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
+  APSS_TRY(ensure(h, h->win_s, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
+  if (h->dbgcfg.res_cap <= 0) {
+    // no window overflows its candidate list: the bound holds for the filters' survivors too (twice with a dense-head block,
+    // whose two filters may both pass a pair)
+    const size_t need = (size_t)std::max<int64_t>(1, h->tw.bound_window_max * (h->head_k > 0 ? 2 : 1));
+    APSS_TRY(ensure(h, h->res_q, need, 0, true));
+    APSS_TRY(ensure(h, h->res_c, need, 0, true));
+    APSS_TRY(ensure(h, h->res_s, need, 0, true));
+  }
+  apss_stats sum{};
+  apss_topk_info tk{};
+  tk.k = h->top_k;
+  int64_t n_out = 0;
+  int32_t rc = APSS_OK;
+  for (size_t w = 0; w + 1 < h->win_cuts.size() && rc == APSS_OK; ++w) {
+    const int64_t r0 = h->win_cuts[w], r1 = h->win_cuts[w + 1];
+    h->win_nonempty = h->win_head_nonempty = 0;
+    for (int64_t q = r0; q < r1; ++q) {
+      const int32_t ne = bits ? hb[(size_t)(nq + q)] : (hb[(size_t)q] > 0 ? 3 : 0);
+      h->win_nonempty += ne & 1;
+      h->win_head_nonempty += (ne >> 1) & 1;
+    }
+    const int64_t reruns = h->probe_reruns;
+    rc = probe_inner(h, r1 - r0, q_rowptr + r0, q_idx, q_val, q_ext + r0, q_slot_first < 0 ? -1 : q_slot_first + r0, q_max_nnz,
+                     q_max_norm2, q_nnz_end, nullptr);
+    if (rc != APSS_OK) break;
+    if (h->probe_reruns > reruns) ++h->tw.overflow_reruns;
+    h->tw.pairs_window_max = std::max(h->tw.pairs_window_max, h->n_res);
+    sum.posting_visits += h->st.posting_visits;
+    sum.device_posting_visits += h->st.device_posting_visits;
+    sum.candidate_pairs += h->st.candidate_pairs;
+    sum.filter_survivors += h->st.filter_survivors;
+    sum.probe_launches += h->st.probe_launches;
+    sum.thin_launches += h->st.thin_launches;
+    sum.probe_ms += h->st.probe_ms;
+    sum.rescore_ms += h->st.rescore_ms;
+    sum.head_ms += h->st.head_ms;
+    sum.head_flops += h->st.head_flops;
+    sum.head_pairs += h->st.head_pairs;
+    sum.head_survivors += h->st.head_survivors;
+    apss_topk_info one{};
+    rc = cut_final_list(h, r1 - r0, &one);
+    if (rc != APSS_OK) break;
+    tk.pairs_over_theta += one.pairs_over_theta;
+    tk.kept += one.kept;
+    tk.queries_cut += one.queries_cut;
+    tk.longest_segment = std::max(tk.longest_segment, one.longest_segment);
+    tk.select_ms += one.select_ms;
+    tk.select_launches += one.select_launches;
+    if (h->n_res > 0) {
+      if (n_out + h->n_res > (int64_t)h->win_q.cap) {  // (cannot happen: a row keeps at most min(b, k) pairs)
+        rc = fail(h, APSS_E_STATE, "a window kept more pairs than its rows' bounds allow");
+        break;
+      }
+      hipLaunchKernelGGL(k_win_append, dim3((unsigned)std::min<int64_t>(4096, ceil_div(h->n_res, kWinThreads))), dim3(kWinThreads), 0, h->stream,
+                         h->out_q, h->out_c, h->out_s, h->n_res, (int32_t)r0, h->win_q.p + n_out, h->win_c.p + n_out, h->win_s.p + n_out);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) {
+        rc = fail(h, APSS_E_DEVICE, std::string("k_win_append: ") + hipGetErrorString(e));
+        break;
+      }
+      n_out += h->n_res;
+    }
+  }
+  h->win_nonempty = h->win_head_nonempty = -1;
+  if (rc == APSS_OK) {
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) rc = fail(h, APSS_E_DEVICE, std::string("windowed top-k: ") + hipGetErrorString(e));
+  }
+  // the handle names the whole batch again, whatever the last window left
+  h->res_q_ext = q_ext;
+  h->last_q_rowptr = q_rowptr;
+  h->last_q_idx = q_idx;
+  h->last_q_val = q_val;
+  h->last_nq = nq;
+  if (rc != APSS_OK) {
+    h->n_res = -1;
+    return rc;
+  }
+  h->st.posting_visits = sum.posting_visits;
+  h->st.device_posting_visits = sum.device_posting_visits;
+  h->st.candidate_pairs = sum.candidate_pairs;
+  h->st.filter_survivors = sum.filter_survivors;
+  h->st.probe_launches = sum.probe_launches;
+  h->st.thin_launches = sum.thin_launches;
+  h->st.probe_ms = sum.probe_ms;
+  h->st.rescore_ms = sum.rescore_ms;
+  h->st.head_ms = sum.head_ms;
+  h->st.head_flops = sum.head_flops;
+  h->st.head_pairs = sum.head_pairs;
+  h->st.head_survivors = sum.head_survivors;
+  h->tk = tk;
+  h->out_q = h->win_q.p;
+  h->out_c = h->win_c.p;
+  h->out_s = h->win_s.p;
+  h->n_res = n_out;
+  h->st.result_pairs = n_out;
+  if (n_results) *n_results = n_out;
   return APSS_OK;
 }
 
@@ -2970,6 +3170,7 @@ void apss_destroy(apss_handle *h) {
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
   release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
+  release(h->win_df); release(h->win_b); release(h->win_q); release(h->win_c); release(h->win_s);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3260,6 +3461,36 @@ int32_t apss_set_top_k(apss_handle *h, int32_t k) {
   if (k > 0 && h->sharded)
     return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k: a term shard reports candidates with partial scores; the group cuts behind its exchange");
   h->top_k = k;
+  return APSS_OK;
+}
+
+int32_t apss_set_top_k_window(apss_handle *h, int64_t max_pairs) {
+  if (!h) return APSS_E_INVALID;
+  // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
+  if (max_pairs < 0) return fail(h, APSS_E_INVALID, g_create_error = "apss_set_top_k_window: max_pairs must be >= 0 (0: off)");
+  if (max_pairs > 0 && h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k_window: a term shard reports candidates with partial scores; it has no per-query top-k to window");
+  h->top_k_window = max_pairs;
+  return APSS_OK;
+}
+
+int32_t apss_topk_window_get(apss_handle *h, apss_topk_window_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_topk_window_info.struct_size must be set to sizeof(apss_topk_window_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_topk_window_info));
+  h->tw.struct_size = n;
+  std::memcpy(out, &h->tw, (size_t)n);
+  return APSS_OK;
+}
+
+int32_t apss_topk_window_cuts(apss_handle *h, int64_t capacity, int64_t *out_cuts, int64_t *n_cuts) {
+  if (!h || !n_cuts) return APSS_E_INVALID;
+  if (capacity < 0 || (capacity > 0 && !out_cuts)) return fail(h, APSS_E_INVALID, "apss_topk_window_cuts: capacity without an array");
+  *n_cuts = (int64_t)h->win_cuts.size();
+  const int64_t n = std::min<int64_t>(capacity, *n_cuts);
+  if (n > 0) std::memcpy(out_cuts, h->win_cuts.data(), (size_t)n * sizeof(int64_t));
   return APSS_OK;
 }
 

@@ -238,6 +238,12 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
   if (conf.devices.size() == 1) c.device_id = conf.devices[0];
   const int32_t rc = apss_create(&c, &h_);
   if (rc != APSS_OK) throw std::runtime_error(std::string("apss_create: ") + apss_last_error(nullptr));
+  if (conf.topKWindowPairs != 0 && apss_set_top_k_window(h_, conf.topKWindowPairs) != APSS_OK) {
+    const std::string msg = std::string("apss_set_top_k_window: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
   if (conf.topK != 0 && apss_set_top_k(h_, conf.topK) != APSS_OK) {
     const std::string msg = std::string("apss_set_top_k: ") + apss_last_error(h_);
     apss_destroy(h_);

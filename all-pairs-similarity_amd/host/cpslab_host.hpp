@@ -97,6 +97,10 @@ struct Config {
   // apss_group_set_top_k.  A grid (rowRanges > 1) does not support it: the refusal is reported through lastError() and the
   // worker runs with 0
   int topK = 0;
+  // cpslab.allpair.gpu.topKWindowPairs: 0 (default) = off; P > 0 = with topK > 0 the plain handle joins and cuts a call in
+  // windows of query rows holding at most about P uncut pairs each (apss_set_top_k_window): the same answer in bounded memory.
+  // Groups do not take it
+  long topKWindowPairs = 0;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

@@ -1,6 +1,7 @@
 // host_topk_selftest.cpp -- cpslab.allpair.gpu.topK through the mirrored reference interface: a GpuIndexingWorker with
 // topK = 2 replies inner maps of at most two candidates, the ones a plain handle with apss_set_top_k(2) reports for the same
-// rows; a term-sharded worker does the same behind its exchange; a grid refuses and keeps answering with every pair.
+// rows; a term-sharded worker does the same behind its exchange; so does a worker with topKWindowPairs set (the cut in windows
+// of query rows); a grid refuses and keeps answering with every pair.
 // Needs a GPU.  Build: see Makefile in this directory.
 #include <cmath>
 #include <cstdio>
@@ -67,7 +68,9 @@ int main() {
   for (int64_t i = 0; i < n_res; ++i) want["v" + std::to_string(q[(size_t)i])]["v" + std::to_string(cc[(size_t)i])] = (double)s[(size_t)i];
   apss_destroy(h);
 
-  for (int variant = 0; variant < 3; ++variant) {  // one handle; two term shards sharing GPU 0; one member with the exchange forced
+  // one handle; two term shards sharing GPU 0; one member with the exchange forced; one handle cutting in windows of query rows
+  // (cpslab.allpair.gpu.topKWindowPairs = 100 < 48 x 48: the same maps, bit for bit)
+  for (int variant = 0; variant < 4; ++variant) {
     Config conf;
     conf.similarityThreshold = 0.1;
     conf.vectorDim = dim;
@@ -75,6 +78,7 @@ int main() {
     conf.topK = k;
     if (variant == 1) conf.devices = {0, 0};
     if (variant == 2) { conf.devices = {0}; conf.groupFlags = 1u; }
+    if (variant == 3) conf.topKWindowPairs = 100;
     std::vector<SimilarityOutput> got;
     GpuIndexingWorker w(conf, [&](const SimilarityOutput &o) { got.push_back(o); });
     w.receive(batch);
@@ -91,7 +95,7 @@ int main() {
         CHECK(wq != want.end());
         if (wq == want.end()) continue;
         auto wc = wq->second.find(ce.first);
-        if (variant == 0) CHECK(wc != wq->second.end() && wc->second == ce.second);
+        if (variant == 0 || variant == 3) CHECK(wc != wq->second.end() && wc->second == ce.second);
         else if (wc != wq->second.end()) CHECK(std::fabs(wc->second - ce.second) <= 1e-5);
         else {
           double lowest = 2.0;

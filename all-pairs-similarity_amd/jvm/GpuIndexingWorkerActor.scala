@@ -57,11 +57,15 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.topK is not supported with cpslab.allpair.gpu.rowRanges > 1; running with 0")
     0
   } else topKConf
+  // cpslab.allpair.gpu.topKWindowPairs = P (default 0: off; one GPU only): with topK > 0 a call is joined and cut in windows of
+  // query rows that hold at most about P uncut pairs each (apss_set_top_k_window) -- what makes similarityThreshold = 0 fit
+  private val topKWindowPairs =
+    if (conf.hasPath("cpslab.allpair.gpu.topKWindowPairs")) conf.getLong("cpslab.allpair.gpu.topKWindowPairs") else 0L
   private val handle =
     if (grouped && rowRanges > 1)
       NativeApss.createGroupGrid(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, rowRanges, topK)
     else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, topK)
-    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms, topK)
+    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms, topKWindowPairs, topK)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =
     if (grouped) NativeApss.groupSubmit(handle, mode, rowptr, indices, values, ids)

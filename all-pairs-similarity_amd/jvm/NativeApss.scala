@@ -13,7 +13,8 @@ object NativeApss {
     * topK: 0 = every pair >= theta; 1 .. TOP_K_MAX = at most that many candidates per query, the best by (score descending,
     * candidate id ascending), the results grouped by query in rank order (apss_set_top_k).  A topK the library refuses
     * fails the create: 0 is returned and lastError(0) says why */
-  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, headTerms: Int, topK: Int): Long
+  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, headTerms: Int,
+                     topKWindowPairs: Long, topK: Int): Long
   @native def destroy(h: Long): Unit
   @native def lastError(h: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

@@ -24,7 +24,7 @@
 
 JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cls, jint dim, jdouble theta,
                                                           jdouble indexThreshold, jint flags, jint device, jint headTerms,
-                                                          jint topK) {
+                                                          jlong topKWindowPairs, jint topK) {
   (void)env; (void)cls;
   apss_config c = {0};
   c.struct_size = (int32_t)sizeof(c);
@@ -36,7 +36,8 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cl
   c.head_terms = headTerms;
   apss_handle *h = 0;
   if (apss_create(&c, &h) != APSS_OK) return 0;
-  if (apss_set_top_k(h, topK) != APSS_OK) { /* refused: as a failed create (the text stays readable through lastError(0)) */
+  /* refused: as a failed create (the text stays readable through lastError(0)) */
+  if (apss_set_top_k_window(h, (int64_t)topKWindowPairs) != APSS_OK || apss_set_top_k(h, topK) != APSS_OK) {
     apss_destroy(h);
     return 0;
   }

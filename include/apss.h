@@ -282,6 +282,41 @@ typedef struct apss_topk_info {
 int32_t apss_set_top_k(apss_handle *h, int32_t k);
 int32_t apss_topk_get(apss_handle *h, apss_topk_info *out);
 
+/* ---- per-query top-k in bounded memory: windows of query rows ("Windows") ----
+ * Without a window budget the cut runs once, over the call's whole list of pairs >= theta -- which must fit the device first (at
+ * theta <= 0: every pair that shares a term).  With max_pairs > 0 and k > 0 a query-type call whose batch could report more than
+ * max_pairs pairs (query rows x stored rows > max_pairs) is run as WINDOWS of consecutive query rows, each joined and cut on its
+ * own and appended to the call's list, so that the handle never holds more than about max_pairs uncut pairs:
+ *   b(q) = min(sum of df_t over the terms t of query row q, stored rows), df_t = stored rows holding t (rows waiting outside the
+ *   tile index included), bounds the pairs of row q: every reported pair shares a term.  A window is the longest run of rows
+ *   from its start whose sum of b is <= max_pairs; a row with b > max_pairs is a window of one (single_row_over counts them).
+ * The answer is the list of the unwindowed call, element by element: same order, same score bits; apss_topk_info and apss_stats
+ * are summed over the windows (longest_segment: the maximum).  The symmetric whole-store join does not run in windows
+ * (apss_stats.symmetric_declined = APSS_SYM_NOT_WHOLE).  k_win_df / k_win_bound plan the windows (df is recomputed from the
+ * store at every windowed call), k_win_append concatenates.
+ * max_pairs = 0 (the default): off, everything as without the setting.  No effect while k = 0.  The setting may be changed at any
+ * time (it takes effect at the next query-type call, leaves the last call's results alone and survives apss_clear).
+ * APSS_E_INVALID: max_pairs < 0.  APSS_E_UNSUPPORTED: max_pairs > 0 on a term shard (as apss_set_top_k). */
+typedef struct apss_topk_window_info {
+  int32_t struct_size;       /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t windows;           /* windows of the last query-type call (0: it was not windowed) */
+  int64_t max_pairs;         /* the setting the call ran with */
+  int64_t bound_total;       /* sum of b(q) over the batch */
+  int64_t bound_window_max;  /* the largest sum of b over one window */
+  int64_t pairs_window_max;  /* the most pairs >= theta any one window's uncut final list held */
+  int64_t rows_window_min;   /* rows of the shortest / longest window */
+  int64_t rows_window_max;
+  int64_t single_row_over;   /* windows of one row whose bound exceeds max_pairs */
+  int32_t overflow_reruns;   /* windows whose probe ran again because a list overflowed */
+  int32_t plan_launches;     /* k_win_df + k_win_bound launches (k_win_append runs once per non-empty window and is not counted) */
+  double plan_ms;            /* device time of the planning kernels, HIP events */
+} apss_topk_window_info;
+int32_t apss_set_top_k_window(apss_handle *h, int64_t max_pairs);
+int32_t apss_topk_window_get(apss_handle *h, apss_topk_window_info *out);
+/* the windows of the last query-type call as windows + 1 ascending row offsets of its batch (cuts[0] = 0, cuts[windows] = rows of
+ * the batch); *n_cuts = how many there are (0: the call was not windowed); the first min(capacity, *n_cuts) are written */
+int32_t apss_topk_window_cuts(apss_handle *h, int64_t capacity, int64_t *out_cuts, int64_t *n_cuts);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE

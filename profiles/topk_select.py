@@ -12,11 +12,21 @@ pairs_over_theta) at the 6.29 TB/s copy peak, and the bytes this design moves --
   output   12 B per kept pair
 -- computed from the shapes (every segment taken as long when the mean segment is above 1024, four digit passes: an upper
 estimate for data without ties at the cut).
-Usage: python profiles/topk_select.py [--reps 3] [--shape template|c2|all] > profiles/topk_select.json"""
+Usage: python profiles/topk_select.py [--reps 3] [--shape template|c2|all] > profiles/topk_select.json
+
+--window-pairs P [P ...] (apss_set_top_k_window, DESIGN.md 5e "Windows") measures the windowed call instead: on each chosen shape,
+k = --k, `--reps` self-joins alternating the unwindowed setting (0) and every P, each setting on a handle of its own (a handle's
+reservations only grow: `hbm_bytes` of a shared one would be the unwindowed list's) after one warm-up call.  Per call: wall time
+of the call (it returns after the stream is synchronised), probe_ms, rescore_ms, select_ms, plan_ms, windows, the planning
+figures and hbm_bytes.  `--shape c3zero` is C3's store (N = 1M, dim 100k, nnz 100) at theta = 0: the unwindowed setting is left
+out there (its list does not fit the device) and one call per P is made, without a warm-up.
+  python profiles/topk_select.py --shape template --window-pairs 67108864 268435456 > profiles/topk_window_template.json
+  python profiles/topk_select.py --shape c3zero --window-pairs 1073741824 > profiles/topk_window_c3zero.json"""
 import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -34,12 +44,58 @@ def design_bytes(pairs, kept, nq, passes=4):
     return pairs * 4 + pairs * 20 + select + kept * 12
 
 
+C3_ZERO = ("c3_store_theta0", 1_000_000, 100_000, 100, 0.0, 0.0)
+
+
+def windowed_call(ix):
+    t0 = time.perf_counter()
+    ix.self_join(fetch=False)
+    wall = (time.perf_counter() - t0) * 1e3
+    st, ti, tw = ix.stats(), ix.topk_info(), ix.topk_window_info()
+    call = {"wall_ms": wall, "probe_ms": st["probe_ms"], "rescore_ms": st["rescore_ms"], "select_ms": ti["select_ms"],
+            "hbm_bytes": st["hbm_bytes"], "pairs_over_theta": ti["pairs_over_theta"], "kept": ti["kept"]}
+    call.update({k: v for k, v in tw.items() if k != "struct_size"})
+    return call
+
+
+def windows_main(a):
+    out = {}
+    shapes = dict(SHAPES, c3zero=C3_ZERO)
+    for key, (name, n, dim, nnz, zipf, theta) in shapes.items():
+        if a.shape != key and not (a.shape == "all" and key != "c3zero"):
+            continue
+        once = key == "c3zero"
+        rp, idx, val = synth.make_vectors(n, dim, nnz, zipf, seed=11)
+        row = {"n": n, "dim": dim, "nnz": nnz, "zipf_s": zipf, "theta": theta, "k": a.k, "calls": []}
+        settings = list(a.window_pairs) if once else [0] + list(a.window_pairs)
+        handles = []
+        try:
+            for pairs in settings:
+                ix = ApssIndex(dim, theta, top_k=a.k, top_k_window=pairs)
+                handles.append(ix)
+                ix.insert(np.arange(n), rp, idx, val)
+                if not once:
+                    ix.self_join(fetch=False)  # warm-up: sizes this setting's buffers
+            for rep in range(1 if once else a.reps):
+                for pairs, ix in zip(settings, handles):
+                    row["calls"].append(windowed_call(ix))
+        finally:
+            for ix in handles:
+                ix.close()
+        out[name] = row
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--shape", default="all")
+    ap.add_argument("--window-pairs", type=int, nargs="+", default=None,
+                    help="measure apss_set_top_k_window at these budgets against the unwindowed call (see the module docstring)")
     a = ap.parse_args()
+    if a.window_pairs:
+        return windows_main(a)
     out = {}
     for key, (name, n, dim, nnz, zipf, theta) in SHAPES.items():
         if a.shape not in ("all", key):
