@@ -29,7 +29,10 @@ SYMBOLS = [
     "apss_set_top_k", "apss_topk_get", "apss_group_set_top_k", "apss_group_topk_get",
     # ... in windows of query rows (csrc/apss_window.hpp)
     "apss_set_top_k_window", "apss_topk_window_get", "apss_topk_window_cuts",
+    # ... with each round cut inside the theta <= 0 probe kernel
+    "apss_set_top_k_tile_cut", "apss_topk_tile_cut_get",
 ]
+TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
 GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
 GROUP_NO_SYMMETRIC_RANGES = 8
 EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
@@ -94,6 +97,11 @@ class TopkWindowInfo(C.Structure):
                 ("bound_window_max", C.c_int64), ("pairs_window_max", C.c_int64), ("rows_window_min", C.c_int64),
                 ("rows_window_max", C.c_int64), ("single_row_over", C.c_int64), ("overflow_reruns", C.c_int32),
                 ("plan_launches", C.c_int32), ("plan_ms", C.c_double)]
+
+
+class TopkTileCutInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("applied", C.c_int32), ("declined", C.c_int32), ("prefix_bits", C.c_int32),
+                ("pairs_emitted", C.c_int64), ("rounds_cut", C.c_int64)]
 
 
 def build_sources():
@@ -254,5 +262,9 @@ def lib():
     L.apss_topk_window_get.argtypes = [vp, C.POINTER(TopkWindowInfo)]
     L.apss_topk_window_cuts.restype = i32
     L.apss_topk_window_cuts.argtypes = [vp, i64, vp, pi64]
+    L.apss_set_top_k_tile_cut.restype = i32
+    L.apss_set_top_k_tile_cut.argtypes = [vp, i32]
+    L.apss_topk_tile_cut_get.restype = i32
+    L.apss_topk_tile_cut_get.argtypes = [vp, C.POINTER(TopkTileCutInfo)]
     _lib = L
     return L

@@ -26,7 +26,7 @@ def _ptr(a):
 
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
-                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0):
+                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -47,10 +47,12 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
-        if top_k or top_k_window:
+        if top_k or top_k_window or top_k_tile_cut:
             try:
                 if top_k_window:
                     self.set_top_k_window(top_k_window)
+                if top_k_tile_cut:
+                    self.set_top_k_tile_cut(True)
                 if top_k:
                     self.set_top_k(top_k)
             except ApssError:
@@ -158,6 +160,18 @@ class ApssIndex:
         wi.struct_size = C.sizeof(_lib.TopkWindowInfo)
         self._chk(self._L.apss_topk_window_get(self._h, C.byref(wi)))
         return {k: getattr(wi, k) for k, _ in _lib.TopkWindowInfo._fields_}
+
+    def set_top_k_tile_cut(self, on):
+        """with top-k on: a call that runs the theta <= 0 kernel cuts every (query row, tile) round to the pairs that can be
+        among a row's k best before it writes them (False: off).  Same list, element by element"""
+        self._chk(self._L.apss_set_top_k_tile_cut(self._h, 1 if on else 0))
+
+    def topk_tile_cut_info(self):
+        """what the cut inside the probe did in the last query-type call (apss_topk_tile_cut_info)"""
+        ci = _lib.TopkTileCutInfo()
+        ci.struct_size = C.sizeof(_lib.TopkTileCutInfo)
+        self._chk(self._L.apss_topk_tile_cut_get(self._h, C.byref(ci)))
+        return {k: getattr(ci, k) for k, _ in _lib.TopkTileCutInfo._fields_}
 
     def topk_window_cuts(self):
         """the last call's windows as windows + 1 ascending row offsets of its batch (empty: it was not windowed)"""

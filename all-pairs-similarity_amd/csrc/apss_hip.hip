@@ -305,7 +305,13 @@ struct apss_handle {
   apss_topk_window_info tw{};
   // a windowed call's self-touch corrections: non-empty rows of the window being probed (-1: not in a window)
   int64_t win_nonempty = -1, win_head_nonempty = -1;
-  int64_t probe_reruns = 0;     // probes that ran again because a list overflowed, since create
+  // ... with each (query row, tile) round cut inside k_probe<2> (apss_set_top_k_tile_cut): the setting, the rows' uncut counts
+  // of the probe that last ran (probe_inner: cut_ran, cut_uncut, cut_rounds), what the last query-type call did
+  bool tile_cut = false, cut_ran = false;
+  int64_t cut_uncut = 0, cut_rounds = 0;
+  DevBuf<uint32_t> row_pairs;  // [nq]
+  apss_topk_tile_cut_info tci{};
+  int64_t probe_reruns = 0;    // probes that ran again because a list overflowed, since create
   // stats
   apss_stats st{};
   size_t bytes_reserved = 0;
@@ -1542,9 +1548,9 @@ int32_t build_index(apss_handle *h, int64_t row0) {
   return APSS_OK;
 }
 
-template <int MODE, bool FX, int BLOCK = kProbeBlock>
+template <int MODE, bool FX, int BLOCK = kProbeBlock, bool CUT = false>
 int32_t launch_probe(apss_handle *h, const ProbeArgs &a, size_t lds) {
-  auto kern = k_probe<MODE, BLOCK, FX>;
+  auto kern = k_probe<MODE, BLOCK, FX, CUT>;
   HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)a.n_tiles * a.n_chunks)), dim3(BLOCK), lds, h->stream, a);
   HIPCHK(h, hipGetLastError());
@@ -2101,6 +2107,8 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   h->st.thin_launches = 0;
   h->st.queries_per_round = 1;
   h->st.probe_kernel[0] = 0;
+  h->cut_ran = false;
+  h->cut_uncut = h->cut_rounds = 0;
   h->st.head_pairs = h->st.head_survivors = 0;
   h->st.head_ms = h->st.head_flops = 0;
   h->st.head_terms = h->head_k ? (int64_t)h->head_terms.size() : 0;
@@ -2282,6 +2290,13 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
                          h->store_max_nnz * (int64_t)h->ex.cb + (int64_t)kSegAlign * h->cfg.dim < (1LL << 28);
   // ---- path 3: general kernel (k_probe): signed fixed point when the norms are bounded, else fp32 atomics ----
   const bool gen_fx = !coarse_path && !wave_path && fx_scale > 0;
+  // the per-round cut (apss_set_top_k_tile_cut): only where the uncut list is the problem, k_probe<2> of a plain handle
+  const bool gen_cut = h->tile_cut && h->top_k > 0 && !h->sharded && !coarse_path && !wave_path && mode == 2;
+  if (gen_cut) {
+    APSS_TRY(ensure(h, h->row_pairs, (size_t)nq));
+    a.row_pairs = h->row_pairs.p;
+    a.cut_k = h->top_k;
+  }
   const double scale_used = wave_path ? fx_scale : fx_scale / 2;
   a.fx_scale = (float)scale_used;
   a.theta_fx = (uint32_t)std::min(4294967295.0, std::max(1.0, std::ceil(theta * scale_used)));
@@ -2443,6 +2458,7 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     a.res_s = h->res_s.p;
     a.res_cap = h->res_q.cap;
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
+    if (gen_cut) HIPCHK(h, hipMemsetAsync(h->row_pairs.p, 0, (size_t)nq * sizeof(uint32_t), h->stream));  // (every attempt: a re-run counts afresh)
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     int64_t n_launches = 0, thin_launches = 0;
     {  // the instantiation this call launches, spelled as rocprofv3 prints it (apss_stats.probe_kernel)
@@ -2457,6 +2473,8 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
                  cxv.block <= 512 ? 512 : 1024, tf(cxv.shard), cxv.chunk, tf(cxv.vrows), tf(cxv.sgn), tf(cxv.longpf), tf(cxv.acc8));
       else if (wave_path)
         snprintf(nm, cap, "k_probe_wave<%d, %d, %d, %d, %s, %s>", wave_block, wave_u, wave_longcap, wave_survcap, tf(h->sharded), tf(dbg.diag));
+      else if (gen_cut)
+        snprintf(nm, cap, "k_probe<%d, %d, %s, true>", mode, gen_block(mode, h->ex.cb), tf(gen_fx));
       else
         snprintf(nm, cap, "k_probe<%d, %d, %s>", mode, gen_block(mode, h->ex.cb), tf(gen_fx));
     }
@@ -2483,6 +2501,12 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
                 100.0 * d[5] / tot, 100.0 * d[6] / tot, (double)tot / ((double)a.n_tiles * a.nq * (wave_block / kWave)));
       } else if (wave_path) {
         APSS_TRY(launch_wave(false));
+      } else if (gen_cut) {
+        const bool b512 = gen_block(2, h->ex.cb) == 512;
+        if (gen_fx && b512) APSS_TRY((launch_probe<2, true, 512, true>(h, a, lds)));
+        else if (gen_fx) APSS_TRY((launch_probe<2, true, kProbeBlock, true>(h, a, lds)));
+        else if (b512) APSS_TRY((launch_probe<2, false, 512, true>(h, a, lds)));
+        else APSS_TRY((launch_probe<2, false, kProbeBlock, true>(h, a, lds)));
       } else if (gen_fx) {
         if (mode == 0) APSS_TRY((launch_probe<0, true>(h, a, lds)));
         else if (mode == 1) APSS_TRY((launch_probe<1, true>(h, a, lds)));
@@ -2687,6 +2711,11 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
       return APSS_OK;
     }
     h->n_res = (int64_t)c[kCtrResults];
+    if (gen_cut) {  // (kCtrPre, kCtrSnap: the uncut total and the rounds cut -- words k_probe<2> leaves alone otherwise)
+      h->cut_ran = true;
+      h->cut_uncut = (int64_t)c[kCtrPre];
+      h->cut_rounds = (int64_t)c[kCtrSnap];
+    }
     h->out_q = h->res_q.p;
     h->out_c = h->res_c.p;
     h->out_s = h->res_s.p;
@@ -2701,7 +2730,9 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
 // The cut of one final list (the call's, or a window's): h->out_* / h->n_res become the kept list, *info says what was done.
 int32_t cut_final_list(apss_handle *h, int64_t nq, apss_topk_info *info) {
   const size_t before = h->topk.bytes;
-  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info);
+  // (a probe that cut its rounds: the list is what it emitted, the rows' uncut counts say what the call found)
+  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info,
+                                h->cut_ran ? h->row_pairs.p : nullptr, h->cut_uncut);
   h->bytes_reserved += h->topk.bytes - before;
   if (e != hipSuccess) {
     h->n_res = -1;
@@ -2779,9 +2810,21 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
   h->tw = apss_topk_window_info{};
   h->tw.max_pairs = h->top_k_window;
   h->win_cuts.clear();
+  h->tci = apss_topk_tile_cut_info{};
+  h->tci.prefix_bits = 16;
+  h->tci.declined = !h->tile_cut ? APSS_TILE_CUT_OFF : (h->top_k <= 0 ? APSS_TILE_CUT_NO_K : APSS_TILE_CUT_PATH);
+  auto note_cut = [h]() {  // after a probe_inner: what its probe emitted and cut (the sum over a call's windows)
+    h->tci.pairs_emitted += h->n_res;
+    h->tci.rounds_cut += h->cut_rounds;
+    if (h->cut_ran) {
+      h->tci.applied = 1;
+      h->tci.declined = APSS_TILE_CUT_RAN;
+    }
+  };
   const bool windowed = h->top_k > 0 && h->top_k_window > 0 && !h->sharded && nq <= 0x7fffffffLL && nq * h->n_rows > h->top_k_window;
   if (!windowed) {
     APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
+    note_cut();
     h->tk.pairs_over_theta = h->tk.kept = h->n_res;
     if (h->top_k <= 0 || h->sharded) return APSS_OK;
     APSS_TRY(cut_final_list(h, nq, &h->tk));
@@ -2830,6 +2873,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
                      q_max_norm2, q_nnz_end, nullptr);
     if (rc != APSS_OK) break;
     if (h->probe_reruns > reruns) ++h->tw.overflow_reruns;
+    note_cut();
     h->tw.pairs_window_max = std::max(h->tw.pairs_window_max, h->n_res);
     sum.posting_visits += h->st.posting_visits;
     sum.device_posting_visits += h->st.device_posting_visits;
@@ -3171,6 +3215,7 @@ void apss_destroy(apss_handle *h) {
   release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
   release(h->win_df); release(h->win_b); release(h->win_q); release(h->win_c); release(h->win_s);
+  release(h->row_pairs);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3471,6 +3516,27 @@ int32_t apss_set_top_k_window(apss_handle *h, int64_t max_pairs) {
   if (max_pairs > 0 && h->sharded)
     return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k_window: a term shard reports candidates with partial scores; it has no per-query top-k to window");
   h->top_k_window = max_pairs;
+  return APSS_OK;
+}
+
+int32_t apss_set_top_k_tile_cut(apss_handle *h, int32_t on) {
+  if (!h) return APSS_E_INVALID;
+  // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
+  if (on != 0 && on != 1) return fail(h, APSS_E_INVALID, g_create_error = "apss_set_top_k_tile_cut: 0 (off) or 1");
+  if (on && h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k_tile_cut: a term shard reports candidates with partial scores; it has no per-query top-k to cut for");
+  h->tile_cut = on != 0;
+  return APSS_OK;
+}
+
+int32_t apss_topk_tile_cut_get(apss_handle *h, apss_topk_tile_cut_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_topk_tile_cut_info.struct_size must be set to sizeof(apss_topk_tile_cut_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_topk_tile_cut_info));
+  h->tci.struct_size = n;
+  std::memcpy(out, &h->tci, (size_t)n);
   return APSS_OK;
 }
 

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "apss_topk_key.hpp"
+
 namespace apss {
 
 constexpr int kWave = 64;          // CDNA wavefront
@@ -1189,6 +1191,9 @@ struct ProbeArgs {
   uint64_t res_cap;
   unsigned long long *counters;  // [kCtrCount]
   unsigned long long *dbg;       // diagnostic build only: per-segment cycle sums [8]
+  // per-round cut of the theta <= 0 emission (k_probe<2, .., CUT = true>; apss_set_top_k_tile_cut), null / 0 when off
+  uint32_t *row_pairs;           // [nq] uncut pairs >= theta per query row, summed over the tiles
+  int32_t cut_k;
 };
 
 // dynamic-LDS carve (all offsets multiples of 16 B)
@@ -1217,8 +1222,26 @@ __host__ __device__ inline size_t probe_lds_bytes(int cb, int block, int mode) {
 //         never scored by the reference even though 0 >= theta).
 // FX: accumulate in signed 32-bit fixed point (scale a.fx_scale) instead of fp32 -- LDS integer atomics are ~25x
 // faster than ds_add_f32 on gfx950; the host picks FX whenever the row norms bound every partial score.
-template <int MODE, int BLOCK, bool FX>
+// a wave's adds to an LDS histogram: ONE when all its matching lanes hold the same digit (the leading digits of a tile's
+// scores at theta = 0), one per lane otherwise
+__device__ __forceinline__ void probe_hist_add(uint32_t *hist, bool match, uint32_t dig) {
+  const unsigned long long m = __ballot(match);
+  if (m == 0ull) return;
+  const int leader = __ffsll((long long)m) - 1;
+  const uint32_t first = (uint32_t)__shfl((int)dig, leader);
+  if (__all(!match || dig == first)) {
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[first], (uint32_t)__popcll(m));
+  } else if (match) {
+    atomicAdd(&hist[dig], 1u);
+  }
+}
+
+// CUT (MODE 2 only): a round with more than a.cut_k results emits only those whose score key reaches the top 16 bits of the
+// round's cut_k-th largest key (DESIGN.md 5e "Cut inside the probe"): a superset of what any row's top k can hold.  The
+// call's uncut total goes to kCtrPre and the rounds cut to kCtrSnap: two counter words no launch of this kernel uses.
+template <int MODE, int BLOCK, bool FX, bool CUT = false>
 __global__ __launch_bounds__(BLOCK) void k_probe(const ProbeArgs a) {
+  static_assert(!CUT || MODE == 2, "the per-round cut belongs to the theta <= 0 emission");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   ProbeLds L;
   {
@@ -1254,6 +1277,8 @@ __global__ __launch_bounds__(BLOCK) void k_probe(const ProbeArgs a) {
   unsigned long long my_visits = 0;
   unsigned long long my_cands = 0;  // first touches seen by this lane
   unsigned long long my_self = 0;
+  unsigned long long my_uncut = 0;  // CUT, thread 0: results of this workgroup's rounds before the cut
+  uint32_t my_rounds_cut = 0;       // CUT, thread 0: rounds that had more than cut_k of them
   __syncthreads();
 
   // software pipeline of the query-side loads (each level is issued one round before it is needed, so no
@@ -1552,6 +1577,94 @@ __global__ __launch_bounds__(BLOCK) void k_probe(const ProbeArgs a) {
           }
         }
         __syncthreads();
+        if (CUT) {
+          // ---- the round's floor.  LDS: two 256-bin histograms in wq, four words in long_w -- both dead since the term passes
+          uint32_t *const hist = reinterpret_cast<uint32_t *>(L.wq);       // [2][256]: BLOCK >= 512 words
+          uint32_t *const cw = reinterpret_cast<uint32_t *>(L.long_w);     // n, {first digit, still wanted}, floor
+          static_assert(BLOCK >= 512, "two histograms in wq");
+          if (tid < 512) hist[tid] = 0u;
+          if (tid < kWave) {
+            const int n_cnt = n_steps * NWV;
+            uint32_t run = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) run += tid * 8 + j < n_cnt ? cnt[tid * 8 + j] : 0u;
+            const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(run), kWave - 1);
+            if (tid == 0) {
+              cw[0] = n;
+              if (n) atomicAdd(&a.row_pairs[q], n);
+              my_uncut += n;
+              my_rounds_cut += n > (uint32_t)a.cut_k ? 1u : 0u;
+            }
+          }
+          __syncthreads();
+          if (cw[0] > (uint32_t)a.cut_k) {  // (one LDS word: the same answer, and the same barriers, for every thread)
+            auto key_of = [&](const int i) -> uint32_t { return topk_key(FX ? (float)acci[i] * fxinv : L.acc[i]); };
+            // the digit (bins scanned from the top by one wave, four per lane) that holds the `want`-th largest; what is still
+            // wanted inside it
+            auto pick = [&](const uint32_t *hh, const uint32_t want, uint32_t &digit, uint32_t &rest) {
+              uint32_t v[4], run = 0;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                v[j] = hh[255 - (tid * 4 + j)];
+                run += v[j];
+              }
+              const uint32_t incl = wave_incl_scan(run);
+              uint32_t above = incl - run;
+              const bool mine = above < want && incl >= want;  // exactly one lane
+              uint32_t dg = 0, rs = 0;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                if (mine && above < want && above + v[j] >= want) {
+                  dg = 255u - (uint32_t)(tid * 4 + j);
+                  rs = want - above;
+                }
+                above += v[j];
+              }
+              const unsigned long long who = __ballot(mine);
+              const int src = who ? __ffsll((long long)who) - 1 : 0;
+              digit = (uint32_t)__shfl((int)dg, src);
+              rest = (uint32_t)__shfl((int)rs, src);
+            };
+            for (int k = 0; k < n_steps; ++k) {
+              const bool ok = (masks[k * NWV + wvi] >> (tid % kWave)) & 1ull;
+              probe_hist_add(hist, ok, ok ? key_of(k * BLOCK + tid) >> 24 : 0u);
+            }
+            __syncthreads();
+            if (tid < kWave) {
+              uint32_t d1, rest;
+              pick(hist, (uint32_t)a.cut_k, d1, rest);
+              if (tid == 0) {
+                cw[1] = d1;
+                cw[2] = rest;
+              }
+            }
+            __syncthreads();
+            const uint32_t d1 = cw[1];
+            for (int k = 0; k < n_steps; ++k) {
+              const bool ok = (masks[k * NWV + wvi] >> (tid % kWave)) & 1ull;
+              const uint32_t key = ok ? key_of(k * BLOCK + tid) : 0u;
+              probe_hist_add(hist + 256, ok && (key >> 24) == d1, (key >> 16) & 255u);
+            }
+            __syncthreads();
+            if (tid < kWave) {
+              uint32_t d2, rest;
+              pick(hist + 256, cw[2], d2, rest);
+              if (tid == 0) cw[3] = (d1 << 24) | (d2 << 16);
+            }
+            __syncthreads();
+            const uint32_t floor_key = cw[3];
+            for (int k = 0; k < n_steps; ++k) {
+              const unsigned long long m0 = masks[k * NWV + wvi];
+              const bool ok = (m0 >> (tid % kWave)) & 1ull;
+              const unsigned long long m = __ballot(ok && key_of(k * BLOCK + tid) >= floor_key);
+              if ((tid % kWave) == 0 && m != m0) {
+                cnt[k * NWV + wvi] = (uint32_t)__popcll(m);
+                masks[k * NWV + wvi] = m;
+              }
+            }
+            __syncthreads();
+          }
+        }
         if (tid < kWave) {  // n_steps * NWV <= 512 counts: eight per lane
           const int n_cnt = n_steps * NWV;
           uint32_t v[8], run = 0;
@@ -1633,6 +1746,10 @@ __global__ __launch_bounds__(BLOCK) void k_probe(const ProbeArgs a) {
   if (tid == 0) {
     atomicAdd(&a.counters[kCtrVisits], stat[0]);
     atomicAdd(&a.counters[kCtrCands], stat[1] - stat[2]);
+    if (CUT) {
+      if (my_uncut) atomicAdd(&a.counters[kCtrPre], my_uncut);
+      if (my_rounds_cut) atomicAdd(&a.counters[kCtrSnap], (unsigned long long)my_rounds_cut);
+    }
   }
 }
 

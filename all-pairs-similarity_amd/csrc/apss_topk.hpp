@@ -9,6 +9,8 @@
 //                   table keyed by query row and adds once per distinct row to the global counters.
 //   k_topk_scan     one workgroup: exclusive scans of count (segment starts) and of min(count, k) (output starts), the kept
 //                   total, the rows cut and the longest segment; resets the counters, which become the scatter's cursors.
+//                   (A probe that cut its rounds -- apss_set_top_k_tile_cut -- hands in the rows' UNCUT counts as a second input:
+//                   the rows cut and the longest segment are then theirs, what the call found and not what the probe emitted.)
 //   k_topk_scatter  (candidate slot, score) of every pair into its row's segment; the same LDS table hands out a workgroup's
 //                   places in a segment with one global atomic per distinct row.
 //   k_topk_select   one workgroup per query row.  A segment of up to 1024 pairs is sorted whole in LDS.  A longer one is cut
@@ -94,9 +96,11 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_count(const int32_t *__re
 }
 
 // cnt[nq] -> seg_start[nq + 1], out_start[nq + 1], info[kTopkInfoWords]; cnt is zeroed (the scatter's cursors)
+// uncut (or null): the rows' counts before a cut inside the probe; min(count, k) is the same for both
 __global__ __launch_bounds__(kTopkScanThreads) void k_topk_scan(unsigned int *__restrict__ cnt, int32_t nq, int32_t k,
                                                                 int64_t *__restrict__ seg_start, int64_t *__restrict__ out_start,
-                                                                unsigned long long *__restrict__ info) {
+                                                                unsigned long long *__restrict__ info,
+                                                                const unsigned int *__restrict__ uncut) {
   __shared__ unsigned long long sa[kTopkScanThreads], sb[kTopkScanThreads];
   __shared__ unsigned int s_cut, s_long;
   const int t = threadIdx.x;
@@ -109,8 +113,9 @@ __global__ __launch_bounds__(kTopkScanThreads) void k_topk_scan(unsigned int *__
     const unsigned int c = cnt[i];
     a += c;
     b += c < (unsigned)k ? c : (unsigned)k;
-    cut += c > (unsigned)k ? 1u : 0u;
-    longest = c > longest ? c : longest;
+    const unsigned int u = uncut ? uncut[i] : c;
+    cut += u > (unsigned)k ? 1u : 0u;
+    longest = u > longest ? u : longest;
   }
   sa[t] = a;
   sb[t] = b;
@@ -417,11 +422,14 @@ inline hipError_t topk_grow(TopkWork &w, T *&p, size_t old_n, size_t n) {
 
 // Runs the pass over (q, c, s)[0, n) on `stream` and waits for it (the one host read: the four info words).  The new list is
 // w.out_*[0, info->kept).  n == 0: nothing is launched.  info: k, pairs_over_theta, kept, queries_cut, longest_segment,
-// select_ms, select_launches are filled.
+// select_ms, select_launches are filled.  uncut (or null) / uncut_total: the rows' pair counts and their sum before a cut inside the
+// probe thinned the list; pairs_over_theta, queries_cut and longest_segment then speak of those (k_topk_scan's second input: the
+// launches stay four).
 inline hipError_t topk_run(TopkWork &w, hipStream_t stream, const int32_t *q, const int32_t *c, const float *s, int64_t n, int64_t nq,
-                           const int64_t *c_ext, int64_t n_store, int32_t k, apss_topk_info *info) {
+                           const int64_t *c_ext, int64_t n_store, int32_t k, apss_topk_info *info, const unsigned int *uncut = nullptr,
+                           int64_t uncut_total = 0) {
   info->k = k;
-  info->pairs_over_theta = n;
+  info->pairs_over_theta = uncut ? uncut_total : n;
   info->kept = info->queries_cut = info->longest_segment = 0;
   info->select_ms = 0.0;
   info->select_launches = 0;
@@ -458,7 +466,8 @@ inline hipError_t topk_run(TopkWork &w, hipStream_t stream, const int32_t *q, co
   if ((e = hipMemsetAsync(w.cnt, 0, ((size_t)nq + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e;
   if ((e = hipEventRecord(w.e0, stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_topk_count, dim3(blocks), dim3(kTopkThreads), 0, stream, q, n, (int32_t)nq, w.cnt);
-  hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(kTopkScanThreads), 0, stream, w.cnt, (int32_t)nq, k, w.seg_start, w.out_start, w.info);
+  hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(kTopkScanThreads), 0, stream, w.cnt, (int32_t)nq, k, w.seg_start, w.out_start, w.info,
+                     uncut);
   hipLaunchKernelGGL(k_topk_scatter, dim3(blocks), dim3(kTopkThreads), 0, stream, q, c, s, n, (int32_t)nq,
                      (const int64_t *)w.seg_start, w.cnt, w.seg_c, w.seg_s);
   hipLaunchKernelGGL(k_topk_select, dim3((unsigned)nq), dim3(kTopkThreads), 0, stream, (const int64_t *)w.seg_start,

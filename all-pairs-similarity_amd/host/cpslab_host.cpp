@@ -244,6 +244,12 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
     h_ = nullptr;
     throw std::runtime_error(msg);
   }
+  if (conf.topKTileCut && apss_set_top_k_tile_cut(h_, 1) != APSS_OK) {
+    const std::string msg = std::string("apss_set_top_k_tile_cut: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
   if (conf.topK != 0 && apss_set_top_k(h_, conf.topK) != APSS_OK) {
     const std::string msg = std::string("apss_set_top_k: ") + apss_last_error(h_);
     apss_destroy(h_);

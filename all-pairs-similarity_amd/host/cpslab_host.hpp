@@ -101,6 +101,10 @@ struct Config {
   // windows of query rows holding at most about P uncut pairs each (apss_set_top_k_window): the same answer in bounded memory.
   // Groups do not take it
   long topKWindowPairs = 0;
+  // cpslab.allpair.gpu.topKTileCut: false (default) = off; true = with topK > 0 and similarityThreshold <= 0 the plain handle's
+  // probe kernel cuts every (query row, tile) round to the pairs that can be among a query's topK before it writes them
+  // (apss_set_top_k_tile_cut): the same answer, a shorter list for the cut.  Groups do not take it
+  bool topKTileCut = false;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

@@ -1,7 +1,8 @@
 // host_topk_selftest.cpp -- cpslab.allpair.gpu.topK through the mirrored reference interface: a GpuIndexingWorker with
 // topK = 2 replies inner maps of at most two candidates, the ones a plain handle with apss_set_top_k(2) reports for the same
 // rows; a term-sharded worker does the same behind its exchange; so does a worker with topKWindowPairs set (the cut in windows
-// of query rows); a grid refuses and keeps answering with every pair.
+// of query rows); a worker with topKTileCut at similarityThreshold = 0 replies what the one without it does (the cut inside the
+// probe kernel); a grid refuses and keeps answering with every pair.
 // Needs a GPU.  Build: see Makefile in this directory.
 #include <cmath>
 #include <cstdio>
@@ -105,6 +106,29 @@ int main() {
       }
     }
     CHECK(pairs == (size_t)n_res);
+  }
+
+  // cpslab.allpair.gpu.topKTileCut at similarityThreshold = 0 (the reference's shipped value, where the probe's rounds are cut
+  // before they are written): the same maps as the worker without it, bit for bit -- and more candidates than topK to cut from
+  {
+    std::vector<SimilarityOutput> got[2];
+    for (int cut = 0; cut < 2; ++cut) {
+      Config conf;
+      conf.similarityThreshold = 0.0;
+      conf.vectorDim = dim;
+      conf.tileRows = 64;
+      conf.topK = k;
+      conf.topKTileCut = cut == 1;
+      GpuIndexingWorker w(conf, [&](const SimilarityOutput &o) { got[cut].push_back(o); });
+      w.receive(batch);
+      CHECK(got[cut].size() == 1 && w.lastError().empty());
+    }
+    if (got[0].size() == 1 && got[1].size() == 1) {
+      CHECK(got[0][0].output == got[1][0].output);
+      size_t pairs = 0;
+      for (auto &qe : got[1][0].output) pairs += qe.second.size();
+      CHECK(pairs == (size_t)n * (size_t)k);
+    }
   }
 
   // a grid does not support it: reported through lastError(), the worker answers with every pair

@@ -61,11 +61,16 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
   // query rows that hold at most about P uncut pairs each (apss_set_top_k_window) -- what makes similarityThreshold = 0 fit
   private val topKWindowPairs =
     if (conf.hasPath("cpslab.allpair.gpu.topKWindowPairs")) conf.getLong("cpslab.allpair.gpu.topKWindowPairs") else 0L
+  // cpslab.allpair.gpu.topKTileCut = true (default false: off; one GPU only): with topK > 0 and similarityThreshold <= 0 the
+  // probe kernel cuts every (query row, tile) round to the pairs that can be among a query's topK before it writes them
+  // (apss_set_top_k_tile_cut) -- the same reply
+  private val topKTileCut =
+    if (conf.hasPath("cpslab.allpair.gpu.topKTileCut") && conf.getBoolean("cpslab.allpair.gpu.topKTileCut")) 1 else 0
   private val handle =
     if (grouped && rowRanges > 1)
       NativeApss.createGroupGrid(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, rowRanges, topK)
     else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, topK)
-    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), headTerms, topKWindowPairs, topK)
+    else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), topKTileCut, headTerms, topKWindowPairs, topK)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =
     if (grouped) NativeApss.groupSubmit(handle, mode, rowptr, indices, values, ids)

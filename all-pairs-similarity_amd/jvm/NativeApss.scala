@@ -12,9 +12,11 @@ object NativeApss {
   /** headTerms: dense-head block of the library (0 = it decides from the term distribution, -1 = never).
     * topK: 0 = every pair >= theta; 1 .. TOP_K_MAX = at most that many candidates per query, the best by (score descending,
     * candidate id ascending), the results grouped by query in rank order (apss_set_top_k).  A topK the library refuses
-    * fails the create: 0 is returned and lastError(0) says why */
-  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, headTerms: Int,
-                     topKWindowPairs: Long, topK: Int): Long
+    * fails the create: 0 is returned and lastError(0) says why.
+    * topKTileCut: 0 = off; 1 = with topK > 0 and theta <= 0 the probe kernel cuts every (query row, tile) round to the pairs
+    * that can be among a query's topK before it writes them (apss_set_top_k_tile_cut): the same reply, a shorter list to cut */
+  @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, topKTileCut: Int,
+                     headTerms: Int, topKWindowPairs: Long, topK: Int): Long
   @native def destroy(h: Long): Unit
   @native def lastError(h: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

@@ -23,8 +23,8 @@
 #define H(x) ((apss_handle *)(intptr_t)(x))
 
 JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cls, jint dim, jdouble theta,
-                                                          jdouble indexThreshold, jint flags, jint device, jint headTerms,
-                                                          jlong topKWindowPairs, jint topK) {
+                                                          jdouble indexThreshold, jint flags, jint device, jint topKTileCut,
+                                                          jint headTerms, jlong topKWindowPairs, jint topK) {
   (void)env; (void)cls;
   apss_config c = {0};
   c.struct_size = (int32_t)sizeof(c);
@@ -37,7 +37,8 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_create(JNIEnv *env, jclass cl
   apss_handle *h = 0;
   if (apss_create(&c, &h) != APSS_OK) return 0;
   /* refused: as a failed create (the text stays readable through lastError(0)) */
-  if (apss_set_top_k_window(h, (int64_t)topKWindowPairs) != APSS_OK || apss_set_top_k(h, topK) != APSS_OK) {
+  if (apss_set_top_k_window(h, (int64_t)topKWindowPairs) != APSS_OK || apss_set_top_k(h, topK) != APSS_OK ||
+      apss_set_top_k_tile_cut(h, topKTileCut) != APSS_OK) {
     apss_destroy(h);
     return 0;
   }

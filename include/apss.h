@@ -303,7 +303,8 @@ typedef struct apss_topk_window_info {
   int64_t max_pairs;         /* the setting the call ran with */
   int64_t bound_total;       /* sum of b(q) over the batch */
   int64_t bound_window_max;  /* the largest sum of b over one window */
-  int64_t pairs_window_max;  /* the most pairs >= theta any one window's uncut final list held */
+  int64_t pairs_window_max;  /* the most pairs >= theta any one window's uncut final list held (with apss_set_top_k_tile_cut
+                              applied: the most pairs any one window's probe EMITTED -- what the handle really held) */
   int64_t rows_window_min;   /* rows of the shortest / longest window */
   int64_t rows_window_max;
   int64_t single_row_over;   /* windows of one row whose bound exceeds max_pairs */
@@ -316,6 +317,37 @@ int32_t apss_topk_window_get(apss_handle *h, apss_topk_window_info *out);
 /* the windows of the last query-type call as windows + 1 ascending row offsets of its batch (cuts[0] = 0, cuts[windows] = rows of
  * the batch); *n_cuts = how many there are (0: the call was not windowed); the first min(capacity, *n_cuts) are written */
 int32_t apss_topk_window_cuts(apss_handle *h, int64_t capacity, int64_t *out_cuts, int64_t *n_cuts);
+
+/* ---- per-query top-k: each round cut inside the theta <= 0 probe kernel ("Cut inside the probe") ----
+ * At theta <= 0 the probe writes every touched candidate of every (query row, candidate tile) round, and the pass above then
+ * reads that list three more times to keep k pairs per row.  With on = 1 and k > 0, a call that runs the theta <= 0 kernel
+ * (k_probe<2, ...>) on a plain handle cuts each ROUND before it is written: a round with more than k pairs >= theta emits only
+ * those whose score key (the order-preserving 32-bit image of the fp32 score) is >= P << 16, P = the top 16 bits of the round's
+ * k-th largest key.  Every pair among a row's first k is among the first k of its own round, so the pass sees a superset of
+ * every row's winners with unchanged score bits: the final list is the list of the call without the setting, element by element.
+ * apss_topk_info keeps reporting what the call FOUND (pairs_over_theta, queries_cut, longest_segment: from per-row counts the
+ * kernel takes before the cut); apss_topk_tile_cut_info says what the probe emitted.  In a windowed call every window's probe
+ * takes the cut; the info is summed over the windows, and apss_topk_window_info.pairs_window_max then reports the EMITTED list
+ * of a window, which is what the handle really held (ties can make a round emit everything: b(q) stays the reservation).
+ * Every other path ignores the setting and says why in `declined`: theta > 0 (the two-pass join, k_probe_wave, k_probe<0 | 1>,
+ * with or without APSS_FLAG_EXACT_ACCUM), k = 0, a call that launched nothing.  Groups do not take the setting.
+ * on = 0 (the default): off, everything exactly as without the setting.  The setting may be changed at any time (it takes effect
+ * at the next query-type call, leaves the last call's results alone and survives apss_clear).
+ * APSS_E_INVALID: on outside {0, 1}, NULL.  APSS_E_UNSUPPORTED: on = 1 on a term shard (as apss_set_top_k). */
+#define APSS_TILE_CUT_RAN 0
+#define APSS_TILE_CUT_OFF 1     /* setting off */
+#define APSS_TILE_CUT_NO_K 2    /* k == 0 */
+#define APSS_TILE_CUT_PATH 3    /* the call did not run the theta <= 0 kernel (or the handle is a term shard) */
+typedef struct apss_topk_tile_cut_info {
+  int32_t struct_size;     /* IN: caller's sizeof; OUT: bytes written */
+  int32_t applied;         /* 1: the last query-type call's probe cut its rounds */
+  int32_t declined;        /* APSS_TILE_CUT_* */
+  int32_t prefix_bits;     /* 16 */
+  int64_t pairs_emitted;   /* pairs the probe left for the pass (== pairs_over_theta when not applied) */
+  int64_t rounds_cut;      /* (query row, tile) rounds that had more than k pairs >= theta */
+} apss_topk_tile_cut_info;  /* 32 bytes */
+int32_t apss_set_top_k_tile_cut(apss_handle *h, int32_t on);
+int32_t apss_topk_tile_cut_get(apss_handle *h, apss_topk_tile_cut_info *out);
 
 
 /* =====================================================================================================================

@@ -21,7 +21,15 @@ of the call (it returns after the stream is synchronised), probe_ms, rescore_ms,
 figures and hbm_bytes.  `--shape c3zero` is C3's store (N = 1M, dim 100k, nnz 100) at theta = 0: the unwindowed setting is left
 out there (its list does not fit the device) and one call per P is made, without a warm-up.
   python profiles/topk_select.py --shape template --window-pairs 67108864 268435456 > profiles/topk_window_template.json
-  python profiles/topk_select.py --shape c3zero --window-pairs 1073741824 > profiles/topk_window_c3zero.json"""
+  python profiles/topk_select.py --shape c3zero --window-pairs 1073741824 > profiles/topk_window_c3zero.json
+
+--tile-cut (apss_set_top_k_tile_cut, DESIGN.md 5e "Cut inside the probe") measures the cut inside the theta <= 0 probe kernel: on
+each chosen shape, k = --k, one handle with the setting off and one with it on (a handle's reservations only grow), a warm-up
+self-join each, then `--reps` self-joins alternating the two.  Per call: probe_ms, select_ms, their sum, pairs_emitted,
+pairs_over_theta, hbm_bytes, the probe's instantiation and why the cut did not apply (C2's shape at theta = 0.5: the declined
+path, which must not move).  A library without the setting (an older commit the script is pointed at) is measured with the off
+handle alone.  profiles/topk_tile_cut.md says what to run beside it.
+  python profiles/topk_select.py --tile-cut --reps 5 > profiles/topk_tile_cut.json"""
 import argparse
 import json
 import os
@@ -86,6 +94,44 @@ def windows_main(a):
     print(json.dumps(out, indent=1))
 
 
+def tile_cut_main(a):
+    have = hasattr(ApssIndex, "set_top_k_tile_cut")
+    out = {"library_has_tile_cut": have}
+    for key, (name, n, dim, nnz, zipf, theta) in SHAPES.items():
+        if a.shape not in ("all", key):
+            continue
+        rp, idx, val = synth.make_vectors(n, dim, nnz, zipf, seed=11)
+        row = {"n": n, "dim": dim, "nnz": nnz, "zipf_s": zipf, "theta": theta, "k": a.k, "calls": []}
+        handles = []
+        try:
+            for on in ([False, True] if have else [False]):
+                ix = ApssIndex(dim, theta, top_k=a.k)
+                handles.append((on, ix))
+                if on:
+                    ix.set_top_k_tile_cut(True)
+                ix.insert(np.arange(n), rp, idx, val)
+                ix.self_join(fetch=False)  # warm-up: sizes this setting's buffers
+            for rep in range(a.reps):
+                for on, ix in handles:
+                    ix.self_join(fetch=False)
+                    st, ti = ix.stats(), ix.topk_info()
+                    call = {"tile_cut": on, "probe_ms": st["probe_ms"], "select_ms": ti["select_ms"],
+                            "probe_plus_select_ms": st["probe_ms"] + ti["select_ms"], "rescore_ms": st["rescore_ms"],
+                            "pairs_over_theta": ti["pairs_over_theta"], "kept": ti["kept"], "hbm_bytes": st["hbm_bytes"],
+                            "probe_kernel": st["probe_kernel"]}
+                    if have:
+                        ci = ix.topk_tile_cut_info()
+                        call.update(applied=ci["applied"], declined=ci["declined"], pairs_emitted=ci["pairs_emitted"],
+                                    rounds_cut=ci["rounds_cut"],
+                                    emitted_share=ci["pairs_emitted"] / max(ti["pairs_over_theta"], 1))
+                    row["calls"].append(call)
+        finally:
+            for _, ix in handles:
+                ix.close()
+        out[name] = row
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -93,9 +139,13 @@ def main():
     ap.add_argument("--shape", default="all")
     ap.add_argument("--window-pairs", type=int, nargs="+", default=None,
                     help="measure apss_set_top_k_window at these budgets against the unwindowed call (see the module docstring)")
+    ap.add_argument("--tile-cut", action="store_true",
+                    help="measure apss_set_top_k_tile_cut off against on, a handle each (see the module docstring)")
     a = ap.parse_args()
     if a.window_pairs:
         return windows_main(a)
+    if a.tile_cut:
+        return tile_cut_main(a)
     out = {}
     for key, (name, n, dim, nnz, zipf, theta) in SHAPES.items():
         if a.shape not in ("all", key):
