@@ -52,8 +52,12 @@
 
 namespace apss {
 
+// the launch's arguments where the kernel finds them: the kernarg segment (scalar loads), see probe_even_body
+using ProbeArgsK = const __attribute__((address_space(4))) ProbeArgs;
+
 template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE>
-__device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
+__device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, const int v0, const int v1, const bool own_tile, const bool first) {
+  // one ITEM of the launch: the rounds [v0, v1) against candidate tile `tile` (`first`: this workgroup's first item)
   // (Tried for C3's full rounds: workgroups of TEN waves -- the eight adding waves of the 512-thread kernel plus two staging
   // waves, 87 VGPRs at five steps.  143 vs 111 ms: ten waves spread 3/3/2/2 over the SIMDs and the second workgroup of a CU
   // needs a SIMD to hold six of them, i.e. <= 80 VGPRs; it did not become resident.)
@@ -89,7 +93,11 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   unsigned char *const smem_raw = reinterpret_cast<unsigned char *>(acc);
   uint32_t *const facts_w = reinterpret_cast<uint32_t *>(facts);
 
-  const int tid = threadIdx.x;
+  // (the thread index, opaque per item: what a lane derives from it -- the addresses of either role -- is otherwise hoisted
+  // out of the persistent loop and stays live through both roles' loops; flagship instantiation: 116 vs 113 VGPRs, 25 vs 11
+  // scalar spills)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
   const int wv = __builtin_amdgcn_readfirstlane(tid / kWave), ln = tid % kWave;
   const int cb = a.cb;
   const int F = a.flat_waves;   // waves that stage a round
@@ -103,8 +111,6 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   // whatever the number of live lanes: the staging wave's instruction count is on the round's critical path)
   const int LOGG = a.flat_group_log2, G = 1 << LOGG;
   const uint32_t sub = (uint32_t)ln & (uint32_t)(G - 1);
-  const int tile = a.tile0 + blockIdx.x / a.n_chunks;
-  const int chunk = blockIdx.x % a.n_chunks;
   // MERGED rounds (ProbeArgs::merge_log2 = m > 0): round v stages the terms of the M = 2^m query rows M v .. M v + M - 1 as
   // ONE row -- they are neighbours in the CSR arrays, so the merged row is the extent rowptr[M v] .. rowptr[M v + M) -- and a
   // candidate's accumulator holds the SUM of its M filter sums: an upper bound of each of them (non-negative weights), so a
@@ -117,23 +123,22 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   // (`mlog` = 0 for this workgroup, on the launch's smaller scale) and marks what it reports with kUnmergedBit.
   // (MERGE: instantiations of their own -- the handful of scalars this costs took the unmerged shard kernel to its SGPR limit: 13.0 -> 13.9 ms at T = 8)
   static_assert(!MERGE || SHARD, "merged rounds: term shards only");
+  // (own_tile is decided per CELL of the launch's (tile, chunk) grid -- probe_even_body below, apss_worklist.hpp -- and the rounds
+  // [v0, v1) of this item count rows then, merged rounds otherwise)
   const int mlaunch = MERGE ? a.merge_log2 : 0;
-  const int c0 = chunk * a.q_chunk;
-  const int row_lo = c0 << mlaunch, row_hi = MERGE ? min(a.nq_rows, (c0 + a.q_chunk) << mlaunch) : 0;  // this workgroup's query rows
-  const bool own_tile = mlaunch != 0 && a.q_slot_base >= 0 && (a.q_slot_base + row_lo) / cb <= tile && tile <= (a.q_slot_base + row_hi - 1) / cb;
   const int mlog = own_tile ? 0 : mlaunch;
-  const int v0 = row_lo >> mlog;
-  const int v1 = own_tile ? row_hi : min(a.nq, c0 + a.q_chunk);
   const int nv = own_tile ? a.nq_rows : a.nq;
-  const int qtile = row_lo / cb;  // (symmetric joins: the chunk lies inside one tile)
-  if (a.tri && tile > qtile) return;  // the mirrored half (ProbeArgs::tri): before any barrier, the whole workgroup
+  const int qtile = (v0 << mlog) / cb;  // (symmetric joins: the item lies inside one tile)
   const int64_t tile_row0 = (int64_t)tile * cb;
   const int unmerged_mark = own_tile ? kUnmergedBit : 0;
   const uint32_t lo = (uint32_t)(ln % LPC);
   const float cxs = a.cx_scale;
 
-  const int64_t qbase = a.q_rowptr[MERGE ? min(v0 << mlog, a.nq_rows) : v0], qend = a.q_rowptr[MERGE ? min(v1 << mlog, a.nq_rows) : v1];
-  const int64_t pbase = a.tile_post_base[tile], pend = a.tile_post_base[tile + 1];
+  // (scalar loads, said to be so: inside the persistent loop these reads lie behind the last item's stores, the compiler no longer
+  // proves them unclobbered and loads them into VECTOR registers -- and a buffer descriptor made of vector registers costs a
+  // waterfall loop around every load through it)
+  const int64_t qbase = uniform_load(a.q_rowptr + (MERGE ? min(v0 << mlog, a.nq_rows) : v0)), qend = uniform_load(a.q_rowptr + (MERGE ? min(v1 << mlog, a.nq_rows) : v1));
+  const int64_t pbase = uniform_load(a.tile_post_base + tile), pend = uniform_load(a.tile_post_base + tile + 1);
   const __amdgpu_buffer_rsrc_t rs_qi =
       __builtin_amdgcn_make_buffer_rsrc((void *)(a.q_idx + qbase), 0, (int)((qend - qbase) * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_qv =
@@ -160,7 +165,10 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   // SIMDs.  C3: 49.3 vs 49.1 ms with it -- profiles/even_steps.md; not kept.)
   constexpr int kFirstSkippable = BLOCK > 512 || !SHARD ? U - 1 : 0;
 
-  for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
+  // (a later item of a persistent workgroup: the accumulators are zero behind the last round's second barrier; the strip
+  // entries are made stale, the facts zero and the spare words 1 again)
+  if (first)
+    for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
   if (tid < kWave) acc[CBMAX / APW + tid] = 1u;  // the spare words (LEAN: never zero in their low accumulator)
   if (LEAN) {  // no strip entry is valid before it is staged
     for (int i = tid; i < 3 * NS * SSZ; i += BLOCK) strips[i].x = kStale;
@@ -627,6 +635,65 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
     atomicAdd(&a.counters[kCtrVisits], stat[0] * twice);
     atomicAdd(&a.counters[kCtrCands], stat[1] * twice);
     atomicAdd(&a.counters[kCtrDevVisits], stat[0]);
+  }
+}
+
+// PERSISTENT LAUNCH (ProbeArgs::items; apss_worklist.hpp).  The launch holds as many workgroups as the chip keeps
+// resident; each takes the next ITEM {tile, rounds [v0, v1)} of the launch's work list -- one lane, a returning global atomic
+// on a.work_ctr -- runs it as the grid launch's workgroup ran its cell, and comes back for another until the list is spent.
+// The index reaches the other waves through LDS behind a barrier that EVERY wave executes (BARRIER PAIRING above: one more
+// per take, in every wave, the failed last take included).  No workgroup ever waits for another one -- no spin, no flag, no
+// grid barrier; all a workgroup shares with the others is the counter -- so a launch of more workgroups than are resident
+// is merely wasteful (the surplus starts when a slot falls free and finds the list spent), never stuck.
+// Between items only what an item's start needs is redone (probe_even_item, `first`).  Everything per item -- tile, rounds,
+// own_tile, the buffer descriptors -- is re-derived from the item, on the scalar unit.  Statistics are flushed per item
+// (`twice` depends on the item's tile).  Without a list (APSS_DEBUG=no_persist) workgroup b runs the one cell that blockIdx
+// names, derived here as work_cell() derives it on the host, and leaves.
+template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE>
+__device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
+  // the grid launch's one cell, worked out before the loop and handed to it in three scalars (left inside the loop the
+  // derivation is a loop invariant: hoisted with its intermediate values, 64-bit quotients among them, and kept across the item)
+  int g_tile = 0, g_v0 = 0, g_v1 = 0;
+  if (!a.items) {
+    const int cb = a.cb, mlaunch = MERGE ? a.merge_log2 : 0;
+    const int tile = a.tile0 + blockIdx.x / a.n_chunks;
+    const int c0 = (blockIdx.x % a.n_chunks) * a.q_chunk;
+    const int row_lo = c0 << mlaunch, row_hi = MERGE ? min(a.nq_rows, (c0 + a.q_chunk) << mlaunch) : 0;  // this workgroup's query rows
+    const bool own_tile = mlaunch != 0 && a.q_slot_base >= 0 && (a.q_slot_base + row_lo) / cb <= tile && tile <= (a.q_slot_base + row_hi - 1) / cb;
+    if (a.tri && tile > row_lo / cb) return;  // the mirrored half (ProbeArgs::tri): before any barrier, the whole workgroup
+    g_tile = tile | (own_tile ? kUnmergedBit : 0);  // (tiles number far below 2^30)
+    g_v0 = own_tile ? row_lo : c0;
+    g_v1 = own_tile ? row_hi : min(a.nq, c0 + a.q_chunk);
+    asm volatile("" : "+s"(g_tile), "+s"(g_v0), "+s"(g_v1));
+  }
+  __shared__ int next_item;
+  for (bool first = true;; first = false) {
+    int tile, v0, v1;
+    bool own_tile;
+    if (a.items) {
+      if (threadIdx.x == 0) next_item = (int)atomicAdd(a.work_ctr, 1ull);
+      __syncthreads();  // (the next write of next_item lies behind the item's own barriers)
+      const int idx = __builtin_amdgcn_readfirstlane(next_item);
+      if (idx >= a.n_items) return;
+      const ProbeItem *const it = a.items + idx;  // (16 B: one scalar load)
+      tile = uniform_load(&it->tile);
+      v0 = uniform_load(&it->v0);
+      v1 = uniform_load(&it->v1);
+      own_tile = uniform_load(&it->own) != 0;
+    } else {
+      if (!first) return;
+      tile = g_tile & ~kUnmergedBit;
+      v0 = g_v0;
+      v1 = g_v1;
+      own_tile = (g_tile & kUnmergedBit) != 0;
+    }
+    // The item reads the launch's arguments through a pointer to the kernarg segment (the kernel's one parameter lies at its
+    // start) that is opaque per item: read through `a` they are loop invariants, hoisted out of this loop and kept in SGPRs
+    // across the whole item on top of what the item derives from them -- the kernels sit at their SGPR limit as it is
+    // (DESIGN.md 5a): 48 scalar spills in the flagship instantiation against 11 this way (the grid launch had 3).
+    ProbeArgsK *ak = reinterpret_cast<ProbeArgsK *>(reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()));
+    asm volatile("" : "+s"(ak));
+    probe_even_item<BLOCK, U, LONGCAP, SHARD, SIGNED, ACC8, MERGE>(*ak, tile, v0, v1, own_tile, first);
   }
 }
 

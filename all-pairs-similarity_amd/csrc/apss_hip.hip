@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
 #include <string>
 #include <vector>
@@ -77,6 +78,9 @@ struct DebugCfg {
   int merge_u = 0;             // merge_u=U      ... as long as the merged round fits a window of U steps (default 7)
   int merge_single = 0;        // merge_single=U ... and a single row's round takes a window of at most U steps (default 4)
   bool no_fused_ingest = false; // no_fused_ingest a plain batch is ingested by k_ingest_count + k_ingest_write too (never the one-pass k_ingest_plain)
+  bool no_persist = false;     // no_persist     k_probe_even launches one workgroup per (tile, chunk) cell, never resident workgroups over a work list
+  int persist_wgs = 0;         // persist_wgs=N  ... the persistent launch has N workgroups (default: as many as the chip holds at a time)
+  int persist_fine = 0;        // persist_fine=R ... and the last items of its list are R rounds long (a power of two; default kPersistFine)
 };
 
 DebugCfg parse_debug_env() {
@@ -133,6 +137,9 @@ DebugCfg parse_debug_env() {
     else if (key == "no_merge_prune") d.no_merge_prune = val != 0;
     else if (key == "merge_single") d.merge_single = (int)val;
     else if (key == "no_fused_ingest") d.no_fused_ingest = val != 0;
+    else if (key == "no_persist") d.no_persist = val != 0;
+    else if (key == "persist_wgs") d.persist_wgs = val;
+    else if (key == "persist_fine") d.persist_fine = val;
     else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
@@ -312,6 +319,16 @@ struct apss_handle {
   DevBuf<uint32_t> row_pairs;  // [nq]
   apss_topk_tile_cut_info tci{};
   int64_t probe_reruns = 0;    // probes that ran again because a list overflowed, since create
+  // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
+  // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
+  std::vector<apss::WorkListKey> wl_keys;
+  std::vector<int64_t> wl_off, wl_fine;  // [launches + 1] first item of every launch's list; [launches] its cut pieces
+  apss::ProbeItem *wl_pin = nullptr;
+  size_t wl_pin_cap = 0;
+  DevBuf<apss::ProbeItem> wl_dev;
+  hipEvent_t wl_ev = nullptr;            // the last upload out of wl_pin
+  std::map<const void *, int> wl_per_cu;
+  int n_cus = 0;
   // stats
   apss_stats st{};
   size_t bytes_reserved = 0;
@@ -1668,8 +1685,42 @@ bool cx_variant_exists(const CxVariant &v) {
   return false;
 }
 
-int32_t launch_cx(apss_handle *h, const CxVariant &v, const ProbeArgs &a) {
-  const dim3 grid((unsigned)((int64_t)a.n_tiles * a.n_chunks));
+// the k_probe_even / k_probe_even_merged instantiation of a variant (null: none)
+const void *even_kernel(const CxVariant &v) {
+  if (v.even && v.merge) {
+#define X(U, A8) \
+    if (v.block == 512 && v.u == U && v.acc8 == A8) return reinterpret_cast<const void *>(&k_probe_even_merged<U, A8>);
+    APSS_EVEN_MERGE_VARIANTS(X)
+#undef X
+  } else if (v.even) {
+#define X(B, U, SH, SG, A8) \
+    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8) \
+      return reinterpret_cast<const void *>(&k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>);
+    APSS_EVEN_VARIANTS(X)
+#undef X
+  }
+  return nullptr;
+}
+
+// workgroups of a k_probe_even instantiation that the chip holds at a time: the occupancy query (the kernels' LDS is static,
+// so the query sees it: two per CU for the 512-thread ones, one for the 1024-thread ones) x the CUs; asked once per instantiation
+int32_t even_resident_slots(apss_handle *h, const CxVariant &v, int *slots) {
+  const void *kern = even_kernel(v);
+  if (!kern) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
+  if (h->n_cus == 0) HIPCHK(h, hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->dev));
+  auto it = h->wl_per_cu.find(kern);
+  if (it == h->wl_per_cu.end()) {
+    int per_cu = 0;
+    HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, v.block, (size_t)h->dbgcfg.pad_lds));
+    it = h->wl_per_cu.emplace(kern, std::max(per_cu, 1)).first;
+  }
+  *slots = it->second * h->n_cus;
+  return APSS_OK;
+}
+
+// persist_wgs > 0 (k_probe_even only): a.items holds the launch's work list and that many workgroups take its items
+int32_t launch_cx(apss_handle *h, const CxVariant &v, const ProbeArgs &a, int64_t persist_wgs = 0) {
+  const dim3 grid((unsigned)(persist_wgs > 0 ? persist_wgs : (int64_t)a.n_tiles * a.n_chunks));
   if (v.even && v.merge) {
 #define X(U, A8)                                                                                                           \
     if (v.block == 512 && v.u == U && v.acc8 == A8) {                                                                      \
@@ -2256,7 +2307,10 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   int64_t want_chunks = 1024;
   if (h->idx_rows > 0) {
     const int64_t tiles_now = std::max<int64_t>(1, ceil_div(h->idx_rows, h->use_coarse ? h->cx.cb : h->ex.cb));
-    // (eight workgroups per resident slot: with four, the last, partly filled wave of workgroups cost a fifth of the launch)
+    // (eight workgroups per resident slot: with four, the last, partly filled wave of workgroups cost a fifth of the launch.
+    // That was the grid launch, which k_probe_coarse, k_probe_wave and k_probe keep.  k_probe_even's launch is persistent --
+    // resident workgroups over a work list of these (tile, chunk) cells, the last ones cut finer: see `persist` below -- and a
+    // chunk there is the unit a workgroup's set-up is paid for, no longer the unit the end of the launch is ragged by.)
     want_chunks = std::min<int64_t>(1024, std::max<int64_t>(ceil_div(4096, tiles_now), ceil_div(nq, 256)));
   }
   if (dbg.chunks > 0) want_chunks = dbg.chunks;
@@ -2439,6 +2493,63 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   const bool chain = coarse_path && !h->sharded && !hybrid && !tri && nq <= kChainMaxQueries && !dbg.no_chain;
   const int64_t chain_tail_pairs = chain ? nq * tail_n : 0;
   if (chain) APSS_TRY(ensure(h, h->chain_ctr, kCtrCount));
+  // ---- k_probe_even: PERSISTENT launches (apss_even.hpp, apss_worklist.hpp).  One work list per launch of the call, built
+  // here, one behind the other, and kept in the handle with their keys: a call whose launches have the keys of the last
+  // call's (a join repeated, a stream of equal batches) uploads nothing.  The lists go up asynchronously from pinned memory.
+  // (A list of millions of cells -- a join of tens of millions of rows in small chunks -- is not worth its upload: grid launch.)
+  constexpr int kPersistFine = 128;  // rounds per item at the end of a list (profiles/persist_filter.md has the sweep)
+  constexpr int64_t kPersistMaxCells = 1LL << 22;
+  int persist_slots = 0;
+  const bool persist = coarse_path && cxv.even && !dbg.no_persist && total_tiles > 0 && total_tiles * (int64_t)a.n_chunks <= kPersistMaxCells;
+  if (persist) {
+    APSS_TRY(even_resident_slots(h, cxv, &persist_slots));
+    int fine = 1;
+    while (2 * fine <= (dbg.persist_fine > 0 ? dbg.persist_fine : kPersistFine)) fine *= 2;
+    std::vector<apss::WorkListKey> keys;
+    for (int64_t t0 = 0; t0 < total_tiles; t0 += tiles_per_launch) {
+      apss::WorkListKey k;
+      k.q_slot_base = a.merge_log2 > 0 ? q_slot_base : -1;  // (decides own_tile, which only merged launches have)
+      k.nq = a.nq;
+      k.nq_rows = a.nq_rows;
+      k.q_chunk = a.q_chunk;
+      k.n_chunks = a.n_chunks;
+      k.cb = a.cb;
+      k.tri = a.tri;
+      k.merge_log2 = a.merge_log2;
+      k.tile0 = (int32_t)t0;
+      k.n_tiles = (int32_t)std::min<int64_t>(tiles_per_launch, total_tiles - t0);
+      k.fine = fine;
+      k.slots = dbg.persist_wgs > 0 ? dbg.persist_wgs : persist_slots;
+      keys.push_back(k);
+    }
+    if (!(keys == h->wl_keys) || !h->wl_dev.p) {
+      std::vector<apss::ProbeItem> items;
+      h->wl_keys.clear();  // (nothing is cached while this fails half way)
+      h->wl_off.assign(1, 0);
+      h->wl_fine.clear();
+      for (const apss::WorkListKey &k : keys) {
+        h->wl_fine.push_back(apss::build_work_list(k, items));
+        h->wl_off.push_back((int64_t)items.size());
+      }
+      if (!h->wl_ev) HIPCHK(h, hipEventCreateWithFlags(&h->wl_ev, hipEventDisableTiming));
+      else HIPCHK(h, hipEventSynchronize(h->wl_ev));  // the last upload has left the pinned buffer
+      if (items.size() > h->wl_pin_cap) {
+        if (h->wl_pin) (void)hipHostFree(h->wl_pin);
+        h->wl_pin = nullptr;
+        h->wl_pin_cap = 0;
+        const size_t cap = std::max<size_t>(items.size() + items.size() / 2, 4096);
+        HIPCHK(h, hipHostMalloc((void **)&h->wl_pin, cap * sizeof(apss::ProbeItem), hipHostMallocDefault));
+        h->wl_pin_cap = cap;
+      }
+      APSS_TRY(ensure(h, h->wl_dev, std::max<size_t>(items.size(), 1)));
+      if (!items.empty()) {
+        std::memcpy(h->wl_pin, items.data(), items.size() * sizeof(apss::ProbeItem));
+        HIPCHK(h, hipMemcpyAsync(h->wl_dev.p, h->wl_pin, items.size() * sizeof(apss::ProbeItem), hipMemcpyHostToDevice, h->stream));
+      }
+      HIPCHK(h, hipEventRecord(h->wl_ev, h->stream));
+      h->wl_keys = keys;
+    }
+  }
   for (int attempt = 0; attempt < 3; ++attempt) {
     if (chain) {  // (room for everything the candidate list can hold + every (query, waiting row) pair)
       // (sized for the longest tail there can be, once: the tail grows by a row per message)
@@ -2481,7 +2592,20 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     for (int64_t t0 = 0; t0 < total_tiles; t0 += tiles_per_launch, ++n_launches) {
       a.tile0 = (int32_t)t0;
       a.n_tiles = (int32_t)std::min<int64_t>(tiles_per_launch, total_tiles - t0);
-      if (coarse_path) {
+      if (coarse_path && persist) {
+        // (the work counter is zero behind the memset above; a later launch of the call starts it again)
+        if (n_launches > 0) HIPCHK(h, hipMemsetAsync(h->counters.p + kCtrWork, 0, sizeof(unsigned long long), h->stream));
+        const int64_t n_items = h->wl_off[n_launches + 1] - h->wl_off[n_launches];
+        a.items = h->wl_dev.p + h->wl_off[n_launches];
+        a.n_items = (int32_t)n_items;
+        a.work_ctr = h->counters.p + kCtrWork;
+        // never more workgroups than items
+        const int64_t wgs = std::min<int64_t>(n_items, dbg.persist_wgs > 0 ? dbg.persist_wgs : persist_slots);
+        if (dbg.diag)
+          fprintf(stderr, "[apss diag] persist: items %lld fine %lld workgroups %lld\n", (long long)n_items, (long long)h->wl_fine[n_launches], (long long)wgs);
+        if (wgs > 0) APSS_TRY(launch_cx(h, cxv, a, wgs));
+        thin_launches += 1;
+      } else if (coarse_path) {
         APSS_TRY(launch_cx(h, cxv, a));
         thin_launches += cxv.even ? 1 : 0;
       } else if (wave_path && dbg.diag) {
@@ -2575,9 +2699,9 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
       HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    unsigned long long cc_stack[kCtrCount] = {0, 0, 0, 0, 0, 0, 0, 0}, c_stack[kCtrCount];
-    unsigned long long *cc = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 64) : cc_stack;
-    unsigned long long *c = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 128) : c_stack;
+    unsigned long long cc_stack[kCtrCount] = {}, c_stack[kCtrCount];
+    unsigned long long *cc = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 128) : cc_stack;
+    unsigned long long *c = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 256) : c_stack;
     for (int k = 0; k < kCtrCount; ++k) cc[k] = 0;
     if (chain) {
       HIPCHK(h, hipMemsetAsync(h->chain_ctr.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
@@ -3217,6 +3341,9 @@ void apss_destroy(apss_handle *h) {
   release(h->win_df); release(h->win_b); release(h->win_q); release(h->win_c); release(h->win_s);
   release(h->row_pairs);
   if (h->pin) (void)hipHostFree(h->pin);
+  release(h->wl_dev);
+  if (h->wl_pin) (void)hipHostFree(h->wl_pin);
+  if (h->wl_ev) (void)hipEventDestroy(h->wl_ev);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);

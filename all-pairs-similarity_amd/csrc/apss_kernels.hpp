@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "apss_topk_key.hpp"
+#include "apss_worklist.hpp"
 
 namespace apss {
 
@@ -51,7 +52,8 @@ constexpr int kUnmergedBit = 0x40000000;
 // kCtrPre: the rounds the filter reported before k_expand_merged turned them into pairs; kCtrOver: the list capacity that
 // k_expand_merged / k_shard_prune would have needed when their INPUT list had overflowed (a maximum, in a counter of its own:
 // added to kCtrResults it would shift the slots the kernels hand out, and the list's first `cap` entries would stay unwritten)
-enum Counter { kCtrResults = 0, kCtrVisits = 1, kCtrCands = 2, kCtrFlags = 3, kCtrDevVisits = 4, kCtrSnap = 5, kCtrPre = 6, kCtrOver = 7, kCtrCount = 8 };
+// kCtrWork: the next item of a persistent filter launch's work list (apss_worklist.hpp); zero before every launch
+enum Counter { kCtrResults = 0, kCtrVisits = 1, kCtrCands = 2, kCtrFlags = 3, kCtrDevVisits = 4, kCtrSnap = 5, kCtrPre = 6, kCtrOver = 7, kCtrWork = 8, kCtrCount = 9 };
 
 // ---------------------------------------------------------------------------------------------------------
 // wavefront ballot / prefix-sum compaction: every active lane with `pred` gets a distinct slot of a global list
@@ -1194,6 +1196,11 @@ struct ProbeArgs {
   // per-round cut of the theta <= 0 emission (k_probe<2, .., CUT = true>; apss_set_top_k_tile_cut), null / 0 when off
   uint32_t *row_pairs;           // [nq] uncut pairs >= theta per query row, summed over the tiles
   int32_t cut_k;
+  // persistent launch of k_probe_even / k_probe_even_merged (apss_worklist.hpp): the launch's work items and the counter its
+  // workgroups take them through; items null: the grid launch, workgroup b runs the cell (tile0 + b / n_chunks, b % n_chunks)
+  int32_t n_items;
+  const ProbeItem *items;
+  unsigned long long *work_ctr;
 };
 
 // dynamic-LDS carve (all offsets multiples of 16 B)
