@@ -34,6 +34,38 @@ struct DevBuf {
   size_t cap = 0;  // elements
 };
 
+// A list of (query row, candidate, score) pairs: three arrays that grow, swap and go together, so they share one capacity
+struct PairList {
+  DevBuf<int32_t> q, c;
+  DevBuf<float> s;
+  size_t cap() const { return q.cap; }
+  int32_t ensure(apss_handle *h, size_t n, size_t keep = 0, bool exact = false);  // (grow-only, as the arrays' own ensure)
+  void release();
+  void swap(PairList &o) {
+    std::swap(q, o.q);
+    std::swap(c, o.c);
+    std::swap(s, o.s);
+  }
+  // where the filters append (the capacity they may fill is the site's to say)
+  void as_candidates(ProbeArgs &a) const {
+    a.res_q = q.p;
+    a.res_c = c.p;
+    a.res_s = s.p;
+  }
+  void as_in(ShardPruneArgs &x) const {
+    x.in_q = q.p;
+    x.in_c = c.p;
+    x.in_s = s.p;
+  }
+  // the out_* fields of a kernel's arguments, or of the handle (where the last call's results live)
+  template <class A>
+  void as_out(A &x) const {
+    x.out_q = q.p;
+    x.out_c = c.p;
+    x.out_s = s.p;
+  }
+};
+
 // Test and experiment hooks: ONE environment word, APSS_DEBUG, read once when a handle is created -- a comma-separated
 // list of the tokens below.  Nothing else in the library reads the environment.
 struct DebugCfg {
@@ -237,11 +269,10 @@ struct apss_handle {
   DevBuf<int32_t> vq_first, vrow_q;  // virtual-row table of the last query batch (queries of > 512 terms)
   DevBuf<int64_t> vrow_ptr, vrow_np, vrow_first;
   // results of the last query-type call
-  DevBuf<int32_t> res_q, res_c, fin_q, fin_c;
-  DevBuf<float> res_s, fin_s;
-  DevBuf<int32_t> res2_q, res2_c;    // merged rounds (k_expand_merged): the second candidate list, swapped with res_* after the expansion
-  DevBuf<float> res2_s, q_prenorm;   // ... and the staged query weights divided by their rows' shard factors
-  const int32_t *out_q = nullptr, *out_c = nullptr;  // where the last call's results live (res_* or fin_*)
+  PairList res, fin;          // the filters' candidates; the exact pass's final list
+  PairList res2;              // merged rounds (k_expand_merged): the second candidate list, swapped with res after the expansion
+  DevBuf<float> q_prenorm;    // ... and the staged query weights divided by their rows' shard factors
+  const int32_t *out_q = nullptr, *out_c = nullptr;  // where the last call's results live (res or fin)
   const float *out_s = nullptr;
   int64_t n_res = -1;
   const int64_t *res_q_ext = nullptr;      // ext ids of the last query batch (device)
@@ -292,8 +323,7 @@ struct apss_handle {
   DevBuf<unsigned int> head_ovf;      // [1] set by k_head_pack if an element ever exceeded 127 (cannot happen: checked, an error)
   DevBuf<uint32_t> df;
   DevBuf<unsigned long long> dedup_tab, head_ctr;
-  DevBuf<int32_t> uq_q, uq_c;         // candidate list after k_pair_dedup
-  DevBuf<float> uq_s;
+  PairList uq;                        // candidate list after k_pair_dedup
   int64_t head_nonempty = 0, last_batch_head_nonempty = 0;
   double head_sample_frac = 0.0;      // fraction of sampled pairs the dense filter passed when the policy last looked
   hipEvent_t ev2 = nullptr, ev3 = nullptr;
@@ -306,8 +336,7 @@ struct apss_handle {
   int64_t top_k_window = 0;
   DevBuf<unsigned int> win_df;  // [dim] exact term counts of the store, recomputed at every windowed call
   DevBuf<int32_t> win_b;        // [nq] b(q), and behind it [nq] the rows' non-empty bits (stored batch of a handle with a head)
-  DevBuf<int32_t> win_q, win_c;
-  DevBuf<float> win_s;
+  PairList win;
   std::vector<int64_t> win_cuts;
   apss_topk_window_info tw{};
   // a windowed call's self-touch corrections: non-empty rows of the window being probed (-1: not in a window)
@@ -381,6 +410,17 @@ void release(DevBuf<T> &b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.cap = 0;
+}
+
+int32_t PairList::ensure(apss_handle *h, size_t n, size_t keep, bool exact) {
+  APSS_TRY(::ensure(h, q, n, keep, exact));
+  APSS_TRY(::ensure(h, c, n, keep, exact));
+  return ::ensure(h, s, n, keep, exact);
+}
+void PairList::release() {
+  ::release(q);
+  ::release(c);
+  ::release(s);
 }
 
 int32_t enter(apss_handle *h) {
@@ -1299,6 +1339,58 @@ int32_t head_pack_store(apss_handle *h, int64_t row0) {
 int32_t run_head(apss_handle *h, const ProbeArgs &a, int64_t nq, int64_t q_slot_base, const uint16_t *Wq, int64_t wq_rows,
                  float thr, double bound, int64_t n_cand);
 
+// a query batch resident on the device: CSR rows (absolute offsets into idx / val) and their external ids
+struct QueryRows {
+  int64_t nq;
+  const int64_t *rowptr;
+  const int32_t *idx;
+  const float *val;
+  const int64_t *ext;
+};
+
+// k_rescore's arguments: the pairs (cand_q, cand_c) of query rows and store slots are re-scored from the fp32 store, and those
+// that reach theta go to h->fin, counted at out_count.  n_pairs_dev (chained launch): the pair count is read on the device
+RescoreArgs rescore_args(const apss_handle *h, const int32_t *cand_q, const int32_t *cand_c, int64_t n_pairs, const unsigned long long *n_pairs_dev,
+                         const QueryRows &q, float theta, unsigned long long *out_count) {
+  RescoreArgs r{};
+  r.n_pairs = n_pairs;
+  r.n_pairs_dev = n_pairs_dev;
+  r.q_row = cand_q;
+  r.c_slot = cand_c;
+  r.q_rowptr = q.rowptr;
+  r.q_idx = q.idx;
+  r.q_val = q.val;
+  r.c_rowptr = h->rowptr.p;
+  r.c_idx = h->idx.p;
+  r.c_val = h->val.p;
+  r.theta = theta;
+  h->fin.as_out(r);
+  r.out_count = out_count;
+  return r;
+}
+inline dim3 rescore_grid(int64_t pairs) { return dim3((unsigned)std::max<int64_t>(1, ceil_div(pairs, (int64_t)kRescorePairs * kRescoreTrips))); }
+
+// k_tail_score's arguments: every (query, waiting row) pair, exactly; appended to h->fin behind its first out_base pairs
+TailArgs tail_args(const apss_handle *h, const QueryRows &q, int64_t tail_n, float theta, int64_t out_base, unsigned long long *counters) {
+  TailArgs t{};
+  t.nq = q.nq;
+  t.n_tail = tail_n;
+  t.q_rowptr = q.rowptr;
+  t.q_idx = q.idx;
+  t.q_val = q.val;
+  t.q_ext = q.ext;
+  t.c_rowptr = h->rowptr.p;
+  t.c_idx = h->idx.p;
+  t.c_val = h->val.p;
+  t.c_ext = h->ext.p;
+  t.tail0 = h->idx_rows;
+  t.theta = theta;
+  h->fin.as_out(t);
+  t.out_base = out_base;
+  t.counters = counters;
+  return t;
+}
+
 // How selective is the dense filter on THIS data: the block's first rows (at most 8192) against its first 512 as queries,
 // stored and re-scored.  Returns the fraction of (q, c != q) elements the filter passes that do NOT reach theta.  (Rows arrive in no
 // particular order in the reference's stream -- ShardRegion routing is random, CommonUtils.scala:28-40 -- so a prefix is a
@@ -1338,14 +1430,10 @@ int32_t head_sample_selectivity(apss_handle *h, double *frac) {
   // pair that reaches theta is a survivor of every filter (the sample of a batch with planted near-duplicates holds 3e-5 of
   // them: counted against the block they vetoed a head that halves the step of C3 with Zipf(0.5) terms)
   constexpr size_t kSampleCap = 1 << 20;
-  APSS_TRY(ensure(h, h->res_q, kSampleCap));
-  APSS_TRY(ensure(h, h->res_c, kSampleCap));
-  APSS_TRY(ensure(h, h->res_s, kSampleCap));
+  APSS_TRY(h->res.ensure(h, kSampleCap));
   ProbeArgs a{};
   a.q_ext = h->ext.p;
-  a.res_q = h->res_q.p;
-  a.res_c = h->res_c.p;
-  a.res_s = h->res_s.p;
+  h->res.as_candidates(a);
   a.res_cap = kSampleCap;
   a.counters = h->head_ctr.p + 2;
   const double bound = (double)h->store_max_norm2 * 1.0001 + 1e-6;  // |q||c| <= the largest squared row norm
@@ -1356,26 +1444,11 @@ int32_t head_sample_selectivity(apss_handle *h, double *frac) {
   const double pairs = (double)Q * (double)S - (double)Q;
   unsigned long long n_true = 0;
   if (c[2] > 0 && c[2] <= kSampleCap) {
-    APSS_TRY(ensure(h, h->fin_q, (size_t)c[2]));
-    APSS_TRY(ensure(h, h->fin_c, (size_t)c[2]));
-    APSS_TRY(ensure(h, h->fin_s, (size_t)c[2]));
+    APSS_TRY(h->fin.ensure(h, (size_t)c[2]));
     HIPCHK(h, hipMemsetAsync(h->head_ctr.p, 0, sizeof(unsigned long long), h->stream));
-    RescoreArgs r{};
-    r.n_pairs = (int64_t)c[2];
-    r.q_row = h->res_q.p;
-    r.c_slot = h->res_c.p;
-    r.q_rowptr = h->rowptr.p;  // (the sample's queries are the store's first rows)
-    r.q_idx = h->idx.p;
-    r.q_val = h->val.p;
-    r.c_rowptr = h->rowptr.p;
-    r.c_idx = h->idx.p;
-    r.c_val = h->val.p;
-    r.theta = (float)h->cfg.theta;
-    r.out_q = h->fin_q.p;
-    r.out_c = h->fin_c.p;
-    r.out_s = h->fin_s.p;
-    r.out_count = h->head_ctr.p;
-    hipLaunchKernelGGL(k_rescore, dim3((unsigned)std::max<int64_t>(1, ceil_div(r.n_pairs, (int64_t)kRescorePairs * kRescoreTrips))), dim3(kRescoreBlock), 0, h->stream, r);
+    // (the sample's queries are the store's first rows)
+    const RescoreArgs r = rescore_args(h, h->res.q.p, h->res.c.p, (int64_t)c[2], nullptr, QueryRows{S, h->rowptr.p, h->idx.p, h->val.p, h->ext.p}, (float)h->cfg.theta, h->head_ctr.p);
+    hipLaunchKernelGGL(k_rescore, rescore_grid(r.n_pairs), dim3(kRescoreBlock), 0, h->stream, r);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(&n_true, h->head_ctr.p, sizeof(n_true), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1565,13 +1638,47 @@ int32_t build_index(apss_handle *h, int64_t row0) {
   return APSS_OK;
 }
 
-template <int MODE, bool FX, int BLOCK = kProbeBlock, bool CUT = false>
-int32_t launch_probe(apss_handle *h, const ProbeArgs &a, size_t lds) {
-  auto kern = k_probe<MODE, BLOCK, FX, CUT>;
-  HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)a.n_tiles * a.n_chunks)), dim3(BLOCK), lds, h->stream, a);
+// An instantiation of a probe kernel (every one takes ProbeArgs as its one argument): its address and its workgroup size.
+// Enough to ask for its occupancy, to set its attributes and to launch it; fn == null: no such instantiation
+struct KernelRef {
+  const void *fn;
+  int block;
+};
+template <class F>
+const void *kernel_addr(F *f) { return reinterpret_cast<const void *>(f); }
+
+int32_t launch_ref(apss_handle *h, const KernelRef &k, dim3 grid, size_t lds, const ProbeArgs &a) {
+  void *args[] = {const_cast<ProbeArgs *>(&a)};
+  (void)hipLaunchKernel(k.fn, grid, dim3(k.block), args, lds, h->stream);
   HIPCHK(h, hipGetLastError());
   return APSS_OK;
+}
+
+// the general kernel k_probe<MODE, BLOCK, FX, CUT>: theta > 0 with 1024 threads; theta <= 0 with either block, with or without
+// the per-round cut
+template <int MODE, int BLOCK, bool CUT>
+KernelRef gen_ref(bool fx) { return {fx ? kernel_addr(&k_probe<MODE, BLOCK, true, CUT>) : kernel_addr(&k_probe<MODE, BLOCK, false, CUT>), BLOCK}; }
+KernelRef gen_kernel(int mode, int block, bool fx, bool cut) {
+  if (mode == 0 && block == kProbeBlock && !cut) return gen_ref<0, kProbeBlock, false>(fx);
+  if (mode == 1 && block == kProbeBlock && !cut) return gen_ref<1, kProbeBlock, false>(fx);
+  if (mode == 2 && block == kProbeBlock) return cut ? gen_ref<2, kProbeBlock, true>(fx) : gen_ref<2, kProbeBlock, false>(fx);
+  if (mode == 2 && block == 512) return cut ? gen_ref<2, 512, true>(fx) : gen_ref<2, 512, false>(fx);
+  return {nullptr, 0};
+}
+// the single-pass exact kernel k_probe_wave: shapes A (8 waves x 64-chunk window) and C (8 waves x 40-chunk window)
+template <int U, int LC, int SC>
+KernelRef wave_ref(bool sharded, bool diag) {
+  if (sharded) return {diag ? kernel_addr(&k_probe_wave<512, U, LC, SC, true, true>) : kernel_addr(&k_probe_wave<512, U, LC, SC, true, false>), 512};
+  return {diag ? kernel_addr(&k_probe_wave<512, U, LC, SC, false, true>) : kernel_addr(&k_probe_wave<512, U, LC, SC, false, false>), 512};
+}
+KernelRef wave_kernel(char variant, bool sharded, bool diag) {
+  return variant == 'A' ? wave_ref<8, 256, 1024>(sharded, diag) : wave_ref<5, 128, 512>(sharded, diag);
+}
+// k_probe / k_probe_wave keep their LDS in a dynamic array: one workgroup per (tile, chunk) cell
+int32_t launch_exact(apss_handle *h, const KernelRef &k, const ProbeArgs &a, size_t lds) {
+  if (!k.fn) return fail(h, APSS_E_UNSUPPORTED, "no probe kernel for this combination of options");
+  HIPCHK(h, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return launch_ref(h, k, dim3((unsigned)((int64_t)a.n_tiles * a.n_chunks)), lds, a);
 }
 // theta <= 0 (every touched candidate is an answer): the round is a chain of barriers and latencies (SQ counters, round 4:
 // 73 % of the wave-cycles waiting, LDS issue 0.39, VALU 0.34), and the 1024-thread workgroup over a 16384-row tile holds 93 KB
@@ -1661,51 +1768,38 @@ struct CxVariant {
   X(7, false) X(6, false) X(5, false) X(4, false) X(3, false) X(2, false) \
   X(7, true) X(6, true) X(5, true) X(4, true) X(3, true) X(2, true)
 
-bool cx_variant_exists(const CxVariant &v) {
+// THE lookup: the instantiation of a variant (fn == null: not listed).  The only walk of the three tables
+KernelRef cx_kernel(const CxVariant &v) {
+  const bool even_shape = v.chunk == 16 && !v.vrows && !v.longpf;  // (what every k_probe_even is built for)
   if (v.even && v.merge) {
 #define X(U, A8) \
-    if (v.block == 512 && v.u == U && v.shard && !v.sgn && v.acc8 == A8) return v.chunk == 16 && !v.vrows && !v.longpf;
+    if (v.block == 512 && v.u == U && v.shard && !v.sgn && v.acc8 == A8 && even_shape) return {kernel_addr(&k_probe_even_merged<U, A8>), 512};
     APSS_EVEN_MERGE_VARIANTS(X)
 #undef X
-    return false;
+    return {nullptr, 0};
   }
   if (v.even) {
 #define X(B, U, SH, SG, A8) \
-    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8) return v.chunk == 16 && !v.vrows && !v.longpf;
+    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8 && even_shape) \
+      return {kernel_addr(&k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>), B};
     APSS_EVEN_VARIANTS(X)
 #undef X
-    return false;
+    return {nullptr, 0};
   }
 #define X(B, U, SH, CH, VR, SG, LP, A8)                                                                                 \
   if (v.block == B && v.u == U && v.shard == SH && v.chunk == CH && v.vrows == VR && v.sgn == SG && v.longpf == LP &&   \
       v.acc8 == A8)                                                                                                     \
-    return true;
+    return {kernel_addr(&k_probe_coarse<B, U, (B <= 512 ? 128 : 256), (B <= 512 ? 512 : 1024), SH, CH, VR, SG, LP, A8>), B};
   APSS_CX_VARIANTS(X)
 #undef X
-  return false;
+  return {nullptr, 0};
 }
-
-// the k_probe_even / k_probe_even_merged instantiation of a variant (null: none)
-const void *even_kernel(const CxVariant &v) {
-  if (v.even && v.merge) {
-#define X(U, A8) \
-    if (v.block == 512 && v.u == U && v.acc8 == A8) return reinterpret_cast<const void *>(&k_probe_even_merged<U, A8>);
-    APSS_EVEN_MERGE_VARIANTS(X)
-#undef X
-  } else if (v.even) {
-#define X(B, U, SH, SG, A8) \
-    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8) \
-      return reinterpret_cast<const void *>(&k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>);
-    APSS_EVEN_VARIANTS(X)
-#undef X
-  }
-  return nullptr;
-}
+inline bool cx_variant_exists(const CxVariant &v) { return cx_kernel(v).fn != nullptr; }
 
 // workgroups of a k_probe_even instantiation that the chip holds at a time: the occupancy query (the kernels' LDS is static,
 // so the query sees it: two per CU for the 512-thread ones, one for the 1024-thread ones) x the CUs; asked once per instantiation
 int32_t even_resident_slots(apss_handle *h, const CxVariant &v, int *slots) {
-  const void *kern = even_kernel(v);
+  const void *kern = v.even ? cx_kernel(v).fn : nullptr;
   if (!kern) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
   if (h->n_cus == 0) HIPCHK(h, hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->dev));
   auto it = h->wl_per_cu.find(kern);
@@ -1719,42 +1813,12 @@ int32_t even_resident_slots(apss_handle *h, const CxVariant &v, int *slots) {
 }
 
 // persist_wgs > 0 (k_probe_even only): a.items holds the launch's work list and that many workgroups take its items
+// (the filter kernels keep their LDS in static arrays: the dynamic bytes are pad_lds's experiment, on k_probe_even alone)
 int32_t launch_cx(apss_handle *h, const CxVariant &v, const ProbeArgs &a, int64_t persist_wgs = 0) {
+  const KernelRef k = cx_kernel(v);
+  if (!k.fn) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
   const dim3 grid((unsigned)(persist_wgs > 0 ? persist_wgs : (int64_t)a.n_tiles * a.n_chunks));
-  if (v.even && v.merge) {
-#define X(U, A8)                                                                                                           \
-    if (v.block == 512 && v.u == U && v.acc8 == A8) {                                                                      \
-      hipLaunchKernelGGL((k_probe_even_merged<U, A8>), grid, dim3(512), (size_t)h->dbgcfg.pad_lds, h->stream, a);           \
-      HIPCHK(h, hipGetLastError());                                                                                        \
-      return APSS_OK;                                                                                                      \
-    }
-    APSS_EVEN_MERGE_VARIANTS(X)
-#undef X
-    return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
-  }
-  if (v.even) {
-#define X(B, U, SH, SG, A8)                                                                                                \
-    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8) {                                        \
-      hipLaunchKernelGGL((k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>), grid, dim3(B),                          \
-                         (size_t)h->dbgcfg.pad_lds, h->stream, a);                                                                                 \
-      HIPCHK(h, hipGetLastError());                                                                                        \
-      return APSS_OK;                                                                                                      \
-    }
-    APSS_EVEN_VARIANTS(X)
-#undef X
-    return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
-  }
-#define X(B, U, SH, CH, VR, SG, LP, A8)                                                                                    \
-  if (v.block == B && v.u == U && v.shard == SH && v.chunk == CH && v.vrows == VR && v.sgn == SG && v.longpf == LP &&      \
-      v.acc8 == A8) {                                                                                                      \
-    hipLaunchKernelGGL((k_probe_coarse<B, U, (B <= 512 ? 128 : 256), (B <= 512 ? 512 : 1024), SH, CH, VR, SG, LP, A8>), grid, dim3(B), \
-                       0, h->stream, a);                                                                                   \
-    HIPCHK(h, hipGetLastError());                                                                                          \
-    return APSS_OK;                                                                                                        \
-  }
-  APSS_CX_VARIANTS(X)
-#undef X
-  return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
+  return launch_ref(h, k, grid, v.even ? (size_t)h->dbgcfg.pad_lds : 0, a);
 }
 
 // ---- dense-head filter of one query batch (apss_head.hpp): appends its candidates to the sparse filter's list ----
@@ -2022,66 +2086,43 @@ int32_t cut_long_queries(apss_handle *h, const int64_t *s_rowptr, int64_t nq, in
   return APSS_OK;
 }
 
-// The exact pass of the two-pass join: the filters' survivors (h->res_*, h->n_res of them; with a dense-head block a pair may
+// The exact pass of the two-pass join: the filters' survivors (h->res, h->n_res of them; with a dense-head block a pair may
 // be there twice) are re-scored from the fp32 store and pruned at theta (k_rescore); then the rows that still wait outside the
-// index are scored against every query, pair by pair (k_tail_score).  Leaves the final list in h->fin_* / h->n_res.
-int32_t exact_pass(apss_handle *h, bool hybrid, double theta, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx,
-                   const float *q_val, const int64_t *q_ext, int64_t tail_n) {
+// index are scored against every query, pair by pair (k_tail_score).  Leaves the final list in h->fin / h->n_res.
+int32_t exact_pass(apss_handle *h, bool hybrid, double theta, const QueryRows &q, int64_t tail_n) {
   float ms = 0.f;
   // exact pass: re-score what the filter(s) let through from the fp32 store and prune at theta
   int64_t n_cand = h->n_res;
   h->st.filter_survivors = n_cand;
   h->n_res = 0;
-  const int32_t *cand_q = h->res_q.p, *cand_c = h->res_c.p;
+  const int32_t *cand_q = h->res.q.p, *cand_c = h->res.c.p;
   if (hybrid && n_cand > 0) {
     // a pair that passed both filters is in the list twice
     uint64_t tab = 1024;
     while (tab < (uint64_t)n_cand * 2) tab <<= 1;
     APSS_TRY(ensure(h, h->dedup_tab, (size_t)tab, 0, true));
-    APSS_TRY(ensure(h, h->uq_q, (size_t)n_cand, 0, true));
-    APSS_TRY(ensure(h, h->uq_c, (size_t)n_cand, 0, true));
-    APSS_TRY(ensure(h, h->uq_s, (size_t)n_cand, 0, true));
+    APSS_TRY(h->uq.ensure(h, (size_t)n_cand, 0, true));
     HIPCHK(h, hipMemsetAsync(h->dedup_tab.p, 0xff, (size_t)tab * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, sizeof(unsigned long long), h->stream));
     hipLaunchKernelGGL(k_pair_dedup, dim3((unsigned)ceil_div(n_cand, 256)), dim3(256), 0, h->stream,
-                       (const int32_t *)h->res_q.p, (const int32_t *)h->res_c.p, (const float *)h->res_s.p, n_cand,
-                       h->dedup_tab.p, tab - 1, h->uq_q.p, h->uq_c.p, h->uq_s.p, h->counters.p);
+                       (const int32_t *)h->res.q.p, (const int32_t *)h->res.c.p, (const float *)h->res.s.p, n_cand,
+                       h->dedup_tab.p, tab - 1, h->uq.q.p, h->uq.c.p, h->uq.s.p, h->counters.p);
     HIPCHK(h, hipGetLastError());
     unsigned long long nu = 0;
     HIPCHK(h, hipMemcpyAsync(&nu, h->counters.p, sizeof(nu), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     n_cand = (int64_t)nu;
-    cand_q = h->uq_q.p;
-    cand_c = h->uq_c.p;
+    cand_q = h->uq.q.p;
+    cand_c = h->uq.c.p;
   }
   if (n_cand > 0) {
-    APSS_TRY(ensure(h, h->fin_q, (size_t)n_cand, 0, true));
-    APSS_TRY(ensure(h, h->fin_c, (size_t)n_cand, 0, true));
-    APSS_TRY(ensure(h, h->fin_s, (size_t)n_cand, 0, true));
+    APSS_TRY(h->fin.ensure(h, (size_t)n_cand, 0, true));
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, sizeof(unsigned long long), h->stream));
-    RescoreArgs r{};
-    r.n_pairs = n_cand;
-    r.q_row = cand_q;
-    r.c_slot = cand_c;
-    r.q_rowptr = q_rowptr;
-    r.q_idx = q_idx;
-    r.q_val = q_val;
-    r.c_rowptr = h->rowptr.p;
-    r.c_idx = h->idx.p;
-    r.c_val = h->val.p;
-    r.theta = (float)theta;
-    r.out_q = h->fin_q.p;
-    r.out_c = h->fin_c.p;
-    r.out_s = h->fin_s.p;
-    r.out_count = h->counters.p;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     // (a launch may not have 2^32 threads or more: 16 lanes per pair -> at most 2^27 pairs per launch)
     for (int64_t p0 = 0; p0 < n_cand; p0 += (1LL << 27)) {
-      RescoreArgs rr = r;
-      rr.n_pairs = std::min<int64_t>(1LL << 27, n_cand - p0);
-      rr.q_row = cand_q + p0;
-      rr.c_slot = cand_c + p0;
-      hipLaunchKernelGGL(k_rescore, dim3((unsigned)std::max<int64_t>(1, ceil_div(rr.n_pairs, (int64_t)kRescorePairs * kRescoreTrips))), dim3(kRescoreBlock), 0, h->stream, rr);
+      const RescoreArgs r = rescore_args(h, cand_q + p0, cand_c + p0, std::min<int64_t>(1LL << 27, n_cand - p0), nullptr, q, (float)theta, h->counters.p);
+      hipLaunchKernelGGL(k_rescore, rescore_grid(r.n_pairs), dim3(kRescoreBlock), 0, h->stream, r);
       HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
@@ -2094,29 +2135,10 @@ int32_t exact_pass(apss_handle *h, bool hybrid, double theta, int64_t nq, const 
   }
   if (tail_n > 0) {
     // the rows that wait outside the index: every (query, tail row) pair, exactly (k_tail_score)
-    const int64_t pairs = nq * tail_n;
-    APSS_TRY(ensure(h, h->fin_q, (size_t)(h->n_res + pairs), (size_t)h->n_res));
-    APSS_TRY(ensure(h, h->fin_c, (size_t)(h->n_res + pairs), (size_t)h->n_res));
-    APSS_TRY(ensure(h, h->fin_s, (size_t)(h->n_res + pairs), (size_t)h->n_res));
+    const int64_t pairs = q.nq * tail_n;
+    APSS_TRY(h->fin.ensure(h, (size_t)(h->n_res + pairs), (size_t)h->n_res));
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
-    TailArgs t{};
-    t.nq = nq;
-    t.n_tail = tail_n;
-    t.q_rowptr = q_rowptr;
-    t.q_idx = q_idx;
-    t.q_val = q_val;
-    t.q_ext = q_ext;
-    t.c_rowptr = h->rowptr.p;
-    t.c_idx = h->idx.p;
-    t.c_val = h->val.p;
-    t.c_ext = h->ext.p;
-    t.tail0 = h->idx_rows;
-    t.theta = (float)theta;
-    t.out_q = h->fin_q.p;
-    t.out_c = h->fin_c.p;
-    t.out_s = h->fin_s.p;
-    t.out_base = h->n_res;
-    t.counters = h->counters.p;
+    const TailArgs t = tail_args(h, q, tail_n, (float)theta, h->n_res, h->counters.p);
     hipLaunchKernelGGL(k_tail_score, dim3((unsigned)ceil_div(pairs * kGroup, 256)), dim3(256), 0, h->stream, t);
     HIPCHK(h, hipGetLastError());
     unsigned long long tc[kCtrCount];
@@ -2127,25 +2149,79 @@ int32_t exact_pass(apss_handle *h, bool hybrid, double theta, int64_t nq, const 
     h->st.device_posting_visits += (int64_t)tc[kCtrVisits];
     h->st.candidate_pairs += (int64_t)tc[kCtrCands];
   }
-  h->out_q = h->fin_q.p;
-  h->out_c = h->fin_c.p;
-  h->out_s = h->fin_s.p;
+  h->fin.as_out(*h);
   h->st.result_pairs = h->n_res;
   return APSS_OK;
 }
 
 int32_t pack_query_head(apss_handle *h, const int64_t *rowptr, const int32_t *idx, const float *val, int64_t nq);
 
-// q_slot_first: slot of query row 0 when the batch is rows of the store (self-join, insert-and-query), else -1.
-int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-                    int64_t q_nnz_end, int64_t *n_results) {
-  const DebugCfg &dbg = h->dbgcfg;
-  h->res_q_ext = q_ext;
-  h->last_q_rowptr = q_rowptr;
-  h->last_q_idx = q_idx;
-  h->last_q_val = q_val;
-  h->last_nq = nq;
+// ---- a query-type call over the index: ONE pass (probe_pass) is the stages below, in the order of their device work ----
+constexpr int32_t kProbeAgain = 1;    // a stage latched a downgrade and rebuilt the index: the call runs again from the very top
+constexpr int32_t kAttemptAgain = 2;  // the candidate list was grown: the attempt runs again
+
+// single-pass exact kernels (k_probe_wave, k_probe): which one, its shape, its dynamic LDS
+struct ExactKernel {
+  bool wave, fx, cut;  // k_probe_wave | k_probe with signed fixed point (else fp32 atomics), with the per-round cut
+  char variant;        // k_probe_wave's shape: 'A' | 'C'
+  int block, u, longcap, survcap;
+  size_t lds;
+};
+
+// the rows the SPARSE filter stages (s_*), the longest indexed row, the postings in the inverted index
+struct StagedRows {
+  const int64_t *rowptr;
+  const int32_t *idx;
+  const float *val;
+  int64_t max_nnz, nnz_end;
+  int64_t c_max_nnz, idx_nnz;
+};
+
+// what choose_path decides: the scales and the kernel family
+struct ProbePath {
+  double theta, bound, fx_scale;
+  int mode;
+  bool forced_general;
+  double cx_shared, cx_scale, cx_theta, a8_scale;  // (cx_scale as launched: a8_scale when that is > 0; cx_theta: theta in its units)
+  bool coarse_path, cx_signed, shard_rule, hybrid, head_outside;
+  float head_thr;
+  int64_t tail_n, q_slot_base;
+  const float *q_sub;
+};
+
+// one pass's state: probe_inner's arguments (q_slot_first: slot of query row 0 when the batch is rows of the store, else -1),
+// then what each stage settles for the ones behind it
+struct Probe {
+  QueryRows q;
+  int64_t q_slot_first, q_max_nnz;
+  float q_max_norm2;
+  int64_t q_nnz_end;
+  StagedRows s;
+  ProbePath p;
+  ProbeArgs a;
+  CxVariant cxv;
+  ExactKernel xk;
+  int64_t total_tiles, tiles_per_launch;
+  bool chain, persist;
+  int persist_slots;
+};
+
+// what one attempt's launches count and leave in the counters: read back in one go
+struct AttemptCounts {
+  int64_t n_launches = 0, thin_launches = 0;
+  unsigned long long cc_stack[kCtrCount] = {}, c_stack[kCtrCount];
+  unsigned long long *c, *cc;  // the filter's counters; the chained exact pass's
+  unsigned long long sparse_results = 0, head_c[4] = {0, 0, 0, 0};
+};
+
+inline apss_handle::IndexSet &probe_index(apss_handle *h, const ProbePath &p) { return p.coarse_path ? h->cx : h->ex; }
+
+int32_t reset_call(apss_handle *h, const Probe &pr, int64_t *n_results) {
+  h->res_q_ext = pr.q.ext;
+  h->last_q_rowptr = pr.q.rowptr;
+  h->last_q_idx = pr.q.idx;
+  h->last_q_val = pr.q.val;
+  h->last_nq = pr.q.nq;
   h->n_res = 0;
   h->st.posting_visits = h->st.candidate_pairs = h->st.result_pairs = 0;
   h->st.device_posting_visits = 0;
@@ -2169,52 +2245,60 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   APSS_TRY(ensure(h, h->counters, kCtrCount));
   h->st.filter_survivors = 0;
   h->st.rescore_ms = 0;
-  if (nq == 0 || h->n_rows == 0 || q_nnz_end <= 0 || h->nnz == 0) return APSS_OK;  // nothing can share a term
-  if (nq > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "query batch too large");
+  return APSS_OK;
+}
 
-  // What the SPARSE filter stages: the query rows themselves -- or, on a handle with a dense-head block, their tail view
-  // (the rows without the block's entries; a stored batch's was made when it was indexed, an outside batch's is made here).
-  // Exact rescoring, the waiting rows' direct scoring and apss_partial_scores_dev keep reading the whole rows.
-  const int64_t *s_rowptr = q_rowptr;
-  const int32_t *s_idx = q_idx;
-  const float *s_val = q_val;
-  int64_t s_max_nnz = q_max_nnz, s_nnz_end = q_nnz_end;
+// What the SPARSE filter stages: the query rows themselves -- or, on a handle with a dense-head block, their tail view
+// (the rows without the block's entries; a stored batch's was made when it was indexed, an outside batch's is made here).
+// Exact rescoring, the waiting rows' direct scoring and apss_partial_scores_dev keep reading the whole rows.
+int32_t stage_rows(apss_handle *h, Probe &pr) {
+  StagedRows &s = pr.s;
+  s = StagedRows{pr.q.rowptr, pr.q.idx, pr.q.val, pr.q_max_nnz, pr.q_nnz_end, 0, 0};
   if (h->head_k > 0) {
-    if (q_slot_first >= 0 && q_slot_first < h->idx_rows) {
-      s_rowptr = h->tv.rowptr.p + q_slot_first;
-      s_idx = h->tv.idx.p;
-      s_val = h->tv.val.p;
-      s_max_nnz = h->tv.max_nnz;
-      s_nnz_end = h->tv.nnz;
-    } else {
-      APSS_TRY(build_tail_view(h, h->qtv, q_rowptr, q_idx, q_val, 0, nq, 0, false));
-      s_rowptr = h->qtv.rowptr.p;
-      s_idx = h->qtv.idx.p;
-      s_val = h->qtv.val.p;
-      s_max_nnz = h->qtv.max_nnz;
-      s_nnz_end = h->qtv.nnz;
-    }
+    const bool stored = pr.q_slot_first >= 0 && pr.q_slot_first < h->idx_rows;
+    if (!stored) APSS_TRY(build_tail_view(h, h->qtv, pr.q.rowptr, pr.q.idx, pr.q.val, 0, pr.q.nq, 0, false));
+    const apss_handle::TailView &v = stored ? h->tv : h->qtv;
+    s.rowptr = stored ? v.rowptr.p + pr.q_slot_first : v.rowptr.p;
+    s.idx = v.idx.p;
+    s.val = v.val.p;
+    s.max_nnz = v.max_nnz;
+    s.nnz_end = v.nnz;
   }
-  const int64_t c_max_nnz = h->head_k > 0 ? h->tv.max_nnz : h->store_max_nnz;  // longest indexed row
-  const int64_t idx_nnz = h->head_k > 0 ? std::max<int64_t>(h->tv.nnz, 1) : h->nnz;  // postings in the inverted index
+  s.c_max_nnz = h->head_k > 0 ? h->tv.max_nnz : h->store_max_nnz;  // longest indexed row
+  s.idx_nnz = h->head_k > 0 ? std::max<int64_t>(h->tv.nnz, 1) : h->nnz;  // postings in the inverted index
+  return APSS_OK;
+}
 
-  const double theta = h->cfg.theta;
-  int mode;
-  if (!(theta > 0.0)) mode = 2;
-  else if (!h->nonneg || (q_slot_first < 0 && !h->q_nonneg) || (h->cfg.flags & APSS_FLAG_FORCE_SCAN)) mode = 1;
-  else mode = 0;
+// back to 16-bit accumulators over smaller tiles, for good; the call runs again
+int32_t drop_acc8(apss_handle *h, bool shard_rule) {
+  h->cx.cb = shard_rule ? 32768 : 65536;
+  h->cx.n_tiles = 0;
+  h->no_acc8 = true;
+  h->downgrades |= APSS_DOWNGRADE_ACC8;
+  APSS_TRY(build_index(h, 0));
+  return kProbeAgain;
+}
+
+// The scales, and which of the three kernel families takes the call: the two-pass join (coarse filter + exact rescoring), the
+// single-pass exact speed kernel, the general kernel.  Three of the downgrades that run the call again are decided here.
+int32_t choose_path(apss_handle *h, Probe &pr) {
+  ProbePath &p = pr.p;
+  const double theta = p.theta = h->cfg.theta;
+  if (!(theta > 0.0)) p.mode = 2;
+  else if (!h->nonneg || (pr.q_slot_first < 0 && !h->q_nonneg) || (h->cfg.flags & APSS_FLAG_FORCE_SCAN)) p.mode = 1;
+  else p.mode = 0;
 
   // every partial score must fit the fixed-point accumulators: by Cauchy-Schwarz a partial sum of non-negative
   // products is at most |q| * |c| <= the product of the largest row norms
-  const double bound = std::sqrt((double)q_max_norm2) * std::sqrt((double)h->store_max_norm2) * 1.0001 + 1e-6;
-  const double fx_scale = bound < 3.9 ? 1073741824.0 : (bound < 15.6 ? 268435456.0 : 0.0);
-  const bool forced_general = (h->cfg.flags & APSS_FLAG_FORCE_GENERAL) || dbg.force_general;
+  const double bound = p.bound = std::sqrt((double)pr.q_max_norm2) * std::sqrt((double)h->store_max_norm2) * 1.0001 + 1e-6;
+  p.fx_scale = bound < 3.9 ? 1073741824.0 : (bound < 15.6 ? 268435456.0 : 0.0);
+  p.forced_general = (h->cfg.flags & APSS_FLAG_FORCE_GENERAL) || h->dbgcfg.force_general;
 
   // ---- path 1: two-pass join (coarse filter + exact rescoring) ----
   // accumulator units per 1.0: a 16-bit sum holds S * |q||c| (fp16 weights: + 2^-11) plus one unit per shared term
   // S = the largest power of two that fits (2^15 for unit-norm input); un-normalised input gets a smaller one as long as
   // the threshold in units stays well above the round-up bias (one unit per shared term), else the filter passes too much
-  const double cx_shared = (double)std::min<int64_t>(s_max_nnz, c_max_nnz);
+  const double cx_shared = p.cx_shared = (double)std::min<int64_t>(pr.s.max_nnz, pr.s.c_max_nnz);
   const double cx_room = 65535.0 - cx_shared;
   double cx_scale = 0.0;
   for (int k = 15; k >= 4 && cx_scale == 0.0; --k)
@@ -2225,45 +2309,37 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   // the shard rule (term-range shards, and the sparse half of a handle with a dense-head block) scales the threshold
   // down per query and tile: the kernel clamps it at 1, which only admits more
   const bool hybrid_wanted = h->head_k > 0;
-  const float head_thr = (float)(theta - 0.0080 * bound - 1e-5);
+  p.head_thr = (float)(theta - 0.0080 * bound - 1e-5);
   // weights of either sign with theta > 0 go through the filter too (it then sums positive products only: an upper bound of
   // the partial score, under the shard rule as much as without it -- the rule's ratios are norms); a handle with a
   // dense-head block (and long queries over 65536-row tiles) has no such instantiation and keeps the general kernel
-  const bool shard_rule = h->sharded || hybrid_wanted;
-  const bool cx_signed = mode == 1 && !(h->cfg.flags & APSS_FLAG_FORCE_SCAN) && !hybrid_wanted &&
-                         (h->cx.cb <= 32768 || s_max_nnz <= 512) && !dbg.chunk8 && !dbg.window;
+  const bool shard_rule = p.shard_rule = h->sharded || hybrid_wanted;
+  p.cx_signed = p.mode == 1 && !(h->cfg.flags & APSS_FLAG_FORCE_SCAN) && !hybrid_wanted &&
+                (h->cx.cb <= 32768 || pr.s.max_nnz <= 512) && !h->dbgcfg.chunk8 && !h->dbgcfg.window;
   // 65536-row tiles (term shards; the sparse regime of a plain handle): the 8-bit filter -- 65536 candidates in 64 KB, two
   // 512-thread workgroups per CU -- if this call's norms and row lengths leave room for its sums
   const bool big_shard_tiles = shard_rule && h->cx.cb > 32768;
-  const double a8_scale = h->cx.cb >= 65536 && mode == 0 && s_max_nnz <= 512 && !dbg.no_acc8 && !h->no_acc8 && !dbg.chunk8
-                              ? acc8_scale(bound, cx_shared, theta) : 0.0;
-  if ((big_shard_tiles || h->cx.cb > 65536) && !(a8_scale > 0)) {
-    // not this time (a long row, a large norm, signed weights): back to 16-bit accumulators over smaller tiles, for good
-    h->cx.cb = shard_rule ? 32768 : 65536;
-    h->cx.n_tiles = 0;
-    h->no_acc8 = true;
-    h->downgrades |= APSS_DOWNGRADE_ACC8;
-    APSS_TRY(build_index(h, 0));
-    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
-  }
-  if (a8_scale > 0) {
-    cx_scale = a8_scale;
-  }
-  const double cx_theta_used = std::floor(theta * cx_scale * (1.0 - 1.0 / 2048 - 1e-6));
-  const bool coarse_path = h->use_coarse && (mode == 0 || cx_signed) && (cx_selective || a8_scale > 0) && cx_fp16_ok && !forced_general && nq < (1LL << 30) &&
-                           !(shard_rule && h->cx.cb > 32768 && !(a8_scale > 0)) &&
-                           !dbg.exact_accum && cx_scale > 0 && cx_theta < 65000.0 && (shard_rule || cx_theta - 2 >= 1.0) &&
-                           std::min(c_max_nnz * (int64_t)h->cx.cb, idx_nnz) + (int64_t)kSegAlignC * h->cfg.dim < (1LL << 27);
+  const double a8_scale = p.a8_scale = h->cx.cb >= 65536 && p.mode == 0 && pr.s.max_nnz <= 512 && !h->dbgcfg.no_acc8 && !h->no_acc8 && !h->dbgcfg.chunk8
+                                           ? acc8_scale(bound, cx_shared, theta) : 0.0;
+  // not this time (a long row, a large norm, signed weights): back to 16-bit accumulators over smaller tiles, for good
+  if ((big_shard_tiles || h->cx.cb > 65536) && !(a8_scale > 0)) return drop_acc8(h, shard_rule);
+  if (a8_scale > 0) cx_scale = a8_scale;
+  p.cx_scale = cx_scale;
+  p.cx_theta = std::floor(theta * cx_scale * (1.0 - 1.0 / 2048 - 1e-6));
+  p.coarse_path = h->use_coarse && (p.mode == 0 || p.cx_signed) && (cx_selective || a8_scale > 0) && cx_fp16_ok && !p.forced_general && pr.q.nq < (1LL << 30) &&
+                  !(shard_rule && h->cx.cb > 32768 && !(a8_scale > 0)) &&
+                  !h->dbgcfg.exact_accum && cx_scale > 0 && cx_theta < 65000.0 && (shard_rule || cx_theta - 2 >= 1.0) &&
+                  std::min(pr.s.c_max_nnz * (int64_t)h->cx.cb, pr.s.idx_nnz) + (int64_t)kSegAlignC * h->cfg.dim < (1LL << 27);
   // rows waiting in the tail are scored pair by pair after the join over the index; that needs the two-pass path's final
   // list and a bounded number of pairs -- otherwise they are folded into the index first
-  const int64_t tail_n = h->n_rows - h->idx_rows;
-  if (tail_n > 0 && (!(coarse_path && !h->sharded) || nq * tail_n > kTailMaxPairs)) {
+  p.tail_n = h->n_rows - h->idx_rows;
+  if (p.tail_n > 0 && (!(p.coarse_path && !h->sharded) || pr.q.nq * p.tail_n > kTailMaxPairs)) {
     APSS_TRY(build_index(h, h->idx_rows));
-    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+    return kProbeAgain;
   }
   // a stored batch that still waits in the tail is not in the index: for the join over the index it is an outside batch
-  const int64_t q_slot_base = q_slot_first >= 0 && q_slot_first < h->idx_rows ? q_slot_first : -1;
-  if (hybrid_wanted && !(coarse_path && mode == 0 && (h->head_i8 || head_thr >= 0.5 * theta))) {  // (the INT8 rows carry no rounding bound)
+  p.q_slot_base = pr.q_slot_first >= 0 && pr.q_slot_first < h->idx_rows ? pr.q_slot_first : -1;
+  if (hybrid_wanted && !(p.coarse_path && p.mode == 0 && (h->head_i8 || p.head_thr >= 0.5 * theta))) {  // (the INT8 rows carry no rounding bound)
     // this call cannot take the hybrid path (signed or very long queries, norms out of range ...): the dense block's
     // terms go back into the inverted index, for good, and the call runs as on a handle without a block
     if (h->sharded)  // (a shard cannot leave the partition its peers were given)
@@ -2272,32 +2348,51 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     h->head_blocked = true;
     h->downgrades |= APSS_DOWNGRADE_HEAD;
     APSS_TRY(build_index(h, 0));
-    return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
+    return kProbeAgain;
   }
-  const bool hybrid = hybrid_wanted;
+  p.hybrid = hybrid_wanted;
   // the batch's rows of the dense-head block and its tail ratios: the store's were packed when it was indexed; an outside
   // batch (or one waiting in the tail) is packed here
   // A stored batch meets the block's candidates as a TRIANGLE (k_head_gemm skips the tiles above a query block; the block that
   // owns them reports the mirrored pair): right only when the batch is the store's last rows.  A window of a windowed call
   // (apss_window.hpp) has stored rows behind it that are no queries of its own: its rows are packed and multiplied as an
   // outside batch's, against every candidate tile (the pair of a row with itself is dropped by external id there)
-  const bool head_outside = hybrid && h->win_nonempty >= 0 && q_slot_base >= 0 && !h->sharded;
-  if (hybrid && (q_slot_base < 0 || head_outside) && !h->sharded) APSS_TRY(pack_query_head(h, q_rowptr, q_idx, q_val, nq));  // (a shard's ingest packed them)
-  const float *q_sub = !shard_rule ? nullptr : (q_slot_base >= 0 ? h->sub.p + q_slot_base : h->q_sub.p);
+  p.head_outside = p.hybrid && h->win_nonempty >= 0 && p.q_slot_base >= 0 && !h->sharded;
+  if (p.hybrid && (p.q_slot_base < 0 || p.head_outside) && !h->sharded) APSS_TRY(pack_query_head(h, pr.q.rowptr, pr.q.idx, pr.q.val, pr.q.nq));  // (a shard's ingest packed them)
+  p.q_sub = !shard_rule ? nullptr : (p.q_slot_base >= 0 ? h->sub.p + p.q_slot_base : h->q_sub.p);
+  return APSS_OK;
+}
 
-  ProbeArgs a{};
+// MERGED rounds (a term shard's thin rounds, apss_even.hpp): M neighbouring query rows share a round, their M filter sums one
+// accumulator -- which then has to hold M sums: the scale for M rows is the scale of one row with M times the norm bound and
+// M times the shared terms.  How many rows the accumulators have room for (plan_filter decides how many a window has):
+double merged_scale(const ProbePath &p, int m) {
+  const double Mx = (double)(1 << m);
+  if (p.a8_scale > 0) return acc8_scale(p.bound * Mx, p.cx_shared * Mx, p.theta);
+  for (int k = 15; k >= 4; --k) {
+    const double S = std::ldexp(1.0, k);
+    if (p.bound * Mx * 1.0005 * S < 65535.0 - p.cx_shared * Mx)
+      return S >= 16384.0 || std::floor(p.theta * S * (1.0 - 1.0 / 2048 - 1e-6)) >= 4.0 * p.cx_shared * Mx ? S : 0.0;
+  }
+  return 0.0;
+}
+
+// the kernels' arguments but the candidate list: store, staged rows, query chunks, the index rendering of the path
+int32_t fill_probe_args(apss_handle *h, Probe &pr) {
+  ProbeArgs &a = pr.a;
+  a = ProbeArgs{};
   a.seg_stride = (int64_t)h->cfg.dim;
   a.ext_id = h->ext.p;
-  a.c_scale = shard_rule ? h->sub.p : nullptr;
+  a.c_scale = pr.p.shard_rule ? h->sub.p : nullptr;
   a.n_rows = h->idx_rows;
-  a.q_rowptr = s_rowptr;
-  a.q_idx = s_idx;
-  a.q_val = s_val;
-  a.q_ext = q_ext;
-  a.q_scale = shard_rule ? q_sub : nullptr;
-  a.nq = (int32_t)nq;
-  a.nq_rows = (int32_t)nq;
-  a.q_nnz_end = s_nnz_end;
+  a.q_rowptr = pr.s.rowptr;
+  a.q_idx = pr.s.idx;
+  a.q_val = pr.s.val;
+  a.q_ext = pr.q.ext;
+  a.q_scale = pr.p.shard_rule ? pr.p.q_sub : nullptr;
+  a.nq = (int32_t)pr.q.nq;
+  a.nq_rows = (int32_t)pr.q.nq;
+  a.q_nnz_end = pr.s.nnz_end;
   // ~2 workgroups per CU per tile in flight at once, tiles swept one after another (tile-major grid) so the
   // chip works on one tile's postings at a time and they stay in L2 / Infinity Cache
   // ... that is the whole-store join (a million queries: 1024 chunks of ~1000 rounds each).  A streamed batch has few queries:
@@ -2309,546 +2404,542 @@ int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     const int64_t tiles_now = std::max<int64_t>(1, ceil_div(h->idx_rows, h->use_coarse ? h->cx.cb : h->ex.cb));
     // (eight workgroups per resident slot: with four, the last, partly filled wave of workgroups cost a fifth of the launch.
     // That was the grid launch, which k_probe_coarse, k_probe_wave and k_probe keep.  k_probe_even's launch is persistent --
-    // resident workgroups over a work list of these (tile, chunk) cells, the last ones cut finer: see `persist` below -- and a
+    // resident workgroups over a work list of these (tile, chunk) cells, the last ones cut finer: see prepare_work_lists -- and a
     // chunk there is the unit a workgroup's set-up is paid for, no longer the unit the end of the launch is ragged by.)
-    want_chunks = std::min<int64_t>(1024, std::max<int64_t>(ceil_div(4096, tiles_now), ceil_div(nq, 256)));
+    want_chunks = std::min<int64_t>(1024, std::max<int64_t>(ceil_div(4096, tiles_now), ceil_div(pr.q.nq, 256)));
   }
-  if (dbg.chunks > 0) want_chunks = dbg.chunks;
-  a.q_chunk = (int32_t)std::max<int64_t>(1, ceil_div(nq, want_chunks));
-  a.n_chunks = (int32_t)ceil_div(nq, a.q_chunk);
-  a.q_slot_base = q_slot_base;
-  a.theta = (float)theta;
+  if (h->dbgcfg.chunks > 0) want_chunks = h->dbgcfg.chunks;
+  a.q_chunk = (int32_t)std::max<int64_t>(1, ceil_div(pr.q.nq, want_chunks));
+  a.n_chunks = (int32_t)ceil_div(pr.q.nq, a.q_chunk);
+  a.q_slot_base = pr.p.q_slot_base;
+  a.theta = (float)pr.p.theta;
   a.counters = h->counters.p;
-  a.cx_scale = (float)cx_scale;
-  a.cx_theta = (float)cx_theta_used;
+  a.cx_scale = (float)pr.p.cx_scale;
+  a.cx_theta = (float)pr.p.cx_theta;
 
-  apss_handle::IndexSet &ix = coarse_path ? h->cx : h->ex;
-  if (!coarse_path) APSS_TRY(ensure_exact_index(h));
+  if (!pr.p.coarse_path) APSS_TRY(ensure_exact_index(h));
+  const apss_handle::IndexSet &ix = probe_index(h, pr.p);
   a.tile_seg = ix.seg.p;
   a.post = h->ex.post.p;
   a.post_c = h->cx.post_c.p;
   a.tile_post_base = ix.base.p;
-  a.tile_scale = shard_rule ? (coarse_path ? h->tile_min_c.p : h->tile_min.p) : nullptr;
+  a.tile_scale = pr.p.shard_rule ? (pr.p.coarse_path ? h->tile_min_c.p : h->tile_min.p) : nullptr;
   a.cb = ix.cb;
   a.n_tiles = (int32_t)ix.n_tiles;
+  return APSS_OK;
+}
 
+// Which single-pass kernel takes the call if the two-pass join does not, and the fixed-point scale both count in
+int32_t choose_exact_kernel(apss_handle *h, Probe &pr) {
   // ---- path 2: single-pass exact speed kernel (k_probe_wave); kernel shapes: A = 8 waves x 64-chunk window, one
   // workgroup per CU at 32768-row tiles; C = 8 waves x 40-chunk window, TWO workgroups per CU at <= 16384-row tiles
-  const char variant = h->ex.cb <= 16384 ? 'C' : 'A';
+  pr.xk.variant = h->ex.cb <= 16384 ? 'C' : 'A';
   const int wave_block = 512;
-  const int wave_u = variant == 'A' ? 8 : 5;
-  const int wave_longcap = variant == 'A' ? 256 : 128;
-  const int wave_survcap = variant == 'A' ? 1024 : 512;
+  pr.xk.u = pr.xk.variant == 'A' ? 8 : 5;
+  pr.xk.longcap = pr.xk.variant == 'A' ? 256 : 128;
+  pr.xk.survcap = pr.xk.variant == 'A' ? 1024 : 512;
   // chunk descriptors pack (first posting * 8 + count - 1) into 32 bits: a tile's postings must number < 2^28
-  const bool wave_path = !coarse_path && mode == 0 && fx_scale > 0 && q_max_nnz <= wave_block && !forced_general &&
-                         h->store_max_nnz * (int64_t)h->ex.cb + (int64_t)kSegAlign * h->cfg.dim < (1LL << 28);
+  pr.xk.wave = !pr.p.coarse_path && pr.p.mode == 0 && pr.p.fx_scale > 0 && pr.q_max_nnz <= wave_block && !pr.p.forced_general &&
+               h->store_max_nnz * (int64_t)h->ex.cb + (int64_t)kSegAlign * h->cfg.dim < (1LL << 28);
   // ---- path 3: general kernel (k_probe): signed fixed point when the norms are bounded, else fp32 atomics ----
-  const bool gen_fx = !coarse_path && !wave_path && fx_scale > 0;
+  pr.xk.fx = !pr.p.coarse_path && !pr.xk.wave && pr.p.fx_scale > 0;
+  pr.xk.block = pr.xk.wave ? wave_block : gen_block(pr.p.mode, h->ex.cb);
   // the per-round cut (apss_set_top_k_tile_cut): only where the uncut list is the problem, k_probe<2> of a plain handle
-  const bool gen_cut = h->tile_cut && h->top_k > 0 && !h->sharded && !coarse_path && !wave_path && mode == 2;
-  if (gen_cut) {
-    APSS_TRY(ensure(h, h->row_pairs, (size_t)nq));
-    a.row_pairs = h->row_pairs.p;
-    a.cut_k = h->top_k;
+  pr.xk.cut = h->tile_cut && h->top_k > 0 && !h->sharded && !pr.p.coarse_path && !pr.xk.wave && pr.p.mode == 2;
+  if (pr.xk.cut) {
+    APSS_TRY(ensure(h, h->row_pairs, (size_t)pr.q.nq));
+    pr.a.row_pairs = h->row_pairs.p;
+    pr.a.cut_k = h->top_k;
   }
-  const double scale_used = wave_path ? fx_scale : fx_scale / 2;
-  a.fx_scale = (float)scale_used;
-  a.theta_fx = (uint32_t)std::min(4294967295.0, std::max(1.0, std::ceil(theta * scale_used)));
-  a.theta_fxi = (int32_t)std::max(-2147483647.0, std::min(2147483647.0, std::ceil(theta * scale_used)));
+  const double scale_used = pr.xk.wave ? pr.p.fx_scale : pr.p.fx_scale / 2;
+  pr.a.fx_scale = (float)scale_used;
+  pr.a.theta_fx = (uint32_t)std::min(4294967295.0, std::max(1.0, std::ceil(pr.p.theta * scale_used)));
+  pr.a.theta_fxi = (int32_t)std::max(-2147483647.0, std::min(2147483647.0, std::ceil(pr.p.theta * scale_used)));
+  // (the filter kernels keep their LDS in static arrays: no dynamic allocation)
+  pr.xk.lds = pr.p.coarse_path ? 0
+              : pr.xk.wave     ? probe_wave_lds_bytes(h->ex.cb, wave_block, pr.xk.u, pr.xk.longcap, pr.xk.survcap)
+                               : probe_lds_bytes(h->ex.cb, pr.xk.block, pr.p.mode);
+  return APSS_OK;
+}
 
-  // MERGED rounds (a term shard's thin rounds, apss_even.hpp): M neighbouring query rows share a round, their M filter sums one
-  // accumulator -- which then has to hold M sums: the scale for M rows is the scale of one row with M times the norm bound and
-  // M times the shared terms.  How many rows the accumulators have room for (plan_filter decides how many a window has):
-  auto merged_scale = [&](int m) -> double {
-    const double Mx = (double)(1 << m);
-    if (a8_scale > 0) return acc8_scale(bound * Mx, cx_shared * Mx, theta);
-    for (int k = 15; k >= 4; --k) {
-      const double S = std::ldexp(1.0, k);
-      if (bound * Mx * 1.0005 * S < 65535.0 - cx_shared * Mx)
-        return S >= 16384.0 || std::floor(theta * S * (1.0 - 1.0 / 2048 - 1e-6)) >= 4.0 * cx_shared * Mx ? S : 0.0;
-    }
-    return 0.0;
-  };
-  // ... and how many the filter stays SELECTIVE with: a chance pair collects about 1 / t of the threshold's scale per shared term
-  // (t = terms of a row inside this shard), and a round of M rows hits a given candidate M t^2 / R times on average (R = terms
-  // of the range).  Rows of a dozen terms over thousands of terms (C3's shards: t = 12.5, R = 12500): a chance candidate is
-  // hit once, by one row.  Rows of three or four terms over a few hundred: three chance hits from different rows of a round
-  // cross the threshold (measured: 8 x more candidates than unmerged) -- not there.  A fuse behind the estimate: a merged
-  // launch that reports more than two rounds per query row turns merging off for the handle (merge_off).
-  // (Term shards only, with or without a dense-head block -- power-law C5's 8 x 1 shard at N = 2M: tail filter 39.5 -> 24.0 ms.  The
-  // sparse half of a PLAIN handle with a block was tried: its rounds take 4-5 window steps, two rows do not fit one window.)
-  const double t_shard = (double)s_nnz_end / (double)std::max<int64_t>(nq, 1);
+// The filter kernel's instantiation (plan_filter), with as many query rows per round as the accumulators have room for AND
+// the filter stays SELECTIVE with: a chance pair collects about 1 / t of the threshold's scale per shared term
+// (t = terms of a row inside this shard), and a round of M rows hits a given candidate M t^2 / R times on average (R = terms
+// of the range).  Rows of a dozen terms over thousands of terms (C3's shards: t = 12.5, R = 12500): a chance candidate is
+// hit once, by one row.  Rows of three or four terms over a few hundred: three chance hits from different rows of a round
+// cross the threshold (measured: 8 x more candidates than unmerged) -- not there.  A fuse behind the estimate: a merged
+// launch that reports more than two rounds per query row turns merging off for the handle (merge_off).
+// (Term shards only, with or without a dense-head block -- power-law C5's 8 x 1 shard at N = 2M: tail filter 39.5 -> 24.0 ms.  The
+// sparse half of a PLAIN handle with a block was tried: its rounds take 4-5 window steps, two rows do not fit one window.)
+int32_t plan_merged_rounds(apss_handle *h, Probe &pr) {
+  const double t_shard = (double)pr.s.nnz_end / (double)std::max<int64_t>(pr.q.nq, 1);
   const double r_shard = (double)std::max<int64_t>(1, (int64_t)h->cfg.term_hi - h->cfg.term_lo);
   int max_merge_log2 = 0;
-  if (coarse_path && h->sharded && mode == 0 && !cx_signed && dbg.merge != 0 && !h->merge_off && t_shard >= 8.0)
-    while (max_merge_log2 < (dbg.merge > 0 ? std::min(dbg.merge, 2) : 1) && (nq >> (max_merge_log2 + 1)) >= 1 &&
-           (double)(2 << max_merge_log2) * t_shard * t_shard <= 0.25 * r_shard && merged_scale(max_merge_log2 + 1) > 0)
+  if (pr.p.coarse_path && h->sharded && pr.p.mode == 0 && !pr.p.cx_signed && h->dbgcfg.merge != 0 && !h->merge_off && t_shard >= 8.0)
+    while (max_merge_log2 < (h->dbgcfg.merge > 0 ? std::min(h->dbgcfg.merge, 2) : 1) && (pr.q.nq >> (max_merge_log2 + 1)) >= 1 &&
+           (double)(2 << max_merge_log2) * t_shard * t_shard <= 0.25 * r_shard && merged_scale(pr.p, max_merge_log2 + 1) > 0)
       ++max_merge_log2;
-  CxVariant cxv{};
-  if (coarse_path)
-    APSS_TRY(plan_filter(h, FilterFacts{a8_scale > 0, shard_rule, cx_signed, hybrid_wanted, s_max_nnz, s_nnz_end, nq, idx_nnz, max_merge_log2}, cxv, a));
-  if (a.merge_log2 > 0) {
-    const double S = merged_scale(a.merge_log2);
-    a.cx_scale = (float)S;
-    a.cx_theta = (float)std::floor(theta * S * (1.0 - 1.0 / 2048 - 1e-6));
+  pr.cxv = CxVariant{};
+  if (pr.p.coarse_path)
+    APSS_TRY(plan_filter(h, FilterFacts{pr.p.a8_scale > 0, pr.p.shard_rule, pr.p.cx_signed, pr.p.hybrid, pr.s.max_nnz, pr.s.nnz_end, pr.q.nq, pr.s.idx_nnz, max_merge_log2}, pr.cxv, pr.a));
+  if (pr.a.merge_log2 > 0) {
+    const double S = merged_scale(pr.p, pr.a.merge_log2);
+    pr.a.cx_scale = (float)S;
+    pr.a.cx_theta = (float)std::floor(pr.p.theta * S * (1.0 - 1.0 / 2048 - 1e-6));
   }
-  // ---- SYMMETRIC whole-store join: the batch IS the indexed store (query row v = stored row v: apss_self_join, or
-  // insert-and-query into an empty handle), so the pair (q, c) and the pair (c, q) share their terms and their score.  The
-  // filter runs a (query tile S, candidate tile T) workgroup only for T <= S and k_mirror_survivors adds the other direction
-  // of every survivor with T < S; both directions are then re-scored exactly, as without the symmetry: same result list,
-  // half the rounds.  Needs query chunks that do not straddle a tile (q_chunk | cb).  The reference finds both directions by
-  // probing twice (IndexingWorkerActor.scala:123-134); posting_visits / candidate_pairs keep counting what IT visits (the
-  // kernels count a tile pair below the diagonal twice: both statistics are symmetric in the two tiles), and
-  // device_posting_visits says what the kernels visited.
-  bool tri = false;
+  return APSS_OK;
+}
+
+// ---- SYMMETRIC whole-store join: the batch IS the indexed store (query row v = stored row v: apss_self_join, or
+// insert-and-query into an empty handle), so the pair (q, c) and the pair (c, q) share their terms and their score.  The
+// filter runs a (query tile S, candidate tile T) workgroup only for T <= S and k_mirror_survivors adds the other direction
+// of every survivor with T < S; both directions are then re-scored exactly, as without the symmetry: same result list,
+// half the rounds.  Needs query chunks that do not straddle a tile (q_chunk | cb).  The reference finds both directions by
+// probing twice (IndexingWorkerActor.scala:123-134); posting_visits / candidate_pairs keep counting what IT visits (the
+// kernels count a tile pair below the diagonal twice: both statistics are symmetric in the two tiles), and
+// device_posting_visits says what the kernels visited.
+void decide_symmetry(apss_handle *h, Probe &pr) {
+  const apss_handle::IndexSet &ix = probe_index(h, pr.p);
   uint32_t sym_declined = APSS_SYM_RAN;  // why not (apss_stats.symmetric_declined)
-  if (dbg.no_sym || (h->cfg.flags & APSS_FLAG_NO_SYMMETRY)) sym_declined = APSS_SYM_FLAG;
-  else if (!(q_slot_base == 0 && nq == h->idx_rows && nq == h->n_rows && tail_n == 0)) sym_declined = APSS_SYM_NOT_WHOLE;
-  else if (!coarse_path) sym_declined = APSS_SYM_PATH;
-  else if (cxv.vrows) sym_declined = APSS_SYM_LONG_ROWS;
+  if (h->dbgcfg.no_sym || (h->cfg.flags & APSS_FLAG_NO_SYMMETRY)) sym_declined = APSS_SYM_FLAG;
+  else if (!(pr.p.q_slot_base == 0 && pr.q.nq == h->idx_rows && pr.q.nq == h->n_rows && pr.p.tail_n == 0)) sym_declined = APSS_SYM_NOT_WHOLE;
+  else if (!pr.p.coarse_path) sym_declined = APSS_SYM_PATH;
+  else if (pr.cxv.vrows) sym_declined = APSS_SYM_LONG_ROWS;
   else if (ix.n_tiles <= 1) sym_declined = APSS_SYM_ONE_TILE;
   else {
     int64_t qc = 1;
-    while (qc < a.q_chunk) qc <<= 1;
+    while (qc < pr.a.q_chunk) qc <<= 1;
     if (qc <= ix.cb && ix.cb % qc == 0) {
-      tri = true;
-      a.tri = 1;
-      a.q_chunk = (int32_t)qc;
-      a.n_chunks = (int32_t)ceil_div(nq, qc);
+      pr.a.tri = 1;
+      pr.a.q_chunk = (int32_t)qc;
+      pr.a.n_chunks = (int32_t)ceil_div(pr.q.nq, qc);
     } else {
       sym_declined = APSS_SYM_CHUNK;
     }
   }
   h->st.symmetric_declined = sym_declined;
-  h->st.query_chunk = a.q_chunk;
+  h->st.query_chunk = pr.a.q_chunk;
   h->st.filter_tile_rows = ix.cb;
-  h->st.queries_per_round = 1 << a.merge_log2;
-  if (a.merge_log2 > 0) {
-    // from here on the launch counts ROUNDS: a chunk is a whole number of them (a symmetric join's power of two stays one)
-    const int64_t M = 1LL << a.merge_log2;
-    const int64_t qc = ceil_div(a.q_chunk, M) * M;
-    a.q_chunk = (int32_t)(qc / M);
-    a.n_chunks = (int32_t)ceil_div(nq, qc);
-    a.nq = (int32_t)ceil_div(nq, M);
-    APSS_TRY(ensure(h, h->q_prenorm, (size_t)s_nnz_end));
-    hipLaunchKernelGGL(k_prenorm_rows, dim3((unsigned)ceil_div(nq * kGroup, 256)), dim3(256), 0, h->stream, s_rowptr, s_val, q_sub, nq, h->q_prenorm.p);
-    HIPCHK(h, hipGetLastError());
-    a.q_val = h->q_prenorm.p;
-  }
-  const int vrow_part = 512;
-  // (the filter kernels keep their LDS in static arrays: no dynamic allocation)
-  const size_t lds = coarse_path ? 0
-                     : wave_path ? probe_wave_lds_bytes(h->ex.cb, wave_block, wave_u, wave_longcap, wave_survcap)
-                                 : probe_lds_bytes(h->ex.cb, gen_block(mode, h->ex.cb), mode);
-  auto launch_wave = [&](bool diag) -> int32_t {
-    const dim3 grid((unsigned)((int64_t)a.n_tiles * a.n_chunks));
-#define APSS_LAUNCH_WAVE1(B, UU, LC, SC, SH, DG)                                                                         \
-    do {                                                                                                                   \
-      auto kern = k_probe_wave<B, UU, LC, SC, SH, DG>;                                                                     \
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      hipLaunchKernelGGL(kern, grid, dim3(B), lds, h->stream, a);                                                          \
-    } while (0)
-#define APSS_LAUNCH_WAVE(B, UU, LC, SC)                                                                                  \
-    do {                                                                                                                   \
-      if (h->sharded) { if (diag) APSS_LAUNCH_WAVE1(B, UU, LC, SC, true, true); else APSS_LAUNCH_WAVE1(B, UU, LC, SC, true, false); } \
-      else { if (diag) APSS_LAUNCH_WAVE1(B, UU, LC, SC, false, true); else APSS_LAUNCH_WAVE1(B, UU, LC, SC, false, false); }          \
-    } while (0)
-    if (variant == 'A') APSS_LAUNCH_WAVE(512, 8, 256, 1024);
-    else APSS_LAUNCH_WAVE(512, 5, 128, 512);
-#undef APSS_LAUNCH_WAVE1
-#undef APSS_LAUNCH_WAVE
-    HIPCHK(h, hipGetLastError());
-    return APSS_OK;
-  };
+  h->st.queries_per_round = 1 << pr.a.merge_log2;
+}
 
-  if (coarse_path && s_max_nnz > vrow_part) APSS_TRY(cut_long_queries(h, s_rowptr, nq, vrow_part, a));
+// merged rounds: from here on the launch counts ROUNDS, and the rows' weights are staged divided by their shard factors
+int32_t stage_merged_rows(apss_handle *h, Probe &pr) {
+  // a chunk is a whole number of rounds (a symmetric join's power of two stays one)
+  const int64_t M = 1LL << pr.a.merge_log2;
+  const int64_t qc = ceil_div(pr.a.q_chunk, M) * M;
+  pr.a.q_chunk = (int32_t)(qc / M);
+  pr.a.n_chunks = (int32_t)ceil_div(pr.q.nq, qc);
+  pr.a.nq = (int32_t)ceil_div(pr.q.nq, M);
+  APSS_TRY(ensure(h, h->q_prenorm, (size_t)pr.s.nnz_end));
+  hipLaunchKernelGGL(k_prenorm_rows, dim3((unsigned)ceil_div(pr.q.nq * kGroup, 256)), dim3(256), 0, h->stream, pr.s.rowptr, pr.s.val, pr.p.q_sub, pr.q.nq, h->q_prenorm.p);
+  HIPCHK(h, hipGetLastError());
+  pr.a.q_val = h->q_prenorm.p;
+  return APSS_OK;
+}
+
+// ---- streamed batches (single-vector messages up to a few tens of thousands of rows): the exact pass is CHAINED behind the filter on the stream --
+// k_rescore takes its pair count from the filter's counter on the device, k_tail_score appends to the same list -- and the
+// call synchronises ONCE, reading all counters together (a host round trip costs as much as these kernels do)
+constexpr int64_t kChainMaxQueries = 65536;
+
+// tiles per launch, the candidate list's first reservation, whether the exact pass is chained
+int32_t size_launches(apss_handle *h, Probe &pr) {
   // one launch sweeps a group of tiles sized for roughly 2e11 posting visits (a few hundred ms): a very large join
   // becomes a sequence of launches of bounded duration instead of one kernel that runs for tens of seconds
-  const int64_t total_tiles = ix.n_tiles;
+  const int64_t total_tiles = pr.total_tiles = probe_index(h, pr.p).n_tiles;
   int64_t tiles_per_launch = std::max<int64_t>(1, total_tiles);
   if (total_tiles > 0) {
-    const double per_tile = (double)s_nnz_end * ((double)idx_nnz / (double)total_tiles / (double)h->cfg.dim) + 1.0;
+    const double per_tile = (double)pr.s.nnz_end * ((double)pr.s.idx_nnz / (double)total_tiles / (double)h->cfg.dim) + 1.0;
     tiles_per_launch = (int64_t)std::min<double>((double)total_tiles, std::max(1.0, std::floor(2e11 / per_tile)));
-    if (dbg.tiles_per_launch > 0) tiles_per_launch = dbg.tiles_per_launch;
-    tiles_per_launch = std::min<int64_t>(tiles_per_launch, std::max<int64_t>(1, 2000000000LL / std::max(1, a.n_chunks)));
+    if (h->dbgcfg.tiles_per_launch > 0) tiles_per_launch = h->dbgcfg.tiles_per_launch;
+    tiles_per_launch = std::min<int64_t>(tiles_per_launch, std::max<int64_t>(1, 2000000000LL / std::max(1, pr.a.n_chunks)));
   }
+  pr.tiles_per_launch = tiles_per_launch;
   // room for two hits per query up front -- and, with a dense-head block, for what its filters passed on the policy's sample
   // (a narrow folded block passes a few pairs per million: 1e8 of them at N = 1e7): growing means running the whole probe again
-  int64_t want_cap = std::min<int64_t>(2 * nq, 1LL << 28);
-  if (hybrid_wanted && h->head_sample_frac > 0.0)
-    want_cap = std::min<int64_t>(want_cap + (int64_t)(1.5 * h->head_sample_frac * (double)nq * (double)h->idx_rows), 1LL << 30);
-  else if (hybrid_wanted && h->sharded)  // (a shard was given its head: no sample of its own; power-law C5 measured ~1 per query and shard)
-    want_cap = std::min<int64_t>(want_cap + 6 * nq, 1LL << 30);
-  if (h->res_q.cap < (size_t)want_cap) {
-    const size_t cap0 = (size_t)(dbg.res_cap > 0 ? dbg.res_cap : std::max<int64_t>(1 << 20, want_cap));  // (res_cap: test hook, forces the regrowth path)
-    APSS_TRY(ensure(h, h->res_q, cap0, 0, true));
-    APSS_TRY(ensure(h, h->res_c, cap0, 0, true));
-    APSS_TRY(ensure(h, h->res_s, cap0, 0, true));
+  int64_t want_cap = std::min<int64_t>(2 * pr.q.nq, 1LL << 28);
+  if (pr.p.hybrid && h->head_sample_frac > 0.0)
+    want_cap = std::min<int64_t>(want_cap + (int64_t)(1.5 * h->head_sample_frac * (double)pr.q.nq * (double)h->idx_rows), 1LL << 30);
+  else if (pr.p.hybrid && h->sharded)  // (a shard was given its head: no sample of its own; power-law C5 measured ~1 per query and shard)
+    want_cap = std::min<int64_t>(want_cap + 6 * pr.q.nq, 1LL << 30);
+  if (h->res.cap() < (size_t)want_cap) {
+    const size_t cap0 = (size_t)(h->dbgcfg.res_cap > 0 ? h->dbgcfg.res_cap : std::max<int64_t>(1 << 20, want_cap));  // (res_cap: test hook, forces the regrowth path)
+    APSS_TRY(h->res.ensure(h, cap0, 0, true));
   }
-  if (hybrid) APSS_TRY(ensure(h, h->head_ctr, 4));
-  // ---- streamed batches (single-vector messages up to a few tens of thousands of rows): the exact pass is CHAINED behind the filter on the stream --
-  // k_rescore takes its pair count from the filter's counter on the device, k_tail_score appends to the same list -- and the
-  // call synchronises ONCE, reading all counters together (a host round trip costs as much as these kernels do)
-  constexpr int64_t kChainMaxQueries = 65536;
-  const bool chain = coarse_path && !h->sharded && !hybrid && !tri && nq <= kChainMaxQueries && !dbg.no_chain;
-  const int64_t chain_tail_pairs = chain ? nq * tail_n : 0;
-  if (chain) APSS_TRY(ensure(h, h->chain_ctr, kCtrCount));
-  // ---- k_probe_even: PERSISTENT launches (apss_even.hpp, apss_worklist.hpp).  One work list per launch of the call, built
-  // here, one behind the other, and kept in the handle with their keys: a call whose launches have the keys of the last
-  // call's (a join repeated, a stream of equal batches) uploads nothing.  The lists go up asynchronously from pinned memory.
-  // (A list of millions of cells -- a join of tens of millions of rows in small chunks -- is not worth its upload: grid launch.)
-  constexpr int kPersistFine = 128;  // rounds per item at the end of a list (profiles/persist_filter.md has the sweep)
-  constexpr int64_t kPersistMaxCells = 1LL << 22;
-  int persist_slots = 0;
-  const bool persist = coarse_path && cxv.even && !dbg.no_persist && total_tiles > 0 && total_tiles * (int64_t)a.n_chunks <= kPersistMaxCells;
-  if (persist) {
-    APSS_TRY(even_resident_slots(h, cxv, &persist_slots));
-    int fine = 1;
-    while (2 * fine <= (dbg.persist_fine > 0 ? dbg.persist_fine : kPersistFine)) fine *= 2;
-    std::vector<apss::WorkListKey> keys;
-    for (int64_t t0 = 0; t0 < total_tiles; t0 += tiles_per_launch) {
-      apss::WorkListKey k;
-      k.q_slot_base = a.merge_log2 > 0 ? q_slot_base : -1;  // (decides own_tile, which only merged launches have)
-      k.nq = a.nq;
-      k.nq_rows = a.nq_rows;
-      k.q_chunk = a.q_chunk;
-      k.n_chunks = a.n_chunks;
-      k.cb = a.cb;
-      k.tri = a.tri;
-      k.merge_log2 = a.merge_log2;
-      k.tile0 = (int32_t)t0;
-      k.n_tiles = (int32_t)std::min<int64_t>(tiles_per_launch, total_tiles - t0);
-      k.fine = fine;
-      k.slots = dbg.persist_wgs > 0 ? dbg.persist_wgs : persist_slots;
-      keys.push_back(k);
-    }
-    if (!(keys == h->wl_keys) || !h->wl_dev.p) {
-      std::vector<apss::ProbeItem> items;
-      h->wl_keys.clear();  // (nothing is cached while this fails half way)
-      h->wl_off.assign(1, 0);
-      h->wl_fine.clear();
-      for (const apss::WorkListKey &k : keys) {
-        h->wl_fine.push_back(apss::build_work_list(k, items));
-        h->wl_off.push_back((int64_t)items.size());
-      }
-      if (!h->wl_ev) HIPCHK(h, hipEventCreateWithFlags(&h->wl_ev, hipEventDisableTiming));
-      else HIPCHK(h, hipEventSynchronize(h->wl_ev));  // the last upload has left the pinned buffer
-      if (items.size() > h->wl_pin_cap) {
-        if (h->wl_pin) (void)hipHostFree(h->wl_pin);
-        h->wl_pin = nullptr;
-        h->wl_pin_cap = 0;
-        const size_t cap = std::max<size_t>(items.size() + items.size() / 2, 4096);
-        HIPCHK(h, hipHostMalloc((void **)&h->wl_pin, cap * sizeof(apss::ProbeItem), hipHostMallocDefault));
-        h->wl_pin_cap = cap;
-      }
-      APSS_TRY(ensure(h, h->wl_dev, std::max<size_t>(items.size(), 1)));
-      if (!items.empty()) {
-        std::memcpy(h->wl_pin, items.data(), items.size() * sizeof(apss::ProbeItem));
-        HIPCHK(h, hipMemcpyAsync(h->wl_dev.p, h->wl_pin, items.size() * sizeof(apss::ProbeItem), hipMemcpyHostToDevice, h->stream));
-      }
-      HIPCHK(h, hipEventRecord(h->wl_ev, h->stream));
-      h->wl_keys = keys;
+  if (pr.p.hybrid) APSS_TRY(ensure(h, h->head_ctr, 4));
+  pr.chain = pr.p.coarse_path && !h->sharded && !pr.p.hybrid && !pr.a.tri && pr.q.nq <= kChainMaxQueries && !h->dbgcfg.no_chain;
+  if (pr.chain) APSS_TRY(ensure(h, h->chain_ctr, kCtrCount));
+  return APSS_OK;
+}
+
+// ---- k_probe_even: PERSISTENT launches (apss_even.hpp, apss_worklist.hpp).  One work list per launch of the call, built
+// here, one behind the other, and kept in the handle with their keys: a call whose launches have the keys of the last
+// call's (a join repeated, a stream of equal batches) uploads nothing.  The lists go up asynchronously from pinned memory.
+// (A list of millions of cells -- a join of tens of millions of rows in small chunks -- is not worth its upload: grid launch.)
+constexpr int kPersistFine = 128;  // rounds per item at the end of a list (profiles/persist_filter.md has the sweep)
+constexpr int64_t kPersistMaxCells = 1LL << 22;
+int32_t prepare_work_lists(apss_handle *h, Probe &pr) {
+  pr.persist_slots = 0;
+  pr.persist = pr.p.coarse_path && pr.cxv.even && !h->dbgcfg.no_persist && pr.total_tiles > 0 && pr.total_tiles * (int64_t)pr.a.n_chunks <= kPersistMaxCells;
+  if (!pr.persist) return APSS_OK;
+  APSS_TRY(even_resident_slots(h, pr.cxv, &pr.persist_slots));
+  int fine = 1;
+  while (2 * fine <= (h->dbgcfg.persist_fine > 0 ? h->dbgcfg.persist_fine : kPersistFine)) fine *= 2;
+  std::vector<apss::WorkListKey> keys;
+  for (int64_t t0 = 0; t0 < pr.total_tiles; t0 += pr.tiles_per_launch) {
+    apss::WorkListKey k;
+    k.q_slot_base = pr.a.merge_log2 > 0 ? pr.p.q_slot_base : -1;  // (decides own_tile, which only merged launches have)
+    k.nq = pr.a.nq;
+    k.nq_rows = pr.a.nq_rows;
+    k.q_chunk = pr.a.q_chunk;
+    k.n_chunks = pr.a.n_chunks;
+    k.cb = pr.a.cb;
+    k.tri = pr.a.tri;
+    k.merge_log2 = pr.a.merge_log2;
+    k.tile0 = (int32_t)t0;
+    k.n_tiles = (int32_t)std::min<int64_t>(pr.tiles_per_launch, pr.total_tiles - t0);
+    k.fine = fine;
+    k.slots = h->dbgcfg.persist_wgs > 0 ? h->dbgcfg.persist_wgs : pr.persist_slots;
+    keys.push_back(k);
+  }
+  if (keys == h->wl_keys && h->wl_dev.p) return APSS_OK;
+  std::vector<apss::ProbeItem> items;
+  h->wl_keys.clear();  // (nothing is cached while this fails half way)
+  h->wl_off.assign(1, 0);
+  h->wl_fine.clear();
+  for (const apss::WorkListKey &k : keys) {
+    h->wl_fine.push_back(apss::build_work_list(k, items));
+    h->wl_off.push_back((int64_t)items.size());
+  }
+  if (!h->wl_ev) HIPCHK(h, hipEventCreateWithFlags(&h->wl_ev, hipEventDisableTiming));
+  else HIPCHK(h, hipEventSynchronize(h->wl_ev));  // the last upload has left the pinned buffer
+  if (items.size() > h->wl_pin_cap) {
+    if (h->wl_pin) (void)hipHostFree(h->wl_pin);
+    h->wl_pin = nullptr;
+    h->wl_pin_cap = 0;
+    const size_t cap = std::max<size_t>(items.size() + items.size() / 2, 4096);
+    HIPCHK(h, hipHostMalloc((void **)&h->wl_pin, cap * sizeof(apss::ProbeItem), hipHostMallocDefault));
+    h->wl_pin_cap = cap;
+  }
+  APSS_TRY(ensure(h, h->wl_dev, std::max<size_t>(items.size(), 1)));
+  if (!items.empty()) {
+    std::memcpy(h->wl_pin, items.data(), items.size() * sizeof(apss::ProbeItem));
+    HIPCHK(h, hipMemcpyAsync(h->wl_dev.p, h->wl_pin, items.size() * sizeof(apss::ProbeItem), hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHK(h, hipEventRecord(h->wl_ev, h->stream));
+  h->wl_keys = keys;
+  return APSS_OK;
+}
+
+// ---- one attempt: the launches over the whole index with the candidate list as it is ----
+// the lists the attempt fills, the counters at zero
+int32_t begin_attempt(apss_handle *h, Probe &pr) {
+  // chained: room for everything the candidate list can hold + every (query, waiting row) pair
+  // (sized for the longest tail there can be, once: the tail grows by a row per message)
+  if (pr.chain) APSS_TRY(h->fin.ensure(h, h->res.cap() + (size_t)(pr.q.nq * std::max<int64_t>(pr.p.tail_n, kTailMaxRows))));
+  if (pr.a.merge_log2 > 0) APSS_TRY(h->res2.ensure(h, h->res.cap(), 0, true));  // (k_expand_merged writes the pairs out of place)
+  pr.a.dbg = nullptr;
+  h->res.as_candidates(pr.a);
+  pr.a.res_cap = h->res.cap();
+  HIPCHK(h, hipMemsetAsync(h->counters.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
+  if (pr.xk.cut) HIPCHK(h, hipMemsetAsync(h->row_pairs.p, 0, (size_t)pr.q.nq * sizeof(uint32_t), h->stream));  // (every attempt: a re-run counts afresh)
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  return APSS_OK;
+}
+
+// the instantiation this call launches, spelled as rocprofv3 prints it (apss_stats.probe_kernel)
+void name_probe_kernel(apss_handle *h, const Probe &pr) {
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  char *nm = h->st.probe_kernel;
+  const size_t cap = sizeof(h->st.probe_kernel);
+  if (pr.p.coarse_path && pr.cxv.even)
+    if (pr.cxv.merge) snprintf(nm, cap, "k_probe_even_merged<%d, %s>", pr.cxv.u, tf(pr.cxv.acc8));
+    else snprintf(nm, cap, "k_probe_even<%d, %d, %d, %s, %s, %s>", pr.cxv.block, pr.cxv.u, pr.cxv.block <= 512 ? 128 : 256, tf(pr.cxv.shard), tf(pr.cxv.sgn), tf(pr.cxv.acc8));
+  else if (pr.p.coarse_path)
+    snprintf(nm, cap, "k_probe_coarse<%d, %d, %d, %d, %s, %d, %s, %s, %s, %s>", pr.cxv.block, pr.cxv.u, pr.cxv.block <= 512 ? 128 : 256,
+             pr.cxv.block <= 512 ? 512 : 1024, tf(pr.cxv.shard), pr.cxv.chunk, tf(pr.cxv.vrows), tf(pr.cxv.sgn), tf(pr.cxv.longpf), tf(pr.cxv.acc8));
+  else if (pr.xk.wave)
+    snprintf(nm, cap, "k_probe_wave<%d, %d, %d, %d, %s, %s>", pr.xk.block, pr.xk.u, pr.xk.longcap, pr.xk.survcap, tf(h->sharded), tf(h->dbgcfg.diag));
+  else if (pr.xk.cut)
+    snprintf(nm, cap, "k_probe<%d, %d, %s, true>", pr.p.mode, pr.xk.block, tf(pr.xk.fx));
+  else
+    snprintf(nm, cap, "k_probe<%d, %d, %s>", pr.p.mode, pr.xk.block, tf(pr.xk.fx));
+}
+
+// diagnostic build of k_probe_wave: in-kernel cycle stamps per round segment (shares only; never a benchmark number)
+int32_t launch_wave_diag(apss_handle *h, Probe &pr) {
+  APSS_TRY(ensure(h, h->dbg, 8));
+  HIPCHK(h, hipMemsetAsync(h->dbg.p, 0, 8 * sizeof(unsigned long long), h->stream));
+  pr.a.dbg = h->dbg.p;
+  APSS_TRY(launch_exact(h, wave_kernel(pr.xk.variant, h->sharded, true), pr.a, pr.xk.lds));
+  unsigned long long d[8];
+  HIPCHK(h, hipMemcpyAsync(d, h->dbg.p, sizeof(d), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned long long tot = 0;
+  for (int k = 0; k < 7; ++k) tot += d[k];
+  fprintf(stderr, "[apss diag] stage+flatten %.1f%% | atomics %.1f%% | longs/rest %.1f%% | barrier G %.1f%% | survivors %.1f%% | "
+                  "re-zero %.1f%% | barrier U %.1f%% | cycles/round/wave %.0f\n",
+          100.0 * d[0] / tot, 100.0 * d[1] / tot, 100.0 * d[2] / tot, 100.0 * d[3] / tot, 100.0 * d[4] / tot,
+          100.0 * d[5] / tot, 100.0 * d[6] / tot, (double)tot / ((double)pr.a.n_tiles * pr.a.nq * (pr.xk.block / kWave)));
+  return APSS_OK;
+}
+
+// one launch per group of tiles
+int32_t launch_tile_groups(apss_handle *h, Probe &pr, AttemptCounts &n) {
+  for (int64_t t0 = 0; t0 < pr.total_tiles; t0 += pr.tiles_per_launch, ++n.n_launches) {
+    pr.a.tile0 = (int32_t)t0;
+    pr.a.n_tiles = (int32_t)std::min<int64_t>(pr.tiles_per_launch, pr.total_tiles - t0);
+    if (pr.p.coarse_path && pr.persist) {
+      // (the work counter is zero behind the attempt's memset; a later launch of the call starts it again)
+      if (n.n_launches > 0) HIPCHK(h, hipMemsetAsync(h->counters.p + kCtrWork, 0, sizeof(unsigned long long), h->stream));
+      const int64_t n_items = h->wl_off[n.n_launches + 1] - h->wl_off[n.n_launches];
+      pr.a.items = h->wl_dev.p + h->wl_off[n.n_launches];
+      pr.a.n_items = (int32_t)n_items;
+      pr.a.work_ctr = h->counters.p + kCtrWork;
+      // never more workgroups than items
+      const int64_t wgs = std::min<int64_t>(n_items, h->dbgcfg.persist_wgs > 0 ? h->dbgcfg.persist_wgs : pr.persist_slots);
+      if (h->dbgcfg.diag)
+        fprintf(stderr, "[apss diag] persist: items %lld fine %lld workgroups %lld\n", (long long)n_items, (long long)h->wl_fine[n.n_launches], (long long)wgs);
+      if (wgs > 0) APSS_TRY(launch_cx(h, pr.cxv, pr.a, wgs));
+      n.thin_launches += 1;
+    } else if (pr.p.coarse_path) {
+      APSS_TRY(launch_cx(h, pr.cxv, pr.a));
+      n.thin_launches += pr.cxv.even ? 1 : 0;
+    } else if (pr.xk.wave && h->dbgcfg.diag) {
+      APSS_TRY(launch_wave_diag(h, pr));
+    } else if (pr.xk.wave) {
+      APSS_TRY(launch_exact(h, wave_kernel(pr.xk.variant, h->sharded, false), pr.a, pr.xk.lds));
+    } else {
+      APSS_TRY(launch_exact(h, gen_kernel(pr.p.mode, pr.xk.block, pr.xk.fx, pr.xk.cut), pr.a, pr.xk.lds));
     }
   }
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    if (chain) {  // (room for everything the candidate list can hold + every (query, waiting row) pair)
-      // (sized for the longest tail there can be, once: the tail grows by a row per message)
-      const size_t fin_cap = h->res_q.cap + (size_t)(nq * std::max<int64_t>(tail_n, kTailMaxRows));
-      APSS_TRY(ensure(h, h->fin_q, fin_cap));
-      APSS_TRY(ensure(h, h->fin_c, fin_cap));
-      APSS_TRY(ensure(h, h->fin_s, fin_cap));
-    }
-    if (a.merge_log2 > 0) {  // (k_expand_merged writes the pairs out of place)
-      APSS_TRY(ensure(h, h->res2_q, h->res_q.cap, 0, true));
-      APSS_TRY(ensure(h, h->res2_c, h->res_q.cap, 0, true));
-      APSS_TRY(ensure(h, h->res2_s, h->res_q.cap, 0, true));
-    }
-    a.dbg = nullptr;
-    a.res_q = h->res_q.p;
-    a.res_c = h->res_c.p;
-    a.res_s = h->res_s.p;
-    a.res_cap = h->res_q.cap;
-    HIPCHK(h, hipMemsetAsync(h->counters.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
-    if (gen_cut) HIPCHK(h, hipMemsetAsync(h->row_pairs.p, 0, (size_t)nq * sizeof(uint32_t), h->stream));  // (every attempt: a re-run counts afresh)
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    int64_t n_launches = 0, thin_launches = 0;
-    {  // the instantiation this call launches, spelled as rocprofv3 prints it (apss_stats.probe_kernel)
-      auto tf = [](bool b) { return b ? "true" : "false"; };
-      char *nm = h->st.probe_kernel;
-      const size_t cap = sizeof(h->st.probe_kernel);
-      if (coarse_path && cxv.even)
-        if (cxv.merge) snprintf(nm, cap, "k_probe_even_merged<%d, %s>", cxv.u, tf(cxv.acc8));
-        else snprintf(nm, cap, "k_probe_even<%d, %d, %d, %s, %s, %s>", cxv.block, cxv.u, cxv.block <= 512 ? 128 : 256, tf(cxv.shard), tf(cxv.sgn), tf(cxv.acc8));
-      else if (coarse_path)
-        snprintf(nm, cap, "k_probe_coarse<%d, %d, %d, %d, %s, %d, %s, %s, %s, %s>", cxv.block, cxv.u, cxv.block <= 512 ? 128 : 256,
-                 cxv.block <= 512 ? 512 : 1024, tf(cxv.shard), cxv.chunk, tf(cxv.vrows), tf(cxv.sgn), tf(cxv.longpf), tf(cxv.acc8));
-      else if (wave_path)
-        snprintf(nm, cap, "k_probe_wave<%d, %d, %d, %d, %s, %s>", wave_block, wave_u, wave_longcap, wave_survcap, tf(h->sharded), tf(dbg.diag));
-      else if (gen_cut)
-        snprintf(nm, cap, "k_probe<%d, %d, %s, true>", mode, gen_block(mode, h->ex.cb), tf(gen_fx));
-      else
-        snprintf(nm, cap, "k_probe<%d, %d, %s>", mode, gen_block(mode, h->ex.cb), tf(gen_fx));
-    }
-    for (int64_t t0 = 0; t0 < total_tiles; t0 += tiles_per_launch, ++n_launches) {
-      a.tile0 = (int32_t)t0;
-      a.n_tiles = (int32_t)std::min<int64_t>(tiles_per_launch, total_tiles - t0);
-      if (coarse_path && persist) {
-        // (the work counter is zero behind the memset above; a later launch of the call starts it again)
-        if (n_launches > 0) HIPCHK(h, hipMemsetAsync(h->counters.p + kCtrWork, 0, sizeof(unsigned long long), h->stream));
-        const int64_t n_items = h->wl_off[n_launches + 1] - h->wl_off[n_launches];
-        a.items = h->wl_dev.p + h->wl_off[n_launches];
-        a.n_items = (int32_t)n_items;
-        a.work_ctr = h->counters.p + kCtrWork;
-        // never more workgroups than items
-        const int64_t wgs = std::min<int64_t>(n_items, dbg.persist_wgs > 0 ? dbg.persist_wgs : persist_slots);
-        if (dbg.diag)
-          fprintf(stderr, "[apss diag] persist: items %lld fine %lld workgroups %lld\n", (long long)n_items, (long long)h->wl_fine[n_launches], (long long)wgs);
-        if (wgs > 0) APSS_TRY(launch_cx(h, cxv, a, wgs));
-        thin_launches += 1;
-      } else if (coarse_path) {
-        APSS_TRY(launch_cx(h, cxv, a));
-        thin_launches += cxv.even ? 1 : 0;
-      } else if (wave_path && dbg.diag) {
-        // diagnostic build: in-kernel cycle stamps per round segment (shares only; never a benchmark number)
-        APSS_TRY(ensure(h, h->dbg, 8));
-        HIPCHK(h, hipMemsetAsync(h->dbg.p, 0, 8 * sizeof(unsigned long long), h->stream));
-        a.dbg = h->dbg.p;
-        APSS_TRY(launch_wave(true));
-        unsigned long long d[8];
-        HIPCHK(h, hipMemcpyAsync(d, h->dbg.p, sizeof(d), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        unsigned long long tot = 0;
-        for (int k = 0; k < 7; ++k) tot += d[k];
-        fprintf(stderr, "[apss diag] stage+flatten %.1f%% | atomics %.1f%% | longs/rest %.1f%% | barrier G %.1f%% | survivors %.1f%% | "
-                        "re-zero %.1f%% | barrier U %.1f%% | cycles/round/wave %.0f\n",
-                100.0 * d[0] / tot, 100.0 * d[1] / tot, 100.0 * d[2] / tot, 100.0 * d[3] / tot, 100.0 * d[4] / tot,
-                100.0 * d[5] / tot, 100.0 * d[6] / tot, (double)tot / ((double)a.n_tiles * a.nq * (wave_block / kWave)));
-      } else if (wave_path) {
-        APSS_TRY(launch_wave(false));
-      } else if (gen_cut) {
-        const bool b512 = gen_block(2, h->ex.cb) == 512;
-        if (gen_fx && b512) APSS_TRY((launch_probe<2, true, 512, true>(h, a, lds)));
-        else if (gen_fx) APSS_TRY((launch_probe<2, true, kProbeBlock, true>(h, a, lds)));
-        else if (b512) APSS_TRY((launch_probe<2, false, 512, true>(h, a, lds)));
-        else APSS_TRY((launch_probe<2, false, kProbeBlock, true>(h, a, lds)));
-      } else if (gen_fx) {
-        if (mode == 0) APSS_TRY((launch_probe<0, true>(h, a, lds)));
-        else if (mode == 1) APSS_TRY((launch_probe<1, true>(h, a, lds)));
-        else if (gen_block(2, h->ex.cb) == 512) APSS_TRY((launch_probe<2, true, 512>(h, a, lds)));
-        else APSS_TRY((launch_probe<2, true>(h, a, lds)));
-      } else {
-        if (mode == 0) APSS_TRY((launch_probe<0, false>(h, a, lds)));
-        else if (mode == 1) APSS_TRY((launch_probe<1, false>(h, a, lds)));
-        else if (gen_block(2, h->ex.cb) == 512) APSS_TRY((launch_probe<2, false, 512>(h, a, lds)));
-        else APSS_TRY((launch_probe<2, false>(h, a, lds)));
-      }
-    }  // tile groups
-    if (a.merge_log2 > 0) {  // (round, candidate) -> the round's (query row, candidate) pairs
-      hipLaunchKernelGGL(k_counter_move, dim3(1), dim3(1), 0, h->stream, h->counters.p, (int)kCtrResults, (int)kCtrPre);
-      hipLaunchKernelGGL(k_expand_merged, dim3((unsigned)std::min<int64_t>(1024, ceil_div(nq / 4 + 4096, 256))), dim3(256), 0, h->stream, (const int32_t *)a.res_q, (const int32_t *)a.res_c, (const float *)a.res_s,
-                         (const unsigned long long *)(h->counters.p + kCtrPre), (uint64_t)a.res_cap, a.merge_log2, nq, q_ext, (const int64_t *)h->ext.p,
-                         h->res2_q.p, h->res2_c.p, h->res2_s.p, h->counters.p + kCtrResults, h->counters.p + kCtrOver);
-      HIPCHK(h, hipGetLastError());
-      std::swap(h->res_q, h->res2_q);
-      std::swap(h->res_c, h->res2_c);
-      std::swap(h->res_s, h->res2_s);
-      a.res_q = h->res_q.p;
-      a.res_c = h->res_c.p;
-      a.res_s = h->res_s.p;
-      a.res_cap = std::min(h->res_q.cap, h->res2_q.cap);
-      if (h->sharded && !dbg.no_merge_prune) {
-        // ... and only those of them that pass the shard rule on their EXACT partial score stay (k_shard_prune): the exchange
-        // gets no more candidates than without merging
-        hipLaunchKernelGGL(k_counter_move, dim3(1), dim3(1), 0, h->stream, h->counters.p, (int)kCtrResults, (int)kCtrPre);
-        ShardPruneArgs sp{};
-        sp.in_q = h->res_q.p;
-        sp.in_c = h->res_c.p;
-        sp.in_s = h->res_s.p;
-        sp.n_in = h->counters.p + kCtrPre;
-        sp.cap = a.res_cap;
-        sp.q_rowptr = s_rowptr;
-        sp.q_idx = s_idx;
-        sp.q_val = s_val;
-        sp.q_sub = q_sub;
-        sp.c_rowptr = h->head_k ? h->tv.rowptr.p : h->rowptr.p;
-        sp.c_idx = h->head_k ? h->tv.idx.p : h->idx.p;
-        sp.c_val = h->head_k ? h->tv.val.p : h->val.p;
-        sp.c_sub = h->sub.p;
-        sp.theta = (float)theta;
-        sp.out_q = h->res2_q.p;
-        sp.out_c = h->res2_c.p;
-        sp.out_s = h->res2_s.p;
-        sp.counter = h->counters.p + kCtrResults;
-        sp.over = h->counters.p + kCtrOver;
-        // (a grid for what a shard usually reports -- a fraction of a pair per query row; the kernel strides over whatever the counter holds)
-        const int64_t grid_pairs = std::min<int64_t>((int64_t)a.res_cap, nq / 4 + 4096);
-        hipLaunchKernelGGL(k_shard_prune, dim3((unsigned)std::min<int64_t>(2048, ceil_div(grid_pairs, kPrunePairs * 4))), dim3(kPruneBlock), 0, h->stream, sp);
-        HIPCHK(h, hipGetLastError());
-        std::swap(h->res_q, h->res2_q);
-        std::swap(h->res_c, h->res2_c);
-        std::swap(h->res_s, h->res2_s);
-        a.res_q = h->res_q.p;
-        a.res_c = h->res_c.p;
-        a.res_s = h->res_s.p;
-      }
-    }
-    if (tri) {
-      HIPCHK(h, hipMemcpyAsync(h->counters.p + kCtrSnap, h->counters.p + kCtrResults, sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
-      hipLaunchKernelGGL(k_mirror_survivors, dim3(1024), dim3(256), 0, h->stream, a.res_q, a.res_c, a.res_s,
-                         (const unsigned long long *)(h->counters.p + kCtrSnap), (uint64_t)a.res_cap, (int32_t)a.cb, h->counters.p + kCtrResults);
-      HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    unsigned long long cc_stack[kCtrCount] = {}, c_stack[kCtrCount];
-    unsigned long long *cc = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 128) : cc_stack;
-    unsigned long long *c = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 256) : c_stack;
-    for (int k = 0; k < kCtrCount; ++k) cc[k] = 0;
-    if (chain) {
-      HIPCHK(h, hipMemsetAsync(h->chain_ctr.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
-      RescoreArgs r{};
-      r.n_pairs = (int64_t)a.res_cap;
-      r.n_pairs_dev = h->counters.p + kCtrResults;
-      r.q_row = h->res_q.p;
-      r.c_slot = h->res_c.p;
-      r.q_rowptr = q_rowptr;
-      r.q_idx = q_idx;
-      r.q_val = q_val;
-      r.c_rowptr = h->rowptr.p;
-      r.c_idx = h->idx.p;
-      r.c_val = h->val.p;
-      r.theta = (float)theta;
-      r.out_q = h->fin_q.p;
-      r.out_c = h->fin_c.p;
-      r.out_s = h->fin_s.p;
-      r.out_count = h->chain_ctr.p + kCtrResults;
-      // (grid for what such a batch usually passes; the kernel strides over whatever the counter holds)
-      const int64_t grid_pairs = std::min<int64_t>((int64_t)a.res_cap, 64 * nq + 4096);
-      hipLaunchKernelGGL(k_rescore, dim3((unsigned)std::max<int64_t>(1, ceil_div(grid_pairs, (int64_t)kRescorePairs * kRescoreTrips))), dim3(kRescoreBlock), 0, h->stream, r);
-      if (tail_n > 0) {
-        TailArgs t{};
-        t.nq = nq;
-        t.n_tail = tail_n;
-        t.q_rowptr = q_rowptr;
-        t.q_idx = q_idx;
-        t.q_val = q_val;
-        t.q_ext = q_ext;
-        t.c_rowptr = h->rowptr.p;
-        t.c_idx = h->idx.p;
-        t.c_val = h->val.p;
-        t.c_ext = h->ext.p;
-        t.tail0 = h->idx_rows;
-        t.theta = (float)theta;
-        t.out_q = h->fin_q.p;
-        t.out_c = h->fin_c.p;
-        t.out_s = h->fin_s.p;
-        t.out_base = 0;  // (appends through the same counter as k_rescore: one list)
-        t.counters = h->chain_ctr.p;
-        hipLaunchKernelGGL(k_tail_score, dim3((unsigned)ceil_div(chain_tail_pairs * kGroup, 256)), dim3(256), 0, h->stream, t);
-      }
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(cc, h->chain_ctr.p, kCtrCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    }
-    unsigned long long sparse_results = 0, head_c[4] = {0, 0, 0, 0};
-    if (hybrid) {
-      // the dense half: same candidate list, same counter
-      HIPCHK(h, hipMemcpyAsync(&sparse_results, h->counters.p + kCtrResults, sizeof(sparse_results), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemsetAsync(h->head_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
-      HIPCHK(h, hipEventRecord(h->ev2, h->stream));
-      const bool stored = q_slot_base >= 0 && !head_outside;
-      APSS_TRY(run_head(h, a, nq, stored ? q_slot_base : -1, stored ? h->W.p : h->q_W.p, stored ? (int64_t)(h->W.cap / h->head_k) : ceil_div(nq, kHeadCTile) * kHeadCTile, head_thr, bound, h->idx_rows));
-      HIPCHK(h, hipEventRecord(h->ev3, h->stream));
-      HIPCHK(h, hipMemcpyAsync(head_c, h->head_ctr.p, sizeof(head_c), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipMemcpyAsync(c, h->counters.p, kCtrCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->st.probe_ms += ms;
-    h->st.probe_launches += n_launches;
-    h->st.thin_launches += thin_launches;
-    h->st.posting_visits = (int64_t)c[kCtrVisits];
-    h->st.device_posting_visits = (int64_t)(tri ? c[kCtrDevVisits] : c[kCtrVisits]);
-    h->st.symmetric = tri ? 1u : 0u;
-    h->st.candidate_pairs = (int64_t)c[kCtrCands];
-    // the speed paths count a stored query's touch of its own slot; it is not a (q, c != q) pair
-    if ((wave_path || coarse_path) && q_slot_base >= 0)
-      h->st.candidate_pairs -= h->win_nonempty >= 0 ? h->win_nonempty  // (a window of the batch: its own non-empty rows)
-                               : h->head_k > 0 ? ((q_slot_base == 0 && nq == h->n_rows) ? h->tv.nonempty : h->tv.last_nonempty)
-                                               : ((q_slot_base == 0 && nq == h->n_rows) ? h->store_nonempty : h->last_batch_nonempty);
-    if (hybrid) {
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev2, h->ev3));
-      h->st.head_ms += ms;
-      // positive elements of the contraction, minus a stored query's product with itself
-      int64_t self = 0;
-      if (q_slot_base >= 0)
-        self = h->win_head_nonempty >= 0 ? h->win_head_nonempty
-                                         : (q_slot_base == 0 && nq == h->n_rows) ? h->head_nonempty : h->last_batch_head_nonempty;
-      h->st.head_pairs = (int64_t)head_c[1] - self;
-      h->st.head_survivors = (int64_t)(c[kCtrResults] - sparse_results);
-      // a pair sharing head AND tail terms is scored by both filters; the distinct count lies between max and sum
-      h->st.candidate_pairs = std::max(h->st.candidate_pairs, h->st.head_pairs);
-    }
-    h->st.result_pairs = (int64_t)c[kCtrResults];
-    // (kCtrPre: the rounds the filter reported, or -- with the shard-rule test behind it -- the pairs they expanded to)
-    if (a.merge_log2 > 0 && (int64_t)c[kCtrPre] > (2 * nq + 100000) * (h->sharded && !dbg.no_merge_prune ? (1LL << a.merge_log2) : 1LL))
-      h->merge_off = true;  // (this call's list is right, the filter just passed too much)
-    if (cxv.acc8 && (int64_t)c[kCtrResults] > std::max<int64_t>(64 * nq, 4000000)) {
-      // the 8-bit filter turned out unselective on this data (skewed terms: chance pairs share dozens of them, and every
-      // shared term adds its unit of round-up): correct, but the survivors would swamp the exact pass.  Back to 16-bit
-      // accumulators, for good, and run the call again.
-      h->cx.cb = shard_rule ? 32768 : 65536;
-      h->cx.n_tiles = 0;
-      h->no_acc8 = true;
-      h->downgrades |= APSS_DOWNGRADE_ACC8;
-      APSS_TRY(build_index(h, 0));
-      return probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results);
-    }
-    if (std::max(c[kCtrResults], c[kCtrOver]) > a.res_cap) {
-      // the result list overflowed (or a list on the way to it did: kCtrOver): grow to what the run asked for and repeat the (idempotent) probe
-      const size_t asked = (size_t)std::max(c[kCtrResults], c[kCtrOver]);
-      size_t need = asked + asked / 8 + 1024;
-      if (tri) {
-        // a symmetric run whose FILTER overflowed mirrored only what the list held: the counter under-reports.  What the run
-        // needs is known all the same: the filter's own count (kCtrSnap, taken before the mirror) twice over, plus what the
-        // dense half appended -- asked for at once, instead of one more overflow per stage (each retry is a whole probe)
-        const size_t snap = (size_t)c[kCtrSnap];
-        const size_t head_part = hybrid && c[kCtrResults] > sparse_results ? (size_t)(c[kCtrResults] - sparse_results) : 0;
-        need = std::max(need, 2 * snap + head_part + (2 * snap + head_part) / 8 + 1024);
-      }
-      APSS_TRY(ensure(h, h->res_q, need, 0, true));
-      APSS_TRY(ensure(h, h->res_c, need, 0, true));
-      APSS_TRY(ensure(h, h->res_s, need, 0, true));
-      ++h->probe_reruns;
-      continue;
-    }
-    if (chain) {  // the exact pass has run already: its list is final
-      h->st.filter_survivors = (int64_t)c[kCtrResults];
-      h->n_res = (int64_t)cc[kCtrResults];
-      h->st.posting_visits += (int64_t)cc[kCtrVisits];
-      h->st.device_posting_visits += (int64_t)cc[kCtrVisits];
-      h->st.candidate_pairs += (int64_t)cc[kCtrCands];
-      h->st.result_pairs = h->n_res;
-      h->out_q = h->fin_q.p;
-      h->out_c = h->fin_c.p;
-      h->out_s = h->fin_s.p;
-      if (n_results) *n_results = h->n_res;
-      return APSS_OK;
-    }
-    h->n_res = (int64_t)c[kCtrResults];
-    if (gen_cut) {  // (kCtrPre, kCtrSnap: the uncut total and the rounds cut -- words k_probe<2> leaves alone otherwise)
-      h->cut_ran = true;
-      h->cut_uncut = (int64_t)c[kCtrPre];
-      h->cut_rounds = (int64_t)c[kCtrSnap];
-    }
-    h->out_q = h->res_q.p;
-    h->out_c = h->res_c.p;
-    h->out_s = h->res_s.p;
-    if (coarse_path && h->sharded) h->st.filter_survivors = h->n_res;  // a shard's survivors are its candidates (phase 2 scores them)
-    if (coarse_path && !h->sharded) APSS_TRY(exact_pass(h, hybrid, theta, nq, q_rowptr, q_idx, q_val, q_ext, tail_n));
+  return APSS_OK;
+}
+
+// merged rounds: (round, candidate) -> the round's (query row, candidate) pairs
+int32_t expand_merged_rounds(apss_handle *h, Probe &pr) {
+  hipLaunchKernelGGL(k_counter_move, dim3(1), dim3(1), 0, h->stream, h->counters.p, (int)kCtrResults, (int)kCtrPre);
+  hipLaunchKernelGGL(k_expand_merged, dim3((unsigned)std::min<int64_t>(1024, ceil_div(pr.q.nq / 4 + 4096, 256))), dim3(256), 0, h->stream, (const int32_t *)pr.a.res_q, (const int32_t *)pr.a.res_c, (const float *)pr.a.res_s,
+                     (const unsigned long long *)(h->counters.p + kCtrPre), (uint64_t)pr.a.res_cap, pr.a.merge_log2, pr.q.nq, pr.q.ext, (const int64_t *)h->ext.p,
+                     h->res2.q.p, h->res2.c.p, h->res2.s.p, h->counters.p + kCtrResults, h->counters.p + kCtrOver);
+  HIPCHK(h, hipGetLastError());
+  h->res.swap(h->res2);
+  h->res.as_candidates(pr.a);
+  pr.a.res_cap = std::min(h->res.cap(), h->res2.cap());
+  if (!(h->sharded && !h->dbgcfg.no_merge_prune)) return APSS_OK;
+  // ... and only those of them that pass the shard rule on their EXACT partial score stay (k_shard_prune): the exchange
+  // gets no more candidates than without merging
+  hipLaunchKernelGGL(k_counter_move, dim3(1), dim3(1), 0, h->stream, h->counters.p, (int)kCtrResults, (int)kCtrPre);
+  ShardPruneArgs sp{};
+  h->res.as_in(sp);
+  sp.n_in = h->counters.p + kCtrPre;
+  sp.cap = pr.a.res_cap;
+  sp.q_rowptr = pr.s.rowptr;
+  sp.q_idx = pr.s.idx;
+  sp.q_val = pr.s.val;
+  sp.q_sub = pr.p.q_sub;
+  sp.c_rowptr = h->head_k ? h->tv.rowptr.p : h->rowptr.p;
+  sp.c_idx = h->head_k ? h->tv.idx.p : h->idx.p;
+  sp.c_val = h->head_k ? h->tv.val.p : h->val.p;
+  sp.c_sub = h->sub.p;
+  sp.theta = (float)pr.p.theta;
+  h->res2.as_out(sp);
+  sp.counter = h->counters.p + kCtrResults;
+  sp.over = h->counters.p + kCtrOver;
+  // (a grid for what a shard usually reports -- a fraction of a pair per query row; the kernel strides over whatever the counter holds)
+  const int64_t grid_pairs = std::min<int64_t>((int64_t)pr.a.res_cap, pr.q.nq / 4 + 4096);
+  hipLaunchKernelGGL(k_shard_prune, dim3((unsigned)std::min<int64_t>(2048, ceil_div(grid_pairs, kPrunePairs * 4))), dim3(kPruneBlock), 0, h->stream, sp);
+  HIPCHK(h, hipGetLastError());
+  h->res.swap(h->res2);
+  h->res.as_candidates(pr.a);
+  return APSS_OK;
+}
+
+// a symmetric join: the other direction of every survivor
+int32_t mirror_survivors(apss_handle *h, const Probe &pr) {
+  HIPCHK(h, hipMemcpyAsync(h->counters.p + kCtrSnap, h->counters.p + kCtrResults, sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
+  hipLaunchKernelGGL(k_mirror_survivors, dim3(1024), dim3(256), 0, h->stream, pr.a.res_q, pr.a.res_c, pr.a.res_s,
+                     (const unsigned long long *)(h->counters.p + kCtrSnap), (uint64_t)pr.a.res_cap, (int32_t)pr.a.cb, h->counters.p + kCtrResults);
+  HIPCHK(h, hipGetLastError());
+  return APSS_OK;
+}
+
+// The exact pass CHAINED behind the filter (exact_pass is the same pass with its own host round trips): the pair count is read
+// on the device, the grid is sized for what such a batch usually passes, both kernels count in chain_ctr and append to ONE list
+int32_t chained_exact_pass(apss_handle *h, const Probe &pr, AttemptCounts &n) {
+  HIPCHK(h, hipMemsetAsync(h->chain_ctr.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
+  const RescoreArgs r = rescore_args(h, h->res.q.p, h->res.c.p, (int64_t)pr.a.res_cap, h->counters.p + kCtrResults, pr.q, (float)pr.p.theta, h->chain_ctr.p + kCtrResults);
+  // (the kernel strides over whatever the counter holds)
+  const int64_t grid_pairs = std::min<int64_t>((int64_t)pr.a.res_cap, 64 * pr.q.nq + 4096);
+  hipLaunchKernelGGL(k_rescore, rescore_grid(grid_pairs), dim3(kRescoreBlock), 0, h->stream, r);
+  if (pr.p.tail_n > 0) {
+    const TailArgs t = tail_args(h, pr.q, pr.p.tail_n, (float)pr.p.theta, 0, h->chain_ctr.p);  // (out_base 0: appends through the same counter as k_rescore)
+    hipLaunchKernelGGL(k_tail_score, dim3((unsigned)ceil_div(pr.q.nq * pr.p.tail_n * kGroup, 256)), dim3(256), 0, h->stream, t);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(n.cc, h->chain_ctr.p, kCtrCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  return APSS_OK;
+}
+
+// the dense half: same candidate list, same counter
+int32_t launch_head(apss_handle *h, const Probe &pr, AttemptCounts &n) {
+  HIPCHK(h, hipMemcpyAsync(&n.sparse_results, h->counters.p + kCtrResults, sizeof(n.sparse_results), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->head_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+  HIPCHK(h, hipEventRecord(h->ev2, h->stream));
+  const bool stored = pr.p.q_slot_base >= 0 && !pr.p.head_outside;
+  APSS_TRY(run_head(h, pr.a, pr.q.nq, stored ? pr.p.q_slot_base : -1, stored ? h->W.p : h->q_W.p, stored ? (int64_t)(h->W.cap / h->head_k) : ceil_div(pr.q.nq, kHeadCTile) * kHeadCTile, pr.p.head_thr, pr.p.bound, h->idx_rows));
+  HIPCHK(h, hipEventRecord(h->ev3, h->stream));
+  HIPCHK(h, hipMemcpyAsync(n.head_c, h->head_ctr.p, sizeof(n.head_c), hipMemcpyDeviceToHost, h->stream));
+  return APSS_OK;
+}
+
+// the call's one synchronisation: every counter of the attempt is on the host behind it
+int32_t read_counters(apss_handle *h, AttemptCounts &n) {
+  HIPCHK(h, hipMemcpyAsync(n.c, h->counters.p, kCtrCount * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return APSS_OK;
+}
+
+int32_t account_counters(apss_handle *h, const Probe &pr, const AttemptCounts &n) {
+  const bool tri = pr.a.tri != 0;
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->st.probe_ms += ms;
+  h->st.probe_launches += n.n_launches;
+  h->st.thin_launches += n.thin_launches;
+  h->st.posting_visits = (int64_t)n.c[kCtrVisits];
+  h->st.device_posting_visits = (int64_t)(tri ? n.c[kCtrDevVisits] : n.c[kCtrVisits]);
+  h->st.symmetric = tri ? 1u : 0u;
+  h->st.candidate_pairs = (int64_t)n.c[kCtrCands];
+  // the speed paths count a stored query's touch of its own slot; it is not a (q, c != q) pair
+  if ((pr.xk.wave || pr.p.coarse_path) && pr.p.q_slot_base >= 0)
+    h->st.candidate_pairs -= h->win_nonempty >= 0 ? h->win_nonempty  // (a window of the batch: its own non-empty rows)
+                             : h->head_k > 0 ? ((pr.p.q_slot_base == 0 && pr.q.nq == h->n_rows) ? h->tv.nonempty : h->tv.last_nonempty)
+                                             : ((pr.p.q_slot_base == 0 && pr.q.nq == h->n_rows) ? h->store_nonempty : h->last_batch_nonempty);
+  if (pr.p.hybrid) {
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev2, h->ev3));
+    h->st.head_ms += ms;
+    // positive elements of the contraction, minus a stored query's product with itself
+    int64_t self = 0;
+    if (pr.p.q_slot_base >= 0)
+      self = h->win_head_nonempty >= 0 ? h->win_head_nonempty
+                                       : (pr.p.q_slot_base == 0 && pr.q.nq == h->n_rows) ? h->head_nonempty : h->last_batch_head_nonempty;
+    h->st.head_pairs = (int64_t)n.head_c[1] - self;
+    h->st.head_survivors = (int64_t)(n.c[kCtrResults] - n.sparse_results);
+    // a pair sharing head AND tail terms is scored by both filters; the distinct count lies between max and sum
+    h->st.candidate_pairs = std::max(h->st.candidate_pairs, h->st.head_pairs);
+  }
+  h->st.result_pairs = (int64_t)n.c[kCtrResults];
+  // (kCtrPre: the rounds the filter reported, or -- with the shard-rule test behind it -- the pairs they expanded to)
+  if (pr.a.merge_log2 > 0 && (int64_t)n.c[kCtrPre] > (2 * pr.q.nq + 100000) * (h->sharded && !h->dbgcfg.no_merge_prune ? (1LL << pr.a.merge_log2) : 1LL))
+    h->merge_off = true;  // (this call's list is right, the filter just passed too much)
+  return APSS_OK;
+}
+
+// the result list overflowed (or a list on the way to it did: kCtrOver): grow to what the run asked for; the (idempotent) probe
+// is repeated
+int32_t grow_candidates(apss_handle *h, const Probe &pr, const AttemptCounts &n) {
+  const size_t asked = (size_t)std::max(n.c[kCtrResults], n.c[kCtrOver]);
+  size_t need = asked + asked / 8 + 1024;
+  if (pr.a.tri) {
+    // a symmetric run whose FILTER overflowed mirrored only what the list held: the counter under-reports.  What the run
+    // needs is known all the same: the filter's own count (kCtrSnap, taken before the mirror) twice over, plus what the
+    // dense half appended -- asked for at once, instead of one more overflow per stage (each retry is a whole probe)
+    const size_t snap = (size_t)n.c[kCtrSnap];
+    const size_t head_part = pr.p.hybrid && n.c[kCtrResults] > n.sparse_results ? (size_t)(n.c[kCtrResults] - n.sparse_results) : 0;
+    need = std::max(need, 2 * snap + head_part + (2 * snap + head_part) / 8 + 1024);
+  }
+  APSS_TRY(h->res.ensure(h, need, 0, true));
+  ++h->probe_reruns;
+  return kAttemptAgain;
+}
+
+// the attempt's list held everything: the call's final list and its last statistics
+int32_t finish_call(apss_handle *h, const Probe &pr, const AttemptCounts &n, int64_t *n_results) {
+  if (pr.chain) {  // the exact pass has run already: its list is final
+    h->st.filter_survivors = (int64_t)n.c[kCtrResults];
+    h->n_res = (int64_t)n.cc[kCtrResults];
+    h->st.posting_visits += (int64_t)n.cc[kCtrVisits];
+    h->st.device_posting_visits += (int64_t)n.cc[kCtrVisits];
+    h->st.candidate_pairs += (int64_t)n.cc[kCtrCands];
+    h->st.result_pairs = h->n_res;
+    h->fin.as_out(*h);
     if (n_results) *n_results = h->n_res;
     return APSS_OK;
   }
+  h->n_res = (int64_t)n.c[kCtrResults];
+  if (pr.xk.cut) {  // (kCtrPre, kCtrSnap: the uncut total and the rounds cut -- words k_probe<2> leaves alone otherwise)
+    h->cut_ran = true;
+    h->cut_uncut = (int64_t)n.c[kCtrPre];
+    h->cut_rounds = (int64_t)n.c[kCtrSnap];
+  }
+  h->res.as_out(*h);
+  if (pr.p.coarse_path && h->sharded) h->st.filter_survivors = h->n_res;  // a shard's survivors are its candidates (phase 2 scores them)
+  if (pr.p.coarse_path && !h->sharded) APSS_TRY(exact_pass(h, pr.p.hybrid, pr.p.theta, pr.q, pr.p.tail_n));
+  if (n_results) *n_results = h->n_res;
+  return APSS_OK;
+}
+
+// One attempt.  APSS_OK: the call is finished; kAttemptAgain: the list was grown; kProbeAgain: the 8-bit filter was dropped
+int32_t run_attempt(apss_handle *h, Probe &pr, int64_t *n_results) {
+  AttemptCounts n;
+  // (the small reads land in the pinned staging's scalar slots where there is one)
+  n.cc = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 128) : n.cc_stack;
+  n.c = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 256) : n.c_stack;
+  APSS_TRY(begin_attempt(h, pr));
+  name_probe_kernel(h, pr);
+  APSS_TRY(launch_tile_groups(h, pr, n));
+  if (pr.a.merge_log2 > 0) APSS_TRY(expand_merged_rounds(h, pr));
+  if (pr.a.tri) APSS_TRY(mirror_survivors(h, pr));
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  for (int k = 0; k < kCtrCount; ++k) n.cc[k] = 0;
+  if (pr.chain) APSS_TRY(chained_exact_pass(h, pr, n));
+  if (pr.p.hybrid) APSS_TRY(launch_head(h, pr, n));
+  APSS_TRY(read_counters(h, n));
+  APSS_TRY(account_counters(h, pr, n));
+  // the 8-bit filter turned out unselective on this data (skewed terms: chance pairs share dozens of them, and every
+  // shared term adds its unit of round-up): correct, but the survivors would swamp the exact pass.  Back to 16-bit
+  // accumulators, for good, and run the call again.
+  if (pr.cxv.acc8 && (int64_t)n.c[kCtrResults] > std::max<int64_t>(64 * pr.q.nq, 4000000)) return drop_acc8(h, pr.p.shard_rule);
+  if (std::max(n.c[kCtrResults], n.c[kCtrOver]) > pr.a.res_cap) return grow_candidates(h, pr, n);
+  return finish_call(h, pr, n, n_results);
+}
+
+// One pass of the call.  kProbeAgain: a downgrade was latched and the index rebuilt (no room for 8-bit sums, waiting rows folded
+// into the index, dense head blocked, 8-bit filter unselective) -- the call runs again
+int32_t probe_pass(apss_handle *h, Probe &pr, int64_t *n_results) {
+  APSS_TRY(reset_call(h, pr, n_results));
+  if (pr.q.nq == 0 || h->n_rows == 0 || pr.q_nnz_end <= 0 || h->nnz == 0) return APSS_OK;  // nothing can share a term
+  if (pr.q.nq > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "query batch too large");
+  APSS_TRY(stage_rows(h, pr));
+  APSS_TRY(choose_path(h, pr));
+  APSS_TRY(fill_probe_args(h, pr));
+  APSS_TRY(choose_exact_kernel(h, pr));
+  APSS_TRY(plan_merged_rounds(h, pr));
+  decide_symmetry(h, pr);
+  if (pr.a.merge_log2 > 0) APSS_TRY(stage_merged_rows(h, pr));
+  const int vrow_part = 512;
+  if (pr.p.coarse_path && pr.s.max_nnz > vrow_part) APSS_TRY(cut_long_queries(h, pr.s.rowptr, pr.q.nq, vrow_part, pr.a));
+  APSS_TRY(size_launches(h, pr));
+  APSS_TRY(prepare_work_lists(h, pr));
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    const int32_t rc = run_attempt(h, pr, n_results);
+    if (rc != kAttemptAgain) return rc;
+  }
   return fail(h, APSS_E_STATE, "result buffer kept overflowing");
+}
+
+// Every repeat follows a one-way latch (no_acc8, head_blocked, idx_rows == n_rows): at most three of them
+int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+                    int64_t q_nnz_end, int64_t *n_results) {
+  Probe pr{QueryRows{nq, q_rowptr, q_idx, q_val, q_ext}, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end};
+  for (int pass = 0; pass < 4; ++pass) {
+    const int32_t rc = probe_pass(h, pr, n_results);
+    if (rc != kProbeAgain) return rc;
+  }
+  return fail(h, APSS_E_STATE, "the call kept downgrading the index");
 }
 
 // The cut of one final list (the call's, or a window's): h->out_* / h->n_res become the kept list, *info says what was done.
@@ -2924,7 +3015,24 @@ int32_t plan_windows(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const 
   return APSS_OK;
 }
 
-// A query-type call: the join (probe_inner re-enters itself after a downgrade or a rebuild; what it leaves is the call's final
+// the statistics of a windowed call that are sums over its windows
+template <class F>
+void for_summed_stats(apss_stats &a, const apss_stats &b, F f) {
+  f(a.posting_visits, b.posting_visits);
+  f(a.device_posting_visits, b.device_posting_visits);
+  f(a.candidate_pairs, b.candidate_pairs);
+  f(a.filter_survivors, b.filter_survivors);
+  f(a.probe_launches, b.probe_launches);
+  f(a.thin_launches, b.thin_launches);
+  f(a.probe_ms, b.probe_ms);
+  f(a.rescore_ms, b.rescore_ms);
+  f(a.head_ms, b.head_ms);
+  f(a.head_flops, b.head_flops);
+  f(a.head_pairs, b.head_pairs);
+  f(a.head_survivors, b.head_survivors);
+}
+
+// A query-type call: the join (probe_inner runs its pass again after a downgrade or a rebuild; what it leaves is the call's final
 // list), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
 // apss_set_top_k_window, join and pass window by window over the query rows (apss_window.hpp), the kept lists concatenated.
 int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
@@ -2968,16 +3076,12 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     for (int64_t q = 0; q < nq; ++q) s += std::min<int64_t>(hb[(size_t)q], h->top_k);
     return s;
   }();
-  APSS_TRY(ensure(h, h->win_q, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
-  APSS_TRY(ensure(h, h->win_c, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
-  APSS_TRY(ensure(h, h->win_s, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
+  APSS_TRY(h->win.ensure(h, (size_t)std::max<int64_t>(kept_max, 1), 0, true));
   if (h->dbgcfg.res_cap <= 0) {
     // no window overflows its candidate list: the bound holds for the filters' survivors too (twice with a dense-head block,
     // whose two filters may both pass a pair)
     const size_t need = (size_t)std::max<int64_t>(1, h->tw.bound_window_max * (h->head_k > 0 ? 2 : 1));
-    APSS_TRY(ensure(h, h->res_q, need, 0, true));
-    APSS_TRY(ensure(h, h->res_c, need, 0, true));
-    APSS_TRY(ensure(h, h->res_s, need, 0, true));
+    APSS_TRY(h->res.ensure(h, need, 0, true));
   }
   apss_stats sum{};
   apss_topk_info tk{};
@@ -2999,18 +3103,7 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     if (h->probe_reruns > reruns) ++h->tw.overflow_reruns;
     note_cut();
     h->tw.pairs_window_max = std::max(h->tw.pairs_window_max, h->n_res);
-    sum.posting_visits += h->st.posting_visits;
-    sum.device_posting_visits += h->st.device_posting_visits;
-    sum.candidate_pairs += h->st.candidate_pairs;
-    sum.filter_survivors += h->st.filter_survivors;
-    sum.probe_launches += h->st.probe_launches;
-    sum.thin_launches += h->st.thin_launches;
-    sum.probe_ms += h->st.probe_ms;
-    sum.rescore_ms += h->st.rescore_ms;
-    sum.head_ms += h->st.head_ms;
-    sum.head_flops += h->st.head_flops;
-    sum.head_pairs += h->st.head_pairs;
-    sum.head_survivors += h->st.head_survivors;
+    for_summed_stats(sum, h->st, [](auto &s, const auto &v) { s += v; });
     apss_topk_info one{};
     rc = cut_final_list(h, r1 - r0, &one);
     if (rc != APSS_OK) break;
@@ -3021,12 +3114,12 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     tk.select_ms += one.select_ms;
     tk.select_launches += one.select_launches;
     if (h->n_res > 0) {
-      if (n_out + h->n_res > (int64_t)h->win_q.cap) {  // (cannot happen: a row keeps at most min(b, k) pairs)
+      if (n_out + h->n_res > (int64_t)h->win.cap()) {  // (cannot happen: a row keeps at most min(b, k) pairs)
         rc = fail(h, APSS_E_STATE, "a window kept more pairs than its rows' bounds allow");
         break;
       }
       hipLaunchKernelGGL(k_win_append, dim3((unsigned)std::min<int64_t>(4096, ceil_div(h->n_res, kWinThreads))), dim3(kWinThreads), 0, h->stream,
-                         h->out_q, h->out_c, h->out_s, h->n_res, (int32_t)r0, h->win_q.p + n_out, h->win_c.p + n_out, h->win_s.p + n_out);
+                         h->out_q, h->out_c, h->out_s, h->n_res, (int32_t)r0, h->win.q.p + n_out, h->win.c.p + n_out, h->win.s.p + n_out);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) {
         rc = fail(h, APSS_E_DEVICE, std::string("k_win_append: ") + hipGetErrorString(e));
@@ -3050,22 +3143,9 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     h->n_res = -1;
     return rc;
   }
-  h->st.posting_visits = sum.posting_visits;
-  h->st.device_posting_visits = sum.device_posting_visits;
-  h->st.candidate_pairs = sum.candidate_pairs;
-  h->st.filter_survivors = sum.filter_survivors;
-  h->st.probe_launches = sum.probe_launches;
-  h->st.thin_launches = sum.thin_launches;
-  h->st.probe_ms = sum.probe_ms;
-  h->st.rescore_ms = sum.rescore_ms;
-  h->st.head_ms = sum.head_ms;
-  h->st.head_flops = sum.head_flops;
-  h->st.head_pairs = sum.head_pairs;
-  h->st.head_survivors = sum.head_survivors;
+  for_summed_stats(h->st, sum, [](auto &s, const auto &v) { s = v; });
   h->tk = tk;
-  h->out_q = h->win_q.p;
-  h->out_c = h->win_c.p;
-  h->out_s = h->win_s.p;
+  h->win.as_out(*h);
   h->n_res = n_out;
   h->st.result_pairs = n_out;
   if (n_results) *n_results = n_out;
@@ -3328,17 +3408,17 @@ void apss_destroy(apss_handle *h) {
   if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
   release(h->rowptr); release(h->ext); release(h->idx); release(h->erow); release(h->val); release(h->sub);
   for (apss_handle::IndexSet *s : {&h->ex, &h->cx}) { release(s->seg); release(s->post); release(s->post_c); release(s->base); release(s->total); release(s->maxlen); release(s->chunkw); release(s->scan_part); }
-  release(h->tile_min); release(h->tile_min_c); release(h->fin_q); release(h->fin_c); release(h->fin_s);
+  release(h->tile_min); release(h->tile_min_c); h->fin.release();
   release(h->q_rowptr); release(h->q_ext); release(h->q_idx); release(h->q_val); release(h->q_sub);
   release(h->s_keep); release(h->s_cnt); release(h->s_rowdst); release(h->s_nnzdst); release(h->scan_tmp);
   release(h->in_rowptr); release(h->in_ext); release(h->in_idx); release(h->s_inv); release(h->s_sub); release(h->in_val); release(h->in_val64); release(h->vq_first); release(h->vrow_q); release(h->vrow_ptr); release(h->vrow_np); release(h->vrow_first);
-  release(h->res_q); release(h->res_c); release(h->res_s); release(h->res2_q); release(h->res2_c); release(h->res2_s); release(h->q_prenorm); release(h->counters); release(h->flagword); release(h->dbg);
+  h->res.release(); h->res2.release(); release(h->q_prenorm); release(h->counters); release(h->flagword); release(h->dbg);
   release(h->head_pos); release(h->W);
   for (apss_handle::TailView *v : {&h->tv, &h->qtv}) { release(v->rowptr); release(v->idx); release(v->val); release(v->erow); }
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
-  release(h->head_ctr); release(h->uq_q); release(h->uq_c); release(h->uq_s); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
+  release(h->head_ctr); h->uq.release(); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
-  release(h->win_df); release(h->win_b); release(h->win_q); release(h->win_c); release(h->win_s);
+  release(h->win_df); release(h->win_b); h->win.release();
   release(h->row_pairs);
   if (h->pin) (void)hipHostFree(h->pin);
   release(h->wl_dev);
