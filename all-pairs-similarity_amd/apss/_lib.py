@@ -31,8 +31,11 @@ SYMBOLS = [
     "apss_set_top_k_window", "apss_topk_window_get", "apss_topk_window_cuts",
     # ... with each round cut inside the theta <= 0 probe kernel
     "apss_set_top_k_tile_cut", "apss_topk_tile_cut_get",
+    # removal of stored vectors (csrc/apss_remove.hpp)
+    "apss_remove", "apss_remove_dev", "apss_compact", "apss_set_auto_compact", "apss_removal_get",
 ]
 TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
+TILE_CUT_REMOVED = 4
 GROUP_FORCE_EXCHANGE, GROUP_NO_RCCL, GROUP_ADAPT_LAYOUT = 1, 2, 4
 GROUP_NO_SYMMETRIC_RANGES = 8
 EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
@@ -102,6 +105,13 @@ class TopkWindowInfo(C.Structure):
 class TopkTileCutInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("applied", C.c_int32), ("declined", C.c_int32), ("prefix_bits", C.c_int32),
                 ("pairs_emitted", C.c_int64), ("rounds_cut", C.c_int64)]
+
+
+class RemovalInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("compactions", C.c_int32), ("rows_removed", C.c_int64), ("rows_live", C.c_int64),
+                ("removed_total", C.c_int64), ("pairs_dropped", C.c_int64), ("compacted_rows", C.c_int64),
+                ("auto_compact", C.c_double), ("mark_ms", C.c_double), ("drop_ms", C.c_double), ("compact_ms", C.c_double),
+                ("drop_launches", C.c_int32), ("reserved0", C.c_int32)]
 
 
 def build_sources():
@@ -266,5 +276,15 @@ def lib():
     L.apss_set_top_k_tile_cut.argtypes = [vp, i32]
     L.apss_topk_tile_cut_get.restype = i32
     L.apss_topk_tile_cut_get.argtypes = [vp, C.POINTER(TopkTileCutInfo)]
+    for name in ("apss_remove", "apss_remove_dev"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i64, vp, pi64]
+    L.apss_compact.restype = i32
+    L.apss_compact.argtypes = [vp]
+    L.apss_set_auto_compact.restype = i32
+    L.apss_set_auto_compact.argtypes = [vp, C.c_double]
+    L.apss_removal_get.restype = i32
+    L.apss_removal_get.argtypes = [vp, C.POINTER(RemovalInfo)]
     _lib = L
     return L

@@ -26,7 +26,8 @@ def _ptr(a):
 
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
-                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False):
+                 capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False,
+                 auto_compact=0.0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -47,8 +48,10 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
-        if top_k or top_k_window or top_k_tile_cut:
+        if top_k or top_k_window or top_k_tile_cut or auto_compact:
             try:
+                if auto_compact:
+                    self.set_auto_compact(auto_compact)
                 if top_k_window:
                     self.set_top_k_window(top_k_window)
                 if top_k_tile_cut:
@@ -181,6 +184,37 @@ class ApssIndex:
         if n.value:
             self._chk(self._L.apss_topk_window_cuts(self._h, n.value, _ptr(cuts), C.byref(n)))
         return cuts
+
+    def remove(self, ids):
+        """mark every stored row whose external id is in `ids` (numpy / a sequence, or an int64 torch tensor on this handle's
+        GPU) as removed: query-type calls made from now on answer as if those rows were not stored.  Returns the rows newly
+        marked (ids that are not stored, already removed or repeated count for nothing)"""
+        n = C.c_int64(0)
+        if hasattr(ids, "data_ptr"):
+            import torch
+            assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+            ptr = C.c_void_p(ids.data_ptr()) if ids.numel() else C.c_void_p(0)
+            self._chk(self._L.apss_remove_dev(self._h, ids.numel(), ptr, C.byref(n)))
+        else:
+            ids = _np(ids, np.int64)
+            self._chk(self._L.apss_remove(self._h, ids.size, _ptr(ids), C.byref(n)))
+        return n.value
+
+    def compact(self):
+        """the store becomes its live rows in stored order and the index is rebuilt, on the device (apss_compact); the last
+        call's results are gone afterwards.  Nothing marked: a no-op"""
+        self._chk(self._L.apss_compact(self._h))
+
+    def set_auto_compact(self, fraction):
+        """compact at the start of an insert-type call once more than `fraction` of the stored rows is marked (0: off)"""
+        self._chk(self._L.apss_set_auto_compact(self._h, float(fraction)))
+
+    def removal_info(self):
+        """marks, compactions and what the last query-type call dropped (apss_removal_info)"""
+        ri = _lib.RemovalInfo()
+        ri.struct_size = C.sizeof(_lib.RemovalInfo)
+        self._chk(self._L.apss_removal_get(self._h, C.byref(ri)))
+        return {k: getattr(ri, k) for k, _ in _lib.RemovalInfo._fields_}
 
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`

@@ -21,6 +21,9 @@
 #include "apss_even.hpp"
 #include "apss_topk.hpp"
 #include "apss_window.hpp"
+#include "apss_remove.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace apss;
 
@@ -348,6 +351,18 @@ struct apss_handle {
   DevBuf<uint32_t> row_pairs;  // [nq]
   apss_topk_tile_cut_info tci{};
   int64_t probe_reruns = 0;    // probes that ran again because a list overflowed, since create
+  // removal (apss_remove.hpp): one mark byte per slot -- slots [0, dead_rows) have one, rows stored since then are live and get
+  // theirs (0) when the map is next needed --, the rows marked now, the sorted removal list and the sort's scratch, the filtered
+  // final list of a query-type call, what the last calls did
+  DevBuf<uint8_t> dead;
+  int64_t dead_rows = 0, rm_marked = 0;
+  DevBuf<int64_t> rm_ids, rm_sorted;
+  DevBuf<char> rm_tmp;
+  DevBuf<unsigned long long> rm_ctr;  // [1] rows newly marked / pairs kept
+  PairList rm_out;
+  hipEvent_t rm_ev0 = nullptr, rm_ev1 = nullptr;  // (created by the first apss_remove)
+  double auto_compact = 0.0;
+  apss_removal_info ri{};
   // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
@@ -2445,7 +2460,8 @@ int32_t choose_exact_kernel(apss_handle *h, Probe &pr) {
   pr.xk.fx = !pr.p.coarse_path && !pr.xk.wave && pr.p.fx_scale > 0;
   pr.xk.block = pr.xk.wave ? wave_block : gen_block(pr.p.mode, h->ex.cb);
   // the per-round cut (apss_set_top_k_tile_cut): only where the uncut list is the problem, k_probe<2> of a plain handle
-  pr.xk.cut = h->tile_cut && h->top_k > 0 && !h->sharded && !pr.p.coarse_path && !pr.xk.wave && pr.p.mode == 2;
+  // (not while rows are marked removed: a round's k-th score could belong to one of them)
+  pr.xk.cut = h->tile_cut && h->top_k > 0 && !h->sharded && !pr.p.coarse_path && !pr.xk.wave && pr.p.mode == 2 && h->rm_marked == 0;
   if (pr.xk.cut) {
     APSS_TRY(ensure(h, h->row_pairs, (size_t)pr.q.nq));
     pr.a.row_pairs = h->row_pairs.p;
@@ -3032,8 +3048,63 @@ void for_summed_stats(apss_stats &a, const apss_stats &b, F f) {
   f(a.head_survivors, b.head_survivors);
 }
 
+// ---- removal (apss_remove.hpp) ----
+// every slot of the store gets its mark byte: rows stored since the map was last extended are live
+int32_t rm_extend(apss_handle *h) {
+  if (h->dead_rows >= h->n_rows && h->dead.p) return APSS_OK;
+  APSS_TRY(ensure(h, h->dead, (size_t)std::max<int64_t>(h->n_rows, 1), (size_t)h->dead_rows));
+  if (h->n_rows > h->dead_rows)
+    HIPCHK(h, hipMemsetAsync(h->dead.p + h->dead_rows, 0, (size_t)(h->n_rows - h->dead_rows), h->stream));
+  h->dead_rows = h->n_rows;
+  return APSS_OK;
+}
+
+int32_t rm_events(apss_handle *h) {
+  if (!h->rm_ev0) HIPCHK(h, hipEventCreate(&h->rm_ev0));
+  if (!h->rm_ev1) HIPCHK(h, hipEventCreate(&h->rm_ev1));
+  return APSS_OK;
+}
+
+// The final list of a query-type call (or of one window) without the pairs that touch a marked row: h->out_* / h->n_res become
+// the filtered list.  Runs only while rows are marked; q_slot_first >= 0: the query rows are stored rows from that slot on.
+int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
+  if (h->rm_marked <= 0 || h->n_res <= 0) return APSS_OK;
+  APSS_TRY(rm_extend(h));
+  APSS_TRY(h->rm_out.ensure(h, (size_t)h->n_res));
+  APSS_TRY(ensure(h, h->rm_ctr, 1));
+  HIPCHK(h, hipMemsetAsync(h->rm_ctr.p, 0, sizeof(unsigned long long), h->stream));
+  RmDropArgs a{};
+  a.in_q = h->out_q;
+  a.in_c = h->out_c;
+  a.in_s = h->out_s;
+  a.n = h->n_res;
+  a.dead = h->dead.p;
+  a.rows = h->n_rows;
+  a.q_slot_first = q_slot_first;
+  h->rm_out.as_out(a);
+  a.kept = h->rm_ctr.p;
+  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
+  const int64_t blocks = ceil_div(h->n_res, (int64_t)kRmThreads * kRmItems);
+  hipLaunchKernelGGL(k_rm_drop, dim3((unsigned)std::min<int64_t>(blocks, 16384)), dim3(kRmThreads), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
+  unsigned long long kept_stack = 0;
+  unsigned long long *kept = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 512) : &kept_stack;
+  HIPCHK(h, hipMemcpyAsync(kept, h->rm_ctr.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  if ((int64_t)*kept > h->n_res) return fail(h, APSS_E_STATE, "the removal filter kept more pairs than it was given");
+  h->ri.pairs_dropped += h->n_res - (int64_t)*kept;
+  h->ri.drop_ms += ms;
+  ++h->ri.drop_launches;
+  h->rm_out.as_out(*h);
+  h->n_res = (int64_t)*kept;
+  return APSS_OK;
+}
+
 // A query-type call: the join (probe_inner runs its pass again after a downgrade or a rebuild; what it leaves is the call's final
-// list), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
+// list), then, while rows are marked removed, ONE filter of that list (apss_remove.hpp), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
 // apss_set_top_k_window, join and pass window by window over the query rows (apss_window.hpp), the kept lists concatenated.
 int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
               const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
@@ -3044,7 +3115,13 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
   h->win_cuts.clear();
   h->tci = apss_topk_tile_cut_info{};
   h->tci.prefix_bits = 16;
-  h->tci.declined = !h->tile_cut ? APSS_TILE_CUT_OFF : (h->top_k <= 0 ? APSS_TILE_CUT_NO_K : APSS_TILE_CUT_PATH);
+  h->tci.declined = !h->tile_cut ? APSS_TILE_CUT_OFF
+                    : h->top_k <= 0 ? APSS_TILE_CUT_NO_K
+                    : h->rm_marked > 0 ? APSS_TILE_CUT_REMOVED  // (choose_exact_kernel: a round's k-th score could be a marked row's)
+                                       : APSS_TILE_CUT_PATH;
+  h->ri.pairs_dropped = 0;
+  h->ri.drop_ms = 0;
+  h->ri.drop_launches = 0;
   auto note_cut = [h]() {  // after a probe_inner: what its probe emitted and cut (the sum over a call's windows)
     h->tci.pairs_emitted += h->n_res;
     h->tci.rounds_cut += h->cut_rounds;
@@ -3057,6 +3134,11 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
   if (!windowed) {
     APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
     note_cut();
+    if (h->rm_marked > 0) {
+      APSS_TRY(drop_removed(h, q_slot_first));
+      h->st.result_pairs = h->n_res;
+      if (n_results) *n_results = h->n_res;
+    }
     h->tk.pairs_over_theta = h->tk.kept = h->n_res;
     if (h->top_k <= 0 || h->sharded) return APSS_OK;
     APSS_TRY(cut_final_list(h, nq, &h->tk));
@@ -3104,6 +3186,10 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
     note_cut();
     h->tw.pairs_window_max = std::max(h->tw.pairs_window_max, h->n_res);
     for_summed_stats(sum, h->st, [](auto &s, const auto &v) { s += v; });
+    if (h->rm_marked > 0) {  // the window's list loses its removed rows before its cut
+      rc = drop_removed(h, q_slot_first < 0 ? -1 : q_slot_first + r0);
+      if (rc != APSS_OK) break;
+    }
     apss_topk_info one{};
     rc = cut_final_list(h, r1 - r0, &one);
     if (rc != APSS_OK) break;
@@ -3302,6 +3388,143 @@ int32_t query_dev_impl(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_
                n_results);
 }
 
+// apss_clear: the index, the store and the marks go, the reservations and the settings stay
+int32_t clear_impl(apss_handle *h) {
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->n_rows = 0;
+  h->idx_rows = 0;
+  h->nnz = 0;
+  h->n_tiles = 0;
+  for (apss_handle::IndexSet *s : {&h->ex, &h->cx}) { s->n_tiles = 0; s->post_used = 0; s->h_base.clear(); s->built_rows = 0; }
+  h->ex_built_rows = 0;
+  h->n_res = -1;
+  h->res_q_ext = nullptr;
+  h->last_q_rowptr = nullptr;
+  h->last_q_idx = nullptr;
+  h->last_q_val = nullptr;
+  h->last_nq = 0;
+  h->nonneg = true;
+  h->q_nonneg = true;
+  h->no_acc8 = h->dbgcfg.no_acc8;
+  h->merge_off = false;
+  h->downgrades = 0;
+  h->store_max_nnz = 0;
+  h->store_max_norm2 = 0.f;
+  h->store_nonempty = 0;
+  if (!h->head_fixed) {  // (terms set through apss_set_head_terms are configuration: they outlive the data)
+    h->head_k = 0;
+    h->head_terms.clear();
+  }
+  h->head_eval_rows = 0;
+  h->head_blocked = false;
+  h->head_nonempty = 0;
+  h->cut_lo = h->cut_hi = 0;
+  h->df_rows = -1;
+  h->rm_marked = 0;  // (the marks belong to slots, and the slots are gone)
+  h->dead_rows = 0;
+  return APSS_OK;
+}
+
+int32_t refuse_shard_removal(apss_handle *h, const char *what) {
+  return fail(h, APSS_E_UNSUPPORTED, std::string(what) + ": not on a term shard (it holds slices of rows; a compaction needs whole ones)");
+}
+
+// marks the stored rows whose external id is in d_ids[0, n) (device); *newly = rows that were live before
+int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *newly) {
+  *newly = 0;
+  if (n == 0 || h->n_rows == 0) return APSS_OK;
+  if (n > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "apss_remove: more than 2^31 - 1 ids in one call");
+  APSS_TRY(rm_events(h));
+  APSS_TRY(rm_extend(h));
+  APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
+  APSS_TRY(ensure(h, h->rm_ctr, 1));
+  size_t tmp_bytes = 0;
+  HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+  APSS_TRY(ensure(h, h->rm_tmp, tmp_bytes + 256));
+  HIPCHK(h, hipMemsetAsync(h->rm_ctr.p, 0, sizeof(unsigned long long), h->stream));
+  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
+  HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+  // (two rows per thread; the workgroups loop: one global add each)
+  const int64_t blocks = ceil_div(ceil_div(h->n_rows, 2), kRmThreads);
+  hipLaunchKernelGGL(k_rm_mark, dim3((unsigned)std::min<int64_t>(blocks, 4096)), dim3(kRmThreads), 0, h->stream, (const int64_t *)h->ext.p, h->n_rows,
+                     (const int64_t *)h->rm_sorted.p, n, h->dead.p, h->rm_ctr.p);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
+  unsigned long long marked = 0;
+  HIPCHK(h, hipMemcpyAsync(&marked, h->rm_ctr.p, sizeof(marked), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  h->ri.mark_ms = ms;
+  h->rm_marked += (int64_t)marked;
+  h->ri.removed_total += (int64_t)marked;
+  *newly = (int64_t)marked;
+  return APSS_OK;
+}
+
+// The live rows, gathered on the device into the input staging (k_rm_rows -> the handle's scan -> k_rm_gather), then what
+// apss_clear + apss_insert_stored_dev of them does.  A failure behind the clear leaves an empty handle and the error.
+int32_t compact_impl(apss_handle *h) {
+  if (h->rm_marked <= 0) return APSS_OK;
+  const int64_t n = h->n_rows, marked = h->rm_marked;
+  APSS_TRY(rm_events(h));
+  APSS_TRY(rm_extend(h));
+  APSS_TRY(ensure(h, h->s_keep, (size_t)n + 1));
+  APSS_TRY(ensure(h, h->s_cnt, (size_t)n + 1));
+  APSS_TRY(ensure(h, h->s_rowdst, (size_t)n + 1));
+  APSS_TRY(ensure(h, h->s_nnzdst, (size_t)n + 1));
+  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
+  hipLaunchKernelGGL(k_rm_rows, dim3((unsigned)std::min<int64_t>(ceil_div(n, kRmThreads), 4096)), dim3(kRmThreads), 0, h->stream,
+                     (const uint8_t *)h->dead.p, (const int64_t *)h->rowptr.p, n, h->s_keep.p, h->s_cnt.p);
+  HIPCHK(h, hipGetLastError());
+  APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, n));
+  APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, n));
+  int64_t live_rows = 0, live_nnz = 0;
+  HIPCHK(h, hipMemcpyAsync(&live_rows, h->s_rowdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&live_nnz, h->s_nnzdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (live_rows != n - marked || live_nnz < 0 || live_nnz > h->nnz) return fail(h, APSS_E_STATE, "apss_compact: the marks and their count disagree");
+  APSS_TRY(ensure(h, h->in_rowptr, (size_t)live_rows + 1));
+  APSS_TRY(ensure(h, h->in_ext, (size_t)std::max<int64_t>(live_rows, 1)));
+  APSS_TRY(ensure(h, h->in_idx, (size_t)std::max<int64_t>(live_nnz, 1)));
+  APSS_TRY(ensure(h, h->in_val, (size_t)std::max<int64_t>(live_nnz, 1)));
+  RmGatherArgs g{};
+  g.dead = h->dead.p;
+  g.rowptr = h->rowptr.p;
+  g.ext = h->ext.p;
+  g.idx = h->idx.p;
+  g.val = h->val.p;
+  g.rows = n;
+  g.row_dst = h->s_rowdst.p;
+  g.nnz_dst = h->s_nnzdst.p;
+  g.o_rowptr = h->in_rowptr.p;
+  g.o_ext = h->in_ext.p;
+  g.o_idx = h->in_idx.p;
+  g.o_val = h->in_val.p;
+  hipLaunchKernelGGL(k_rm_gather, dim3((unsigned)ceil_div(n * kRmWave, kRmThreads)), dim3(kRmThreads), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  APSS_TRY(clear_impl(h));
+  int64_t first = 0;
+  h->stored_rows = true;
+  const int32_t rc = insert_dev_impl(h, live_rows, live_nnz, h->in_rowptr.p, h->in_idx.p, h->in_val.p, h->in_ext.p, &first);
+  h->stored_rows = false;
+  APSS_TRY(rc);
+  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  h->ri.compact_ms = ms;
+  h->ri.compacted_rows = marked;
+  ++h->ri.compactions;
+  return APSS_OK;
+}
+
+// apss_set_auto_compact: at the start of an insert-type call, BEFORE its batch is staged (the compaction gathers into the staging)
+int32_t auto_compact(apss_handle *h) {
+  if (!(h->auto_compact > 0.0) || h->rm_marked <= 0 || !((double)h->rm_marked > h->auto_compact * (double)h->n_rows)) return APSS_OK;
+  return compact_impl(h);
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -3420,6 +3643,9 @@ void apss_destroy(apss_handle *h) {
   topk_release(h->topk);
   release(h->win_df); release(h->win_b); h->win.release();
   release(h->row_pairs);
+  release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
+  if (h->rm_ev0) (void)hipEventDestroy(h->rm_ev0);
+  if (h->rm_ev1) (void)hipEventDestroy(h->rm_ev1);
   if (h->pin) (void)hipHostFree(h->pin);
   release(h->wl_dev);
   if (h->wl_pin) (void)hipHostFree(h->wl_pin);
@@ -3445,6 +3671,7 @@ int32_t apss_insert(apss_handle *h, int64_t n, const int64_t *rowptr, const int3
                     const int64_t *ext_ids) {
   APSS_TRY(enter(h));
   APSS_TRY(validate_host_csr(h, n, rowptr, indices, values, ext_ids));
+  APSS_TRY(auto_compact(h));
   if (n == 0) return APSS_OK;
   APSS_TRY(upload(h, n, rowptr, indices, values, ext_ids));
   int64_t first = 0;
@@ -3463,6 +3690,7 @@ int32_t apss_insert_and_query(apss_handle *h, int64_t n, const int64_t *rowptr, 
                               const double *values, const int64_t *ext_ids, int64_t *n_results) {
   APSS_TRY(enter(h));
   APSS_TRY(validate_host_csr(h, n, rowptr, indices, values, ext_ids));
+  APSS_TRY(auto_compact(h));  // (before the batch is staged; the _dev entry below then finds nothing over the fraction)
   APSS_TRY(upload(h, n, rowptr, indices, values, ext_ids));
   return apss_insert_and_query_dev(h, n, n ? rowptr[n] : 0, h->up_rowptr, h->up_idx, h->in_val.p, h->up_ext, n_results);
 }
@@ -3557,6 +3785,7 @@ int32_t apss_insert_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d
   if (n < 0 || nnz < 0) return fail(h, APSS_E_INVALID, "negative size");
   if (n > 0 && (!d_rowptr || !d_ext_ids || (nnz > 0 && (!d_indices || !d_values))))
     return fail(h, APSS_E_INVALID, "null device pointer");
+  APSS_TRY(auto_compact(h));
   int64_t first = 0;
   return insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first);
 }
@@ -3567,6 +3796,7 @@ int32_t apss_insert_stored_dev(apss_handle *h, int64_t n, int64_t nnz, const int
   if (n < 0 || nnz < 0) return fail(h, APSS_E_INVALID, "negative size");
   if (n > 0 && (!d_rowptr || !d_ext_ids || (nnz > 0 && (!d_indices || !d_values))))
     return fail(h, APSS_E_INVALID, "null device pointer");
+  APSS_TRY(auto_compact(h));
   int64_t first = 0;
   h->stored_rows = true;
   const int32_t rc = insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first);
@@ -3602,6 +3832,7 @@ int32_t apss_insert_and_query_dev(apss_handle *h, int64_t n, int64_t nnz, const 
   if (n < 0 || nnz < 0) return fail(h, APSS_E_INVALID, "negative size");
   if (n > 0 && (!d_rowptr || !d_ext_ids || (nnz > 0 && (!d_indices || !d_values))))
     return fail(h, APSS_E_INVALID, "null device pointer");
+  APSS_TRY(auto_compact(h));
   int64_t first = 0;
   APSS_TRY(insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first));
   const int64_t nq = h->n_rows - first;
@@ -3612,37 +3843,7 @@ int32_t apss_insert_and_query_dev(apss_handle *h, int64_t n, int64_t nnz, const 
 
 int32_t apss_clear(apss_handle *h) {
   APSS_TRY(enter(h));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->n_rows = 0;
-  h->idx_rows = 0;
-  h->nnz = 0;
-  h->n_tiles = 0;
-  for (apss_handle::IndexSet *s : {&h->ex, &h->cx}) { s->n_tiles = 0; s->post_used = 0; s->h_base.clear(); s->built_rows = 0; }
-  h->ex_built_rows = 0;
-  h->n_res = -1;
-  h->res_q_ext = nullptr;
-  h->last_q_rowptr = nullptr;
-  h->last_q_idx = nullptr;
-  h->last_q_val = nullptr;
-  h->last_nq = 0;
-  h->nonneg = true;
-  h->q_nonneg = true;
-  h->no_acc8 = h->dbgcfg.no_acc8;
-  h->merge_off = false;
-  h->downgrades = 0;
-  h->store_max_nnz = 0;
-  h->store_max_norm2 = 0.f;
-  h->store_nonempty = 0;
-  if (!h->head_fixed) {  // (terms set through apss_set_head_terms are configuration: they outlive the data)
-    h->head_k = 0;
-    h->head_terms.clear();
-  }
-  h->head_eval_rows = 0;
-  h->head_blocked = false;
-  h->head_nonempty = 0;
-  h->cut_lo = h->cut_hi = 0;
-  h->df_rows = -1;
-  return APSS_OK;
+  return clear_impl(h);
 }
 
 int32_t apss_set_head_terms(apss_handle *h, int32_t n_terms, const int32_t *terms, int32_t part, int32_t n_parts) {
@@ -3744,6 +3945,60 @@ int32_t apss_topk_tile_cut_get(apss_handle *h, apss_topk_tile_cut_info *out) {
   const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_topk_tile_cut_info));
   h->tci.struct_size = n;
   std::memcpy(out, &h->tci, (size_t)n);
+  return APSS_OK;
+}
+
+int32_t apss_remove(apss_handle *h, int64_t n, const int64_t *ext_ids, int64_t *n_rows_removed) {
+  APSS_TRY(enter(h));
+  if (n_rows_removed) *n_rows_removed = 0;
+  if (h->sharded) return refuse_shard_removal(h, "apss_remove");
+  if (n < 0 || (n > 0 && !ext_ids)) return fail(h, APSS_E_INVALID, "apss_remove: n >= 0 ids");
+  if (n == 0 || h->n_rows == 0) return APSS_OK;
+  APSS_TRY(ensure(h, h->rm_ids, (size_t)n));
+  HIPCHK(h, hipMemcpyAsync(h->rm_ids.p, ext_ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  int64_t newly = 0;
+  APSS_TRY(remove_impl(h, n, h->rm_ids.p, &newly));  // (synchronises: the caller's array may be reused on return)
+  if (n_rows_removed) *n_rows_removed = newly;
+  return APSS_OK;
+}
+
+int32_t apss_remove_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int64_t *n_rows_removed) {
+  APSS_TRY(enter(h));
+  if (n_rows_removed) *n_rows_removed = 0;
+  if (h->sharded) return refuse_shard_removal(h, "apss_remove_dev");
+  if (n < 0 || (n > 0 && !d_ext_ids)) return fail(h, APSS_E_INVALID, "apss_remove_dev: n >= 0 ids");
+  int64_t newly = 0;
+  APSS_TRY(remove_impl(h, n, d_ext_ids, &newly));
+  if (n_rows_removed) *n_rows_removed = newly;
+  return APSS_OK;
+}
+
+int32_t apss_compact(apss_handle *h) {
+  APSS_TRY(enter(h));
+  if (h->sharded) return refuse_shard_removal(h, "apss_compact");
+  return compact_impl(h);
+}
+
+int32_t apss_set_auto_compact(apss_handle *h, double fraction) {
+  if (!h) return APSS_E_INVALID;
+  if (h->sharded) return refuse_shard_removal(h, "apss_set_auto_compact");
+  if (!(fraction >= 0.0 && fraction < 1.0)) return fail(h, APSS_E_INVALID, "apss_set_auto_compact: the fraction must be in [0, 1) (0: off)");
+  h->auto_compact = fraction;
+  return APSS_OK;
+}
+
+int32_t apss_removal_get(apss_handle *h, apss_removal_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  if (h->sharded) return refuse_shard_removal(h, "apss_removal_get");
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_removal_info.struct_size must be set to sizeof(apss_removal_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_removal_info));
+  h->ri.struct_size = n;
+  h->ri.rows_removed = h->rm_marked;
+  h->ri.rows_live = h->n_rows - h->rm_marked;
+  h->ri.auto_compact = h->auto_compact;
+  std::memcpy(out, &h->ri, (size_t)n);
   return APSS_OK;
 }
 

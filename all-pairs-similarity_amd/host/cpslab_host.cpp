@@ -256,6 +256,49 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
     h_ = nullptr;
     throw std::runtime_error(msg);
   }
+  if (conf.autoCompact != 0.0 && apss_set_auto_compact(h_, conf.autoCompact) != APSS_OK) {
+    const std::string msg = std::string("apss_set_auto_compact: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
+}
+
+int64_t GpuIndexingWorker::remove(const std::vector<std::string> &ids) {
+  if (g_) {
+    last_error_ = "remove: a term-sharded worker has no removal (cpslab.allpair.gpu.devices with one entry)";
+    return -1;
+  }
+  std::vector<int64_t> ext;
+  for (const std::string &s : ids) {
+    const auto it = id_of_.find(s);
+    if (it != id_of_.end()) ext.push_back(it->second);
+  }
+  int64_t removed = 0;
+  if (apss_remove(h_, (int64_t)ext.size(), ext.data(), &removed) != APSS_OK) {
+    last_error_ = std::string("apss_remove: ") + apss_last_error(h_);
+    return -1;
+  }
+  return removed;
+}
+
+bool GpuIndexingWorker::compact() {
+  if (g_) {
+    last_error_ = "compact: a term-sharded worker has no removal (cpslab.allpair.gpu.devices with one entry)";
+    return false;
+  }
+  if (apss_compact(h_) != APSS_OK) {
+    last_error_ = std::string("apss_compact: ") + apss_last_error(h_);
+    return false;
+  }
+  return true;
+}
+
+int64_t GpuIndexingWorker::liveVectors() const {
+  if (g_) return storedVectors();
+  apss_removal_info ri{};
+  ri.struct_size = (int32_t)sizeof(ri);
+  return apss_removal_get(h_, &ri) == APSS_OK ? ri.rows_live : storedVectors();
 }
 
 GpuIndexingWorker::~GpuIndexingWorker() {

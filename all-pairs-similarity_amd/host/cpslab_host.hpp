@@ -105,6 +105,10 @@ struct Config {
   // probe kernel cuts every (query row, tile) round to the pairs that can be among a query's topK before it writes them
   // (apss_set_top_k_tile_cut): the same answer, a shorter list for the cut.  Groups do not take it
   bool topKTileCut = false;
+  // cpslab.allpair.gpu.autoCompact: 0 (default) = off; f in (0, 1) = vectors withdrawn with GpuIndexingWorker::remove keep their
+  // slots until more than the fraction f of the stored vectors is removed; the next IndexData then compacts the store first
+  // (apss_set_auto_compact).  Groups have no removal
+  double autoCompact = 0.0;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.
@@ -121,6 +125,13 @@ class GpuIndexingWorker {
   void receive(const Test &t);       // :145-147 (echo)
   void receiveTimeout();             // ReceiveTimeout -> stopUpdateIndex = true, :143-144
   int64_t storedVectors() const;
+  // Withdraw vectors by their String ids (the reference cannot: its index only grows until expDuration stops it,
+  // IndexingWorkerActor.scala:33-39).  Later replies hold no pair with them; a vector sent again under a removed id is live.
+  // Returns the vectors newly removed (unknown ids are ignored); -1 and lastError() on a term-sharded worker
+  int64_t remove(const std::vector<std::string> &ids);
+  // rebuild store and index from the live vectors on the device (apss_compact); false and lastError() when refused
+  bool compact();
+  int64_t liveVectors() const;  // storedVectors() minus the removed ones
   const std::string &lastError() const { return last_error_; }
 
  private:

@@ -72,6 +72,17 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, topK)
     else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), topKTileCut, headTerms, topKWindowPairs, topK)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
+  // cpslab.allpair.gpu.autoCompact = f (default 0: off; one GPU only): vectors withdrawn with NativeApss.remove keep their slots
+  // until more than the fraction f of the stored vectors is removed; the next IndexData then compacts the store first
+  // (apss_set_auto_compact).  The reference has no removal: it stops indexing after expDuration instead (below)
+  private val autoCompact =
+    if (conf.hasPath("cpslab.allpair.gpu.autoCompact")) conf.getDouble("cpslab.allpair.gpu.autoCompact") else 0.0
+  if (!grouped && autoCompact != 0.0)
+    require(NativeApss.setAutoCompact(handle, autoCompact) == 0, NativeApss.lastError(handle))
+  /** withdraw vectors by their String ids (unknown ids are ignored); returns the vectors newly removed */
+  def removeVectors(names: Iterable[String]): Long =
+    if (grouped) throw new UnsupportedOperationException("removal needs one GPU (cpslab.allpair.gpu.devices with one entry)")
+    else NativeApss.remove(handle, names.flatMap(idOf.get).toArray)
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =
     if (grouped) NativeApss.groupSubmit(handle, mode, rowptr, indices, values, ids)
     else NativeApss.submit(handle, mode, rowptr, indices, values, ids)

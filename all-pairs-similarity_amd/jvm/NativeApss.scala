@@ -23,6 +23,17 @@ object NativeApss {
   @native def submit(h: Long, mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double],
                      ids: Array[Long]): Long
   @native def fetch(h: Long, count: Long, outQ: Array[Long], outC: Array[Long], outScore: Array[Float]): Int
+  // ---- removal of stored vectors (include/apss.h, apss_remove / apss_compact / apss_set_auto_compact; one handle only, a group
+  // has none).  They travel through `submit` (modes 3, 4, 5 of apss_jni.c): no further native entry point.
+  /** forget every stored vector whose id is in `ids`: later replies hold no pair with them.  Returns the rows newly marked or a
+    * negative status; ids that are unknown, removed already or repeated count for nothing */
+  def remove(h: Long, ids: Array[Long]): Long =
+    submit(h, 3, new Array[Long](ids.length + 1), new Array[Int](0), new Array[Double](0), ids)
+  /** rebuild store and index from the live vectors, on the device; the last results are gone.  0 or a negative status */
+  def compact(h: Long): Int = submit(h, 4, Array(0L), new Array[Int](0), new Array[Double](0), new Array[Long](0)).toInt
+  /** cpslab.allpair.gpu.autoCompact: compact before an insert once more than `fraction` (in [0, 1); 0 = off) of the stored
+    * vectors is removed.  0 or a negative status */
+  def setAutoCompact(h: Long, fraction: Double): Int = submit(h, 5, Array(0L, 1L), Array(0), Array(fraction), Array(0L)).toInt
   /** name the dense-head block's terms instead of the library's policy (include/apss.h, apss_set_head_terms; a handle made by
     * `create` holds the whole term space: part = 0, nParts = 1); empty handle only.  Returns 0 or a negative status.
     * (Term-sharded deployments do not call this: a group -- createGroup -- gives its members their shares itself.) */

@@ -125,6 +125,11 @@ static int32_t handle_submit(void *t, int mode, int64_t n, const int64_t *rp, co
                              int64_t *n_res) {
   if (mode == 0) return apss_insert((apss_handle *)t, n, rp, ix, vl, id);
   if (mode == 1) return apss_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
+  /* removal rides on submit (NativeApss.remove / compact / setAutoCompact): mode 3 = apss_remove of the n ids (the CSR is n
+   * empty rows), the rows newly marked come back as the count; 4 = apss_compact; 5 = apss_set_auto_compact of values(0) */
+  if (mode == 3) return apss_remove((apss_handle *)t, n, id, n_res);
+  if (mode == 4) return apss_compact((apss_handle *)t);
+  if (mode == 5) return apss_set_auto_compact((apss_handle *)t, n == 1 && rp[1] == 1 ? vl[0] : -1.0);
   return apss_insert_and_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
 }
 

@@ -349,6 +349,63 @@ typedef struct apss_topk_tile_cut_info {
 int32_t apss_set_top_k_tile_cut(apss_handle *h, int32_t on);
 int32_t apss_topk_tile_cut_get(apss_handle *h, apss_topk_tile_cut_info *out);
 
+/* ---- removal of stored vectors: mark, drop from the results, compact the store ----
+ * The reference's store only grows; it stops indexing after cpslab.allpair.benchmark.expDuration instead
+ * (IndexingWorkerActor.scala:33-39, 143-144).  Plain handles only.
+ *
+ * apss_remove[_dev](n, ext_ids) MARKS every stored row whose external id is in the list (two rows may carry one id: both are
+ * marked; self-exclusion is by external id too).  Ids that are not stored, ids whose rows are marked already and ids repeated in
+ * the list are ignored; *n_rows_removed (may be NULL) = the rows newly marked.  The mark belongs to the SLOT, not to the id: a
+ * vector inserted later under a removed id is live.  The results of the last call are left alone (as apss_set_top_k leaves
+ * them).  One pass over the store's external ids per call (k_rm_mark), whatever n is.  _dev: d_ext_ids int64[n] on the handle's
+ * device, read on the handle's stream; the call synchronises that stream.
+ *
+ * From then on every query-type call answers as if the marked rows were not stored: no pair with a marked candidate is reported,
+ * and when the query batch IS stored rows (apss_self_join) no pair with a marked query row either -- on every path (two-pass
+ * join, APSS_FLAG_EXACT_ACCUM, APSS_FLAG_FORCE_SCAN, theta <= 0, rows waiting outside the tile index, the dense head, virtual rows,
+ * the mirrored half of a symmetric join): the call's final list is filtered once (k_rm_drop) BEFORE the top-k cut, so with k > 0 a
+ * row's k best are its k best LIVE pairs, and in a windowed call every window's list is filtered before that window's cut.
+ * n_results, apss_stats.result_pairs, apss_topk_info.pairs_over_theta / queries_cut / longest_segment speak of live pairs.
+ * apss_stats.candidate_pairs, posting_visits and the windows' b(q) keep counting marked rows until a compaction (the probe still
+ * visits them): they stay upper bounds.  apss_topk_window_info.pairs_window_max is taken before the filter (what the handle held).
+ * While any row is marked apss_set_top_k_tile_cut is declined (APSS_TILE_CUT_REMOVED): a round's k-th score could belong to a
+ * marked candidate, so the cut inside the probe is not safe; the final list stays right.
+ * With nothing marked a query-type call launches nothing new and reads nothing new.
+ *
+ * apss_compact: the store becomes the live rows in their stored order and the index is rebuilt -- exactly what apss_clear
+ * followed by apss_insert_stored_dev of the live rows gives (no normalisation, prune or admission is applied again; settings
+ * survive as they do across apss_clear), without the rows leaving the device.  Slots shift: the results of the last call are gone
+ * afterwards (APSS_E_STATE, as after an insert), and so are the views of apss_get_store_dev / apss_ext_ids_dev.  With nothing
+ * marked it is a no-op that keeps the last results.  While it runs apss_stats.hbm_bytes may grow by one copy of the live store
+ * (the gathered rows wait in the handle's input staging, which is kept like every reservation).
+ *
+ * apss_set_auto_compact(f): f = 0 (the default) = off; f in (0, 1): at the start of every insert-type call (apss_insert,
+ * apss_insert_and_query, their _dev forms, apss_insert_stored_dev) the handle compacts first if rows_removed > f * rows.  The
+ * setting survives apss_clear.  APSS_E_INVALID: f outside [0, 1) or not a number.
+ *
+ * apss_clear drops the marks.  apss_size and apss_stats.rows keep reporting physical rows, marked ones included.
+ * APSS_E_INVALID: NULL handle, n < 0, NULL ids with n > 0.  APSS_E_UNSUPPORTED ("term shard"): any of the five on a term shard --
+ * it holds slices of rows and a compaction needs whole ones.  apss_group has no removal. */
+#define APSS_TILE_CUT_REMOVED 4 /* apss_topk_tile_cut_info.declined: rows are marked removed (apss_remove) */
+typedef struct apss_removal_info {
+  int32_t struct_size;        /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t compactions;        /* since create */
+  int64_t rows_removed;       /* stored rows currently marked (0 after a compaction or apss_clear) */
+  int64_t rows_live;          /* apss_size rows - rows_removed */
+  int64_t removed_total;      /* rows ever marked, since create */
+  int64_t pairs_dropped;      /* pairs the last query-type call dropped because an end was removed */
+  int64_t compacted_rows;     /* rows the last compaction discarded */
+  double auto_compact;        /* the setting */
+  double mark_ms, drop_ms, compact_ms; /* device time, HIP events: last apss_remove*, last call's drop, last compaction */
+  int32_t drop_launches;      /* k_rm_drop launches of the last query-type call (0 when nothing is marked) */
+  int32_t reserved0;
+} apss_removal_info;          /* 88 bytes */
+int32_t apss_remove(apss_handle *h, int64_t n, const int64_t *ext_ids, int64_t *n_rows_removed);
+int32_t apss_remove_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int64_t *n_rows_removed);
+int32_t apss_compact(apss_handle *h);
+int32_t apss_set_auto_compact(apss_handle *h, double fraction);
+int32_t apss_removal_get(apss_handle *h, apss_removal_info *out);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
