@@ -116,6 +116,7 @@ struct DebugCfg {
   bool no_persist = false;     // no_persist     k_probe_even launches one workgroup per (tile, chunk) cell, never resident workgroups over a work list
   int persist_wgs = 0;         // persist_wgs=N  ... the persistent launch has N workgroups (default: as many as the chip holds at a time)
   int persist_fine = 0;        // persist_fine=R ... and the last items of its list are R rounds long (a power of two; default kPersistFine)
+  int rm_grid = 0;             // rm_grid=N      at most N workgroups for k_rm_mark, k_rm_drop and k_rm_rows (tests of their grid-stride loops; default 4096 / 16384 / 4096)
 };
 
 DebugCfg parse_debug_env() {
@@ -175,6 +176,7 @@ DebugCfg parse_debug_env() {
     else if (key == "no_persist") d.no_persist = val != 0;
     else if (key == "persist_wgs") d.persist_wgs = val;
     else if (key == "persist_fine") d.persist_fine = val;
+    else if (key == "rm_grid") d.rm_grid = val;
     else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
@@ -3059,6 +3061,10 @@ int32_t rm_extend(apss_handle *h) {
   return APSS_OK;
 }
 
+// the most workgroups of k_rm_mark / k_rm_drop / k_rm_rows (they loop over the rest); APSS_DEBUG=rm_grid=N: N, a test hook that
+// makes a small store take their loops' later trips
+int64_t rm_grid_cap(const apss_handle *h, int64_t cap) { return h->dbgcfg.rm_grid > 0 ? h->dbgcfg.rm_grid : cap; }
+
 int32_t rm_events(apss_handle *h) {
   if (!h->rm_ev0) HIPCHK(h, hipEventCreate(&h->rm_ev0));
   if (!h->rm_ev1) HIPCHK(h, hipEventCreate(&h->rm_ev1));
@@ -3085,7 +3091,7 @@ int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
   a.kept = h->rm_ctr.p;
   HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
   const int64_t blocks = ceil_div(h->n_res, (int64_t)kRmThreads * kRmItems);
-  hipLaunchKernelGGL(k_rm_drop, dim3((unsigned)std::min<int64_t>(blocks, 16384)), dim3(kRmThreads), 0, h->stream, a);
+  hipLaunchKernelGGL(k_rm_drop, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 16384))), dim3(kRmThreads), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
   unsigned long long kept_stack = 0;
@@ -3446,7 +3452,7 @@ int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *ne
   HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
   // (two rows per thread; the workgroups loop: one global add each)
   const int64_t blocks = ceil_div(ceil_div(h->n_rows, 2), kRmThreads);
-  hipLaunchKernelGGL(k_rm_mark, dim3((unsigned)std::min<int64_t>(blocks, 4096)), dim3(kRmThreads), 0, h->stream, (const int64_t *)h->ext.p, h->n_rows,
+  hipLaunchKernelGGL(k_rm_mark, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 4096))), dim3(kRmThreads), 0, h->stream, (const int64_t *)h->ext.p, h->n_rows,
                      (const int64_t *)h->rm_sorted.p, n, h->dead.p, h->rm_ctr.p);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
@@ -3474,7 +3480,7 @@ int32_t compact_impl(apss_handle *h) {
   APSS_TRY(ensure(h, h->s_rowdst, (size_t)n + 1));
   APSS_TRY(ensure(h, h->s_nnzdst, (size_t)n + 1));
   HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
-  hipLaunchKernelGGL(k_rm_rows, dim3((unsigned)std::min<int64_t>(ceil_div(n, kRmThreads), 4096)), dim3(kRmThreads), 0, h->stream,
+  hipLaunchKernelGGL(k_rm_rows, dim3((unsigned)std::min<int64_t>(ceil_div(n, kRmThreads), rm_grid_cap(h, 4096))), dim3(kRmThreads), 0, h->stream,
                      (const uint8_t *)h->dead.p, (const int64_t *)h->rowptr.p, n, h->s_keep.p, h->s_cnt.p);
   HIPCHK(h, hipGetLastError());
   APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, n));
