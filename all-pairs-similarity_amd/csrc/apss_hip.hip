@@ -72,13 +72,15 @@ struct PairList {
 // Test and experiment hooks: ONE environment word, APSS_DEBUG, read once when a handle is created -- a comma-separated
 // list of the tokens below.  Nothing else in the library reads the environment.
 struct DebugCfg {
-  bool build_lds = false;      // build_lds      index build with LDS cursors even for a handful of tiles
-  bool build_atomic = false;   // build_atomic   index build with global atomics even for small dims
-  bool build_stream = false;   // build_stream   LDS index build with the whole-tile streaming kernels (never the run-reading ones)
-  bool build_runs = false;     // build_runs     LDS index build with the run-reading kernels whatever the number of ranges and the mean run
-  int run_range = 0;           // run_range=N    terms per range of the run-reading build (<= 16384; default kRunRange)
-  int run_lanes = 0;           // run_lanes=L    its lanes per row (4 | 8 | 16 | 32; default: from the mean run length)
-  int run_sub = -1;            // run_sub=W      run-reading build: scatter in two passes through sub-ranges of W terms (a power of two >= 64; 0: one pass)
+  BuildHooks build;            // what the build plan reads (apss_build_plan.hpp):
+                               // build_lds      index build with LDS cursors even for a handful of tiles
+                               // build_atomic   index build with global atomics even for small dims
+                               // build_stream   LDS index build with the whole-tile streaming kernels (never the run-reading ones)
+                               // build_runs     LDS index build with the run-reading kernels whatever the number of ranges and the mean run
+                               // run_range=N    terms per range of the run-reading build (<= 16384; default kRunRange)
+                               // run_lanes=L    its lanes per row (4 | 8 | 16 | 32; default: from the mean run length)
+                               // run_sub=W      run-reading build: scatter in two passes through sub-ranges of W terms (a power of two >= 64; 0: one pass)
+                               // no_bucket      large dims build with global atomics (never the bucketed LDS build)
   bool build_trace = false;    // build_trace    one line on stderr per index build: which kernels it took
   bool chunk8 = false;         // chunk8         filter kernel with 8-posting chunks (4-step window)
   bool shard_exact = false;    // shard_exact    term-range shards run the single-pass exact kernel
@@ -98,14 +100,11 @@ struct DebugCfg {
   bool even_wide = false;      // even_wide      k_probe_even also with one staging lane per term and windows of up to 7 steps (experiment)
   bool no_even = false;        // no_even        the filter stages every round on all waves (k_probe_coarse), never on F of them (k_probe_even)
   int seg_align = 0;           // seg_align=N    postings per aligned unit of the coarse index (16 | 32)
-  bool bank_order = false;     // bank_order     experiment: bank-aware posting order inside short segments (k_seg_bank_order)
   int fold_w = 0;              // fold_w=N       columns of the dense head's folded block (128 | 256)
   bool no_sym = false;         // no_sym         as APSS_FLAG_NO_SYMMETRY
   int mix = 0;                 // mix=E          ONE head block of 256 columns: E terms with a column each, the others folded into 256 - E
   bool no_chain = false;       // no_chain       small batches take the exact pass with its own host round trips (as large ones do)
   bool no_append = false;      // no_append      a batch that lands in a partly filled tile rebuilds the whole tile (never appends to it)
-  bool no_bucket = false;      // no_bucket      large dims build with global atomics (never the bucketed LDS build)
-  int bucket_range = 0;        // bucket_range=N terms per range of the bucketed LDS build (a power of two <= 16384; default 2048)
   int res_cap = 0;             // res_cap=N      initial capacity of the candidate list (tests of the overflow -> regrow -> re-run path)
   bool head_bf16 = false;      // head_bf16      the dense-head block keeps bf16 rows (v_mfma_f32_32x32x16_bf16), never the INT8 rendering
   int merge = -1;              // merge=L        a term shard's thin rounds: at most 2^L query rows share a round (0: never; default 1: two rows)
@@ -132,13 +131,13 @@ DebugCfg parse_debug_env() {
     const size_t eq = tok.find('=');
     const std::string key = tok.substr(0, eq);
     const int val = eq == std::string::npos ? 1 : atoi(tok.c_str() + eq + 1);
-    if (key == "build_lds") d.build_lds = val != 0;
-    else if (key == "build_atomic") d.build_atomic = val != 0;
-    else if (key == "build_stream") d.build_stream = val != 0;
-    else if (key == "build_runs") d.build_runs = val != 0;
-    else if (key == "run_range") d.run_range = val;
-    else if (key == "run_lanes") d.run_lanes = val;
-    else if (key == "run_sub") d.run_sub = val;
+    if (key == "build_lds") d.build.build_lds = val != 0;
+    else if (key == "build_atomic") d.build.build_atomic = val != 0;
+    else if (key == "build_stream") d.build.build_stream = val != 0;
+    else if (key == "build_runs") d.build.build_runs = val != 0;
+    else if (key == "run_range") d.build.run_range = val;
+    else if (key == "run_lanes") d.build.run_lanes = val;
+    else if (key == "run_sub") d.build.run_sub = val;
     else if (key == "build_trace") d.build_trace = val != 0;
     else if (key == "chunk8") d.chunk8 = val != 0;
     else if (key == "shard_exact") d.shard_exact = val != 0;
@@ -158,7 +157,6 @@ DebugCfg parse_debug_env() {
     else if (key == "pad_lds") d.pad_lds = (int)val;
     else if (key == "flat_group") d.flat_group = (int)val;
     else if (key == "seg_align") d.seg_align = val;
-    else if (key == "bank_order") d.bank_order = val != 0;
     else if (key == "fold_w") d.fold_w = val;
     else if (key == "mix") d.mix = val;
     else if (key == "no_sym") d.no_sym = val != 0;
@@ -166,8 +164,7 @@ DebugCfg parse_debug_env() {
     else if (key == "no_append") d.no_append = val != 0;
     else if (key == "head_bf16") d.head_bf16 = val != 0;
     else if (key == "res_cap") d.res_cap = val;
-    else if (key == "no_bucket") d.no_bucket = val != 0;
-    else if (key == "bucket_range") d.bucket_range = val;
+    else if (key == "no_bucket") d.build.no_bucket = val != 0;
     else if (key == "merge") d.merge = (int)val;
     else if (key == "merge_u") d.merge_u = (int)val;
     else if (key == "no_merge_prune") d.no_merge_prune = val != 0;
@@ -741,11 +738,32 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   return APSS_OK;
 }
 
-void fill_build_args(apss_handle *h, apss_handle::IndexSet &ix, BuildArgs &b, bool scaled) {
+// ---- index build for rows [row0, idx_rows): rebuild every tile of `ix` that contains one of them (build_tiles, below) ----
+// One build's state: what it covers and its plan (apss_build_plan.hpp), then what each stage settles for the ones behind it.
+struct Build {
+  apss_handle::IndexSet &ix;
+  DevBuf<float> &tmin;         // shard rule (`scaled`: the probe scales its threshold per query and tile): min positive sub-norm per tile
+  bool scaled;
+  BuildPlan plan;              // (an Append sets the kind alone: its stages read nothing else of the plan)
+  int64_t tile0, n_tiles, r0;  // tiles [tile0, n_tiles), from the rows [r0, b.row1)  (Append: the one tile, from the batch's first row)
+  bool cuts_on_hand;           // Runs: the cuts k_ingest_plain left while it stored the rows are in this build's form and cover its rows
+  BuildArgs b;
+  BucketArgs bk;
+  double appended_ms;          // time of the append that went before this build
+  dim3 row_grid(int lanes) const { return dim3((unsigned)ceil_div((b.row1 - r0) * lanes, 256)); }  // `lanes` lanes per row, workgroups of 256
+  dim3 tile_grid(int64_t per_tile) const { return dim3((unsigned)((n_tiles - tile0) * per_tile)); }  // `per_tile` workgroups per tile
+};
+
+// the kernels' view of the build of tiles [bd.tile0, bd.n_tiles) from the rows [row0, row1)
+void fill_build_args(apss_handle *h, Build &bd, int64_t row0, int64_t row1) {
+  apss_handle::IndexSet &ix = bd.ix;
+  BuildArgs &b = bd.b = BuildArgs{};
   // (a handle with a dense-head block builds from its tail view: the block's entries are not in the inverted index)
   b.rowptr = h->head_k ? h->tv.rowptr.p : h->rowptr.p;
   b.idx = h->head_k ? h->tv.idx.p : h->idx.p;
   b.val = h->head_k ? h->tv.val.p : h->val.p;
+  b.row0 = bd.r0 = row0;
+  b.row1 = row1;
   b.cb = (int32_t)ix.cb;
   b.dim = h->cfg.dim;
   b.tile_seg = ix.seg.p;
@@ -753,7 +771,7 @@ void fill_build_args(apss_handle *h, apss_handle::IndexSet &ix, BuildArgs &b, bo
   b.coarse = ix.coarse ? 1 : 0;
   b.seg_align = ix.align;
   b.erow = h->head_k ? h->tv.erow.p : h->erow.p;
-  b.row_scale = scaled && ix.coarse ? h->sub.p : nullptr;  // shard rule: postings normalised by |x_g| / |x| (k_probe_coarse)
+  b.row_scale = bd.scaled && ix.coarse ? h->sub.p : nullptr;  // shard rule: postings normalised by |x_g| / |x| (k_probe_coarse)
   b.coarse_shift = ix.coarse && ix.cb <= 32768 ? 1 : 0;  // must agree with k_probe_coarse's SLOT2 (the 512-thread kernels)
   b.coarse_wide = ix.coarse && ix.cb > 65536 ? 1 : 0;     // ... and with its WIDE (131072-row tiles)
   b.tile_post_base = ix.base.p;
@@ -763,162 +781,11 @@ void fill_build_args(apss_handle *h, apss_handle::IndexSet &ix, BuildArgs &b, bo
   b.term_hi = h->cfg.term_hi;
 }
 
-// segment lengths -> segment starts for tiles [tile0, tile0 + n): k_tile_scan_part + k_tile_scan_place
-int32_t launch_tile_scan(apss_handle *h, apss_handle::IndexSet &ix, int64_t tile0, int64_t n, uint32_t keep_len, unsigned long long *chunk_w,
-                         uint32_t count_long) {
-  const int32_t n_blk = (int32_t)ceil_div(h->cfg.dim, kScanBlock);
-  APSS_TRY(ensure(h, ix.scan_part, (size_t)(n * n_blk)));
-  const dim3 grid((unsigned)(n * n_blk));
-  hipLaunchKernelGGL(k_tile_scan_part, grid, dim3(1024), 0, h->stream, (const uint2 *)ix.seg.p, (int64_t)h->cfg.dim, h->cfg.dim, tile0, n_blk,
-                     (uint32_t)ix.align, ix.scan_part.p, ix.maxlen.p, chunk_w, count_long);
-  hipLaunchKernelGGL(k_tile_scan_place, grid, dim3(1024), 0, h->stream, ix.seg.p, (int64_t)h->cfg.dim, h->cfg.dim, tile0, n_blk, (uint32_t)ix.align,
-                     keep_len, (const uint32_t *)ix.scan_part.p, ix.total.p);
-  HIPCHK(h, hipGetLastError());
-  return APSS_OK;
-}
-
-// ---- APPEND rows [row0, row1) to tile `tile` of `ix`, which holds rows [tile * cb, row0) (k_tile_shift, apss_kernels.hpp) ----
-int32_t append_tile(apss_handle *h, apss_handle::IndexSet &ix, int64_t tile, int64_t row0, int64_t row1) {
-  const int64_t stride = (int64_t)h->cfg.dim;
-  const bool scaled = h->sharded || h->head_k > 0;
-  const size_t elt = ix.coarse ? sizeof(uint32_t) : sizeof(Posting);
-  const int64_t base = ix.h_base[(size_t)tile], old_total = ix.h_base[(size_t)tile + 1] - base;
-  uint2 *sg = ix.seg.p + tile * stride;
-  APSS_TRY(ensure(h, h->app_seg, (size_t)stride));
-  APSS_TRY(ensure(h, h->app_post, (size_t)std::max<int64_t>(old_total, 1) * elt));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->app_seg.p, sg, (size_t)stride * sizeof(uint2), hipMemcpyDeviceToDevice, h->stream));
-  if (old_total > 0)
-    HIPCHK(h, hipMemcpyAsync(h->app_post.p, ix.coarse ? (const void *)(ix.post_c.p + base) : (const void *)(ix.post.p + base),
-                             (size_t)old_total * elt, hipMemcpyDeviceToDevice, h->stream));
-  BuildArgs b{};
-  fill_build_args(h, ix, b, scaled);
-  b.row0 = row0;
-  b.row1 = row1;
-  const int threads = 256;
-  const int64_t blocks = ceil_div((row1 - row0) * kWave, threads);
-  hipLaunchKernelGGL(k_tile_hist, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);  // lengths: old + new
-  APSS_TRY(launch_tile_scan(h, ix, tile, 1, 0u, nullptr, 0u));
-  HIPCHK(h, hipGetLastError());
-  int64_t new_total = 0;
-  uint32_t seg_stats[2] = {0, 0};
-  HIPCHK(h, hipMemcpyAsync(&new_total, ix.total.p + tile, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(seg_stats, ix.maxlen.p, sizeof(seg_stats), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  ix.max_seg = seg_stats[0];
-  ix.h_base[(size_t)tile + 1] = base + new_total;
-  ix.post_used = base + new_total;
-  if (ix.coarse) APSS_TRY(ensure(h, ix.post_c, (size_t)ix.post_used + 64, (size_t)base));
-  else APSS_TRY(ensure(h, ix.post, (size_t)ix.post_used + 64, (size_t)base));
-  if (ix.coarse)  // the probe reads a zero word as "no posting": clear the tile's region (padding between segments)
-    HIPCHK(h, hipMemsetAsync(ix.post_c.p + base, 0, (size_t)(new_total + 64) * sizeof(uint32_t), h->stream));
-  HIPCHK(h, hipMemcpyAsync(ix.base.p + tile + 1, ix.h_base.data() + tile + 1, sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  ShiftArgs sa{};
-  sa.seg_old = h->app_seg.p;
-  sa.seg_new = sg;
-  sa.old_c = ix.coarse ? reinterpret_cast<const uint32_t *>(h->app_post.p) : nullptr;
-  sa.old_x = ix.coarse ? nullptr : reinterpret_cast<const Posting *>(h->app_post.p);
-  sa.new_c = ix.coarse ? ix.post_c.p + base : nullptr;
-  sa.new_x = ix.coarse ? nullptr : ix.post.p + base;
-  sa.dim = h->cfg.dim;
-  hipLaunchKernelGGL(k_tile_shift, dim3((unsigned)ceil_div(stride * kGroup, 256)), dim3(256), 0, h->stream, sa);
-  fill_build_args(h, ix, b, scaled);  // (the posting array may have moved)
-  b.row0 = row0;
-  b.row1 = row1;
-  hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);
-  if (scaled) {
-    DevBuf<float> &tmin = ix.coarse ? h->tile_min_c : h->tile_min;
-    hipLaunchKernelGGL(k_tile_min_sub, dim3(1), dim3(1024), 0, h->stream, (const float *)h->sub.p, h->idx_rows, (int32_t)ix.cb, tmin.p, tile);
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipEventSynchronize(h->ev1));  // (the host vector the tile base was copied from lives on; the event gives the build its time)
-  float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  ix.build_ms = ms;
-  return APSS_OK;
-}
-
-// run-reading LDS build: the mean row length (entries the handle keeps of a row) below which the streaming kernels are kept --
-// the cut table and the second pass are paid per row and per (tile, sub-range), the re-reads they remove per entry.  Measured on
-// term shards of C3 (profiles/build_runs.md): T = 2 (50 entries per row) build 3.42 -> 2.67 ms, T = 4 (25) 2.09 -> 1.94,
-// T = 8 (12.5) 1.36 -> 1.78.  And the launch of k_tile_runs with L lanes per row.
-constexpr double kRunMinMeanRow = 20.0;
-constexpr int kRunSub = 256;  // terms per sub-range of the two-pass scatter
-template <int SCATTER>
-void launch_tile_runs(int lanes, dim3 grid, size_t lds, hipStream_t stream, const BuildArgs &b, int64_t tile0, int32_t n_ranges) {
-  if (lanes == 4) hipLaunchKernelGGL((k_tile_runs<SCATTER, 4>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
-  else if (lanes == 8) hipLaunchKernelGGL((k_tile_runs<SCATTER, 8>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
-  else if (lanes == 16) hipLaunchKernelGGL((k_tile_runs<SCATTER, 16>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
-  else hipLaunchKernelGGL((k_tile_runs<SCATTER, 32>), grid, dim3(1024), lds, stream, b, tile0, n_ranges);
-}
-
-// Which kernels the build of tiles [tile0, n_tiles) of `cb` rows takes, and in which form: decided from the shape of what is built
-// -- `rows` rows of `build_nnz` entries, the longest of `max_nnz`.  build_tiles decides with it; ingest_plain asks it beforehand
-// whether the rows it stores will be read by runs (ingest_wants_cuts), so that the two cannot drift apart.
-struct BuildForm {
-  int32_t n_ranges, bucket_rt, run_rt;
-  bool bucket_build, lds_build, run_build;
-  double mean_run;
-};
-BuildForm build_form(const apss_handle *h, int64_t cb, int64_t tile0, int64_t n_tiles, int64_t rows, int64_t build_nnz, int64_t max_nnz) {
-  // small dims: counters and cursors of a (tile, term range) live in one workgroup's LDS (no global atomics)
-  int32_t n_ranges = (int32_t)ceil_div(h->cfg.dim, kBuildRange);
-  // (one workgroup per (tile, range): with fewer than ~48 of them -- a small batch, a rebuilt tail tile, a 1/8 candidate
-  // range -- the row-parallel global-atomic kernels are faster; APSS_BUILD_LDS / APSS_BUILD_ATOMIC force either)
-  // large dims (more than kBuildMaxRanges ranges: vectorDim = 2^20): a build from the first tile partitions the entries by
-  // term range first (k_bucket_pass), so that the LDS build's workgroups read their bucket instead of the whole tile
-  // (terms per range of a bucketed build, measured on C5's shape, build ms per step: 1024: 28.3, 2048: 23.9, 4096: 20.4, 8192: 15.6,
-  // 16384: 17.4 -- against 37.5 with the global-atomic kernels; narrow ranges multiply the workgroups' fixed work)
-  int32_t bucket_rt = h->dbgcfg.bucket_range > 0 ? h->dbgcfg.bucket_range : 8192;
-  while (ceil_div(h->cfg.dim, bucket_rt) > kBucketMaxRanges && bucket_rt < kBuildRange) bucket_rt *= 2;
-  const bool bucket_build = n_ranges > kBuildMaxRanges && ceil_div(h->cfg.dim, bucket_rt) <= kBucketMaxRanges && !h->dbgcfg.build_atomic &&
-                            !h->dbgcfg.no_bucket && tile0 == 0 && n_tiles * n_ranges >= 48 && build_nnz > 0 && build_nnz <= (1LL << 32) &&
-                            n_tiles * (int64_t)kBucketSlices < (1LL << 31);
-  if (bucket_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, bucket_rt);
-  const bool lds_build = bucket_build || (n_ranges <= kBuildMaxRanges && !h->dbgcfg.build_atomic &&
-                                          ((n_tiles - tile0) * n_ranges >= 48 || h->dbgcfg.build_lds));
-  // Run-reading LDS build (k_row_cuts + k_tile_runs): wherever the streaming LDS build would re-read the tile's entries -- two
-  // term ranges or more -- and the rows are long enough to be worth a cut table (kRunMinMeanRow).  With one range
-  // the streaming kernels read every entry exactly once, coalesced: nothing to save.  32-bit cut points: (longest row) x (rows
-  // per tile) < 2^31.
-  const double mean_row = rows > 0 ? (double)build_nnz / (double)rows : 0.0;
-  int32_t run_rt = h->dbgcfg.run_range > 0 ? std::min(h->dbgcfg.run_range, kBuildRange) : kRunRange;
-  const int64_t t_lo = h->cfg.term_lo, t_hi = h->cfg.term_hi;
-  const int64_t run_active = std::max<int64_t>(1, ceil_div(t_hi, run_rt) - t_lo / run_rt);  // ranges that hold terms of this handle
-  const double mean_run = mean_row / (double)run_active;
-  const bool run_build = lds_build && !bucket_build && !h->dbgcfg.build_stream && std::max<int64_t>(max_nnz, 1) * cb < (1LL << 31) &&
-                         ceil_div(h->cfg.dim, run_rt) <= 64 &&
-                         (h->dbgcfg.build_runs || (n_ranges >= 2 && mean_row >= kRunMinMeanRow));
-  if (run_build) n_ranges = (int32_t)ceil_div(h->cfg.dim, run_rt);
-  return BuildForm{n_ranges, bucket_rt, run_rt, bucket_build, lds_build, run_build, mean_run};
-}
-
-// ---- index build for rows [row0, n_rows): rebuild every tile of `ix` that contains one of them ----
-int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
-  const int64_t cb = ix.cb;
-  int64_t tile0 = row0 / cb;
-  const int64_t n_tiles = ceil_div(h->idx_rows, cb);
-  const int64_t stride = (int64_t)h->cfg.dim;
-  double appended_ms = 0.0;
-  if (row0 % cb != 0 && ix.built_rows == row0 && ix.n_tiles == tile0 + 1 && (int64_t)ix.h_base.size() == tile0 + 2 &&
-      !h->dbgcfg.no_append && !h->dbgcfg.bank_order) {
-    // the batch lands in the last, partly filled tile of an up-to-date rendering: append to it, build the tiles beyond as ever
-    DevBuf<float> &tmin_a = ix.coarse ? h->tile_min_c : h->tile_min;
-    if (h->sharded || h->head_k > 0) APSS_TRY(ensure(h, tmin_a, (size_t)n_tiles, (size_t)tile0 + 1));
-    APSS_TRY(ensure(h, ix.total, (size_t)n_tiles, (size_t)tile0 + 1));
-    APSS_TRY(append_tile(h, ix, tile0, row0, std::min<int64_t>(h->idx_rows, (tile0 + 1) * cb)));
-    appended_ms = ix.build_ms;
-    ++tile0;
-    row0 = tile0 * cb;
-    if (h->idx_rows <= row0) {
-      ix.built_rows = h->idx_rows;
-      return APSS_OK;
-    }
-  }
-  ix.n_tiles = n_tiles;
-  ix.built_rows = h->idx_rows;
-  if (n_tiles == tile0) return APSS_OK;
+// The plan, the reservations and the clears of maxlen / chunkw of a build of whole tiles; the build's clock starts at its end.
+int32_t begin_build(apss_handle *h, Build &bd) {
+  apss_handle::IndexSet &ix = bd.ix;
+  BuildArgs &b = bd.b;
+  const int64_t cb = ix.cb, stride = (int64_t)h->cfg.dim, tile0 = bd.tile0, n_tiles = bd.n_tiles, r0 = tile0 * cb;
   APSS_TRY(ensure(h, ix.seg, (size_t)(n_tiles * stride), (size_t)(tile0 * stride)));
   APSS_TRY(ensure(h, ix.base, (size_t)n_tiles + 1, (size_t)tile0 + 1));
   APSS_TRY(ensure(h, ix.total, (size_t)n_tiles, 0));
@@ -928,199 +795,221 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
     HIPCHK(h, hipMemsetAsync(ix.maxlen.p, 0, 2 * sizeof(uint32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(ix.chunkw.p, 0, sizeof(unsigned long long), h->stream));
   }
-  DevBuf<float> &tmin = ix.coarse ? h->tile_min_c : h->tile_min;
-  const bool scaled = h->sharded || h->head_k > 0;  // the probe scales its threshold per query and tile (shard rule)
-  if (scaled) APSS_TRY(ensure(h, tmin, (size_t)n_tiles, (size_t)tile0));
-  if (ix.h_base.empty()) ix.h_base.push_back(0);
-  ix.h_base.resize((size_t)tile0 + 1);  // bases of the tiles that stay
-  const int64_t r0 = tile0 * cb;
+  if (bd.scaled) APSS_TRY(ensure(h, bd.tmin, (size_t)n_tiles, (size_t)tile0));
   const int64_t build_nnz = h->head_k ? h->tv.nnz : h->nnz;  // entries of the rows [0, idx_rows) the index is built from
-  const BuildForm form = build_form(h, cb, tile0, n_tiles, h->idx_rows, build_nnz, h->store_max_nnz);
-  const int32_t n_ranges = form.n_ranges, bucket_rt = form.bucket_rt, run_rt = form.run_rt;
-  const bool bucket_build = form.bucket_build, lds_build = form.lds_build, run_build = form.run_build;
-  const double mean_run = form.mean_run;
-  if (!lds_build)
+  const BuildShape shape{h->cfg.dim, h->cfg.term_lo, h->cfg.term_hi, cb, ix.coarse, tile0, n_tiles, h->idx_rows, build_nnz, h->store_max_nnz};
+  const BuildPlan &p = bd.plan = build_plan(shape, h->dbgcfg.build);
+  const bool runs = p.kind == BuildKind::Runs;
+  if (p.kind == BuildKind::Atomic)  // (the LDS kernels write every length of their range)
     HIPCHK(h, hipMemsetAsync(ix.seg.p + tile0 * stride, 0, (size_t)((n_tiles - tile0) * stride) * sizeof(uint2), h->stream));
-  BuildArgs b{};
-  fill_build_args(h, ix, b, scaled);
-  b.row0 = r0;
-  b.row1 = h->idx_rows;
-  // ... and its scatter in two passes (BuildArgs::sub_shift) when the scratch copy of the entries is affordable
-  int32_t run_sub = h->dbgcfg.run_sub >= 0 ? h->dbgcfg.run_sub : kRunSub;
-  if (run_sub < 64 || run_sub > kPlaceMaxTerms || (run_sub & (run_sub - 1)) || run_rt % run_sub || !ix.coarse || build_nnz > (int64_t)6e8 || build_nnz <= 0)
-    run_sub = 0;
-  const int32_t n_sub = run_sub ? (int32_t)ceil_div(h->cfg.dim, run_sub) : 0;
-  const int64_t n_bk = (n_tiles - tile0) * n_sub;
-  // lanes per row, a power of two in 4 .. 32 (measured at C3, mean run 14.3: profiles/build_runs.md): about the mean run where the
-  // scatter's 4-B stores go straight to memory (one pass: 16), half of it where they are 8-B stores into a handful of streams
-  // (two passes: 8) -- there more rows in flight per workgroup pay more than lanes that never wait for a second chunk
-  const double run_want = run_sub ? mean_run * 0.5 : mean_run;
-  int run_lanes = h->dbgcfg.run_lanes;
-  if (run_lanes != 4 && run_lanes != 8 && run_lanes != 16 && run_lanes != 32)
-    run_lanes = run_want <= 4.0 ? 4 : (run_want <= 8.0 ? 8 : (run_want <= 16.0 ? 16 : 32));
-  if (h->dbgcfg.build_trace)
-    fprintf(stderr, "[apss] build %s tiles [%lld, %lld): %s, %d ranges of %d terms, %d lanes per row (mean run %.2f)\n", ix.coarse ? "coarse" : "exact",
-            (long long)tile0, (long long)n_tiles, bucket_build ? "bucketed" : (run_build ? "runs" : (lds_build ? "stream" : "atomic")), (int)n_ranges,
-            run_build ? run_rt : (bucket_build ? bucket_rt : kBuildRange), run_build ? run_lanes : 0, mean_run);
-  if (h->dbgcfg.build_trace && run_build) fprintf(stderr, "[apss]   scatter through sub-ranges of %d terms\n", (int)run_sub);
-  // the cuts k_ingest_plain left while it stored the rows, when they are in this build's form and cover its rows
-  const bool cuts_on_hand = run_build && !h->head_k && h->cut_cb == (int32_t)cb && h->cut_rt == run_rt && h->cut_ranges == n_ranges &&
-                            h->cut_lo <= r0 && h->cut_hi >= h->idx_rows && h->cut_hi > h->cut_lo;
-  if (h->dbgcfg.diag && run_build)
+  fill_build_args(h, bd, r0, h->idx_rows);
+  if (h->dbgcfg.build_trace) fputs(build_trace_text(shape, p).c_str(), stderr);
+  bd.cuts_on_hand = runs && !h->head_k && h->cut_cb == (int32_t)cb && h->cut_rt == p.range_terms && h->cut_ranges == p.n_ranges &&
+                    h->cut_lo <= r0 && h->cut_hi >= h->idx_rows && h->cut_hi > h->cut_lo;
+  if (h->dbgcfg.diag && runs)
     fprintf(stderr, "[apss diag] build %s rows [%lld, %lld): cuts %s\n", ix.coarse ? "coarse" : "exact", (long long)r0, (long long)h->idx_rows,
-            cuts_on_hand ? "reused" : "computed");
-  if (run_build) {
-    if (!cuts_on_hand) APSS_TRY(ensure(h, h->run_cut, (size_t)((h->idx_rows - r0) * (n_ranges + 1))));
-    b.range_terms = run_rt;
-    b.run_cut = cuts_on_hand ? h->ing_cut.p + r0 * (n_ranges + 1) : h->run_cut.p;
-    if (run_sub) {
-      APSS_TRY(ensure(h, h->bk_cnt, (size_t)n_bk + 2));
-      APSS_TRY(ensure(h, h->bk_base, (size_t)n_bk + 2));
-      APSS_TRY(ensure(h, h->run_ent, (size_t)build_nnz));
-      int sh = 0;
-      while ((1 << sh) < run_sub) ++sh;
-      b.sub_shift = sh;
-      b.n_sub = n_sub;
-      b.sub_cnt = h->bk_cnt.p;
-      b.sub_base = h->bk_base.p;
-      b.o_ent = h->run_ent.p;
-    }
+            bd.cuts_on_hand ? "reused" : "computed");
+  if (runs) {
+    if (!bd.cuts_on_hand) APSS_TRY(ensure(h, h->run_cut, (size_t)((h->idx_rows - r0) * (p.n_ranges + 1))));
+    b.range_terms = p.range_terms;
+    b.run_cut = bd.cuts_on_hand ? h->ing_cut.p + r0 * (p.n_ranges + 1) : h->run_cut.p;
   }
-  const int threads = 256;
-  const int64_t blocks = ceil_div((h->idx_rows - r0) * kWave, threads);
+  if (runs && p.run_sub) {  // its scatter in two passes: the entries partitioned by (tile, sub-range)
+    APSS_TRY(ensure(h, h->bk_cnt, (size_t)((n_tiles - tile0) * p.n_sub) + 2));
+    APSS_TRY(ensure(h, h->bk_base, (size_t)((n_tiles - tile0) * p.n_sub) + 2));
+    APSS_TRY(ensure(h, h->run_ent, (size_t)build_nnz));
+    while ((1 << b.sub_shift) < p.run_sub) ++b.sub_shift;
+    b.n_sub = p.n_sub;
+    b.sub_cnt = h->bk_cnt.p;
+    b.sub_base = h->bk_base.p;
+    b.o_ent = h->run_ent.p;
+  }
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  // bucketed build: tiles in GROUPS whose entries fit a bounded scratch (12 B per entry: a one-shot join of 2e9 entries would
-  // otherwise spend 1.2 s allocating 24 GB to save 0.5 s of atomics).  A single group (C5's shape at N = 2M: 4.8 GB) is bucketed
-  // once for both passes; several groups are bucketed again for the scatter pass (twice 43 ms at N = 10M, against 573 ms).
-  int64_t group_tiles = n_tiles;
-  BucketArgs bk{};
-  if (bucket_build) {
-    const int64_t per_tile = std::max<int64_t>(1, build_nnz / n_tiles);
-    group_tiles = std::max<int64_t>(1, std::min<int64_t>(n_tiles, (int64_t)6e8 / per_tile));
-    // entries of the largest group (row extents are on the device: one small read)
-    std::vector<int64_t> grp_e;
-    {
-      std::vector<int64_t> at;
-      for (int64_t g0 = 0; g0 < n_tiles; g0 += group_tiles) at.push_back(std::min<int64_t>(h->idx_rows, g0 * cb));
-      at.push_back(h->idx_rows);
-      grp_e.resize(at.size());
-      for (size_t i = 0; i < at.size(); ++i)
-        HIPCHK(h, hipMemcpyAsync(&grp_e[i], b.rowptr + at[i], sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (p.kind != BuildKind::Bucketed) return APSS_OK;
+  // Bucketed: the scratch of the largest tile group (row extents are on the device: one small read), k_bucket_pass's arguments, the LDS kernels' view
+  const int64_t nb = p.group_tiles * p.n_ranges;
+  std::vector<int64_t> grp_e((size_t)ceil_div(n_tiles, p.group_tiles) + 1);  // entries before each group, and before the end
+  for (size_t i = 0; i < grp_e.size(); ++i)
+    HIPCHK(h, hipMemcpyAsync(&grp_e[i], b.rowptr + std::min<int64_t>(h->idx_rows, (int64_t)i * p.group_tiles * cb), sizeof(int64_t),
+                             hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int64_t max_e = 1;
+  for (size_t i = 0; i + 1 < grp_e.size(); ++i) max_e = std::max(max_e, grp_e[i + 1] - grp_e[i]);
+  APSS_TRY(ensure(h, h->bk_cnt, (size_t)(2 * nb + 2)));
+  APSS_TRY(ensure(h, h->bk_base, (size_t)nb + 2));
+  APSS_TRY(ensure(h, h->bk_idx, (size_t)max_e));
+  APSS_TRY(ensure(h, h->bk_erow, (size_t)max_e));
+  APSS_TRY(ensure(h, h->bk_val, (size_t)max_e));
+  // (rowptr, idx, val, erow, row1, cb, n_ranges, range_terms, tile0, bucket_cnt, bucket_base, bucket_cur, o_idx, o_erow, o_val)
+  bd.bk = BucketArgs{b.rowptr, b.idx, b.val, b.erow, h->idx_rows, (int32_t)cb, p.n_ranges, p.range_terms, 0, h->bk_cnt.p, h->bk_base.p,
+                     h->bk_cnt.p + nb + 1, h->bk_idx.p, h->bk_erow.p, h->bk_val.p};
+  b.idx = h->bk_idx.p;
+  b.erow = h->bk_erow.p;
+  b.val = h->bk_val.p;
+  b.ent_base = h->bk_base.p;
+  b.range_terms = p.range_terms;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (the build's clock starts behind the reservations)
+  return APSS_OK;
+}
+
+template <int MODE>
+void launch_tile_runs(apss_handle *h, const Build &bd) {  // k_tile_runs with the plan's lanes per row
+  const int l = bd.plan.run_lanes;
+  const auto k = l == 4 ? k_tile_runs<MODE, 4> : (l == 8 ? k_tile_runs<MODE, 8> : (l == 16 ? k_tile_runs<MODE, 16> : k_tile_runs<MODE, 32>));
+  hipLaunchKernelGGL(k, bd.tile_grid(bd.plan.n_ranges), dim3(1024), (size_t)bd.plan.range_terms * sizeof(uint32_t), h->stream, bd.b, bd.tile0, bd.plan.n_ranges);
+}
+
+// One pass of a bucketed build, count or scatter, over its tile groups: partition a group's entries by term range into the scratch arrays
+// (k_bucket_pass: count, scan, scatter), then the pass's LDS kernel over the buckets.  A single group is bucketed once, by the count pass, for
+// both (its buckets are still there); several groups are bucketed again for the scatter pass (twice 43 ms at N = 10M, against 573 ms).
+int32_t for_bucket_groups(apss_handle *h, Build &bd, bool scatter) {
+  const BuildPlan &p = bd.plan;
+  for (int64_t g0 = 0; g0 < bd.n_tiles; g0 += p.group_tiles) {
+    const int64_t gt = std::min<int64_t>(p.group_tiles, bd.n_tiles - g0);
+    const dim3 bgrid((unsigned)(gt * kBucketSlices)), grid((unsigned)(gt * p.n_ranges));
+    if (!scatter || p.group_tiles < bd.n_tiles) {
+      HIPCHK(h, hipMemsetAsync(h->bk_cnt.p, 0, (size_t)(2 * (p.group_tiles * p.n_ranges) + 2) * sizeof(unsigned long long), h->stream));
+      bd.bk.tile0 = g0;
+      hipLaunchKernelGGL(k_bucket_pass<false>, bgrid, dim3(1024), 0, h->stream, bd.bk);
+      APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, gt * p.n_ranges));
+      hipLaunchKernelGGL(k_bucket_pass<true>, bgrid, dim3(1024), 0, h->stream, bd.bk);
+      HIPCHK(h, hipGetLastError());
     }
-    int64_t max_e = 1;
-    for (size_t i = 0; i + 1 < grp_e.size(); ++i) max_e = std::max(max_e, grp_e[i + 1] - grp_e[i]);
-    const int64_t nb = group_tiles * n_ranges;
-    APSS_TRY(ensure(h, h->bk_cnt, (size_t)(2 * nb + 2)));
-    APSS_TRY(ensure(h, h->bk_base, (size_t)nb + 2));
-    APSS_TRY(ensure(h, h->bk_idx, (size_t)max_e));
-    APSS_TRY(ensure(h, h->bk_erow, (size_t)max_e));
-    APSS_TRY(ensure(h, h->bk_val, (size_t)max_e));
-    bk.rowptr = b.rowptr;
-    bk.idx = b.idx;
-    bk.val = b.val;
-    bk.erow = b.erow;
-    bk.row1 = h->idx_rows;
-    bk.cb = (int32_t)cb;
-    bk.n_ranges = n_ranges;
-    bk.range_terms = bucket_rt;
-    bk.bucket_cnt = h->bk_cnt.p;
-    bk.bucket_cur = h->bk_cnt.p + nb + 1;
-    bk.bucket_base = h->bk_base.p;
-    bk.o_idx = h->bk_idx.p;
-    bk.o_erow = h->bk_erow.p;
-    bk.o_val = h->bk_val.p;
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (the build's clock starts behind the reservations)
+    hipLaunchKernelGGL(scatter ? k_tile_scatter_lds : k_tile_hist_lds, grid, dim3(1024), 0, h->stream, bd.b, g0, p.n_ranges);
   }
-  // partition the entries of tiles [g0, g0 + gt) by term range into the scratch arrays (k_bucket_pass: count, scan, scatter)
-  auto bucket_group = [&](int64_t g0, int64_t gt) -> int32_t {
-    const int64_t nbg = gt * n_ranges;
-    HIPCHK(h, hipMemsetAsync(h->bk_cnt.p, 0, (size_t)(2 * (group_tiles * n_ranges) + 2) * sizeof(unsigned long long), h->stream));
-    bk.tile0 = g0;
-    const dim3 bgrid((unsigned)(gt * kBucketSlices));
-    hipLaunchKernelGGL(k_bucket_pass<false>, bgrid, dim3(1024), 0, h->stream, bk);
-    APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, nbg));
-    hipLaunchKernelGGL(k_bucket_pass<true>, bgrid, dim3(1024), 0, h->stream, bk);
-    HIPCHK(h, hipGetLastError());
-    return APSS_OK;
-  };
-  if (bucket_build) {
-    b.idx = h->bk_idx.p;
-    b.erow = h->bk_erow.p;
-    b.val = h->bk_val.p;
-    b.ent_base = h->bk_base.p;
-    b.range_terms = bucket_rt;
-    for (int64_t g0 = 0; g0 < n_tiles; g0 += group_tiles) {
-      const int64_t gt = std::min<int64_t>(group_tiles, n_tiles - g0);
-      APSS_TRY(bucket_group(g0, gt));
-      hipLaunchKernelGGL(k_tile_hist_lds, dim3((unsigned)(gt * n_ranges)), dim3(1024), 0, h->stream, b, g0, n_ranges);
+  return APSS_OK;
+}
+
+// segment lengths into tile_seg[..].y  (Append: on top of the kept lengths -- build_tiles has saved the old segment table and postings)
+int32_t count_segments(apss_handle *h, Build &bd) {
+  switch (bd.plan.kind) {
+  case BuildKind::Append:
+  case BuildKind::Atomic: hipLaunchKernelGGL(k_tile_hist, bd.row_grid(kWave), dim3(256), 0, h->stream, bd.b); break;
+  case BuildKind::Stream: hipLaunchKernelGGL(k_tile_hist_lds, bd.tile_grid(bd.plan.n_ranges), dim3(1024), 0, h->stream, bd.b, bd.tile0, bd.plan.n_ranges); break;
+  case BuildKind::Bucketed: APSS_TRY(for_bucket_groups(h, bd, false)); break;
+  case BuildKind::Runs:
+    if (!bd.cuts_on_hand) hipLaunchKernelGGL(k_row_cuts, bd.row_grid(kGroup), dim3(256), 0, h->stream, bd.b, bd.plan.n_ranges, h->run_cut.p);
+    launch_tile_runs<kRunHist>(h, bd);
+    if (bd.plan.run_sub) {
+      APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, (bd.n_tiles - bd.tile0) * bd.plan.n_sub));
+      launch_tile_runs<kRunPartition>(h, bd);
     }
-    HIPCHK(h, hipGetLastError());
   }
-  const dim3 lds_grid((unsigned)((n_tiles - tile0) * n_ranges));
-  const size_t run_lds = (size_t)run_rt * sizeof(uint32_t);
-  if (bucket_build) {}  // (counted above, group by group)
-  else if (run_build) {
-    if (!cuts_on_hand)
-      hipLaunchKernelGGL(k_row_cuts, dim3((unsigned)ceil_div((h->idx_rows - r0) * kGroup, threads)), dim3(threads), 0, h->stream, b, n_ranges,
-                         h->run_cut.p);
-    launch_tile_runs<kRunHist>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
-    if (run_sub) {
-      APSS_TRY(scan_i64(h, reinterpret_cast<const int64_t *>(h->bk_cnt.p), h->bk_base.p, n_bk));
-      launch_tile_runs<kRunPartition>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
-    }
-  } else if (lds_build) hipLaunchKernelGGL(k_tile_hist_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
-  else hipLaunchKernelGGL(k_tile_hist, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);
-  APSS_TRY(launch_tile_scan(h, ix, tile0, n_tiles - tile0, lds_build ? 1u : 0u, tile0 == 0 ? ix.chunkw.p : nullptr, 1u));
+  return APSS_OK;  // (place_segments checks these launches with its own)
+}
+
+// lengths -> aligned segment starts and tile totals (the tile scan: k_tile_scan_part + k_tile_scan_place), the ONE read-back, tile bases by a
+// host prefix sum (a handful of values), the posting array.  An append keeps what describes the rendering as a whole: chunkw, long_segs,
+// round_chunks -- its scan keeps no lengths, weighs no chunks and counts no long segments.
+int32_t place_segments(apss_handle *h, Build &bd) {
+  apss_handle::IndexSet &ix = bd.ix;
+  const bool app = bd.plan.kind == BuildKind::Append, keep_len = !app && bd.plan.kind != BuildKind::Atomic;
+  const int64_t tile0 = bd.tile0, n = bd.n_tiles - tile0, dim = h->cfg.dim;
+  const int32_t n_blk = (int32_t)ceil_div(dim, kScanBlock);
+  APSS_TRY(ensure(h, ix.scan_part, (size_t)(n * n_blk)));
+  hipLaunchKernelGGL(k_tile_scan_part, bd.tile_grid(n_blk), dim3(1024), 0, h->stream, (const uint2 *)ix.seg.p, dim, h->cfg.dim, tile0, n_blk,
+                     (uint32_t)ix.align, ix.scan_part.p, ix.maxlen.p, tile0 == 0 && !app ? ix.chunkw.p : nullptr, app ? 0u : 1u);
+  hipLaunchKernelGGL(k_tile_scan_place, bd.tile_grid(n_blk), dim3(1024), 0, h->stream, ix.seg.p, dim, h->cfg.dim, tile0, n_blk,
+                     (uint32_t)ix.align, keep_len ? 1u : 0u, (const uint32_t *)ix.scan_part.p, ix.total.p);
   HIPCHK(h, hipGetLastError());
-  // padded posting counts -> tile bases (host prefix sum: a handful of values), then reserve the posting array
-  std::vector<int64_t> tot((size_t)(n_tiles - tile0));
-  HIPCHK(h, hipMemcpyAsync(tot.data(), ix.total.p + tile0, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  std::vector<int64_t> tot((size_t)n);
   uint32_t seg_stats[2] = {0, 0};
   unsigned long long chunk_w = 0;
+  HIPCHK(h, hipMemcpyAsync(tot.data(), ix.total.p + tile0, tot.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(seg_stats, ix.maxlen.p, sizeof(seg_stats), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&chunk_w, ix.chunkw.p, sizeof(chunk_w), hipMemcpyDeviceToHost, h->stream));
+  if (!app) HIPCHK(h, hipMemcpyAsync(&chunk_w, ix.chunkw.p, sizeof(chunk_w), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   ix.max_seg = seg_stats[0];
-  ix.long_segs = seg_stats[1];
+  if (!app) ix.long_segs = seg_stats[1];
   // (measured on a build from the first tile; an appended batch keeps the figure of the build before it)
-  if (tile0 == 0 && h->idx_rows > 0) ix.round_chunks = (double)chunk_w / (double)h->idx_rows;
+  if (!app && tile0 == 0 && h->idx_rows > 0) ix.round_chunks = (double)chunk_w / (double)h->idx_rows;
+  ix.h_base.resize((size_t)tile0 + 1);  // bases of the tiles that stay (a first build: the 0 of tile 0)
   for (size_t i = 0; i < tot.size(); ++i) ix.h_base.push_back(ix.h_base.back() + tot[i]);
-  HIPCHK(h, hipMemcpyAsync(ix.base.p + tile0, ix.h_base.data() + tile0, (size_t)(n_tiles - tile0 + 1) * sizeof(int64_t),
-                           hipMemcpyHostToDevice, h->stream));
+  const int64_t base = ix.h_base[(size_t)tile0];
   ix.post_used = ix.h_base.back();
-  if (ix.coarse) APSS_TRY(ensure(h, ix.post_c, (size_t)ix.post_used + 64, (size_t)ix.h_base[(size_t)tile0]));
-  else APSS_TRY(ensure(h, ix.post, (size_t)ix.post_used + 64, (size_t)ix.h_base[(size_t)tile0]));
+  APSS_TRY(ix.coarse ? ensure(h, ix.post_c, (size_t)ix.post_used + 64, (size_t)base) : ensure(h, ix.post, (size_t)ix.post_used + 64, (size_t)base));
   if (ix.coarse)  // the probe reads a zero word as "no posting": clear the padding between segments
-    HIPCHK(h, hipMemsetAsync(ix.post_c.p + ix.h_base[(size_t)tile0], 0,
-                             (size_t)(ix.post_used - ix.h_base[(size_t)tile0] + 64) * sizeof(uint32_t), h->stream));
-  b.tile_post_base = ix.base.p;
-  b.post = ix.post.p;
-  b.post_c = ix.post_c.p;
-  if (bucket_build) {
-    for (int64_t g0 = 0; g0 < n_tiles; g0 += group_tiles) {
-      const int64_t gt = std::min<int64_t>(group_tiles, n_tiles - g0);
-      if (group_tiles < n_tiles) APSS_TRY(bucket_group(g0, gt));  // (a single group's buckets are still there)
-      hipLaunchKernelGGL(k_tile_scatter_lds, dim3((unsigned)(gt * n_ranges)), dim3(1024), 0, h->stream, b, g0, n_ranges);
-    }
-  } else if (run_build && run_sub) {
-    hipLaunchKernelGGL(k_tile_place_sub, dim3((unsigned)n_bk), dim3(kPlaceBlock), 0, h->stream, b, tile0);  // the partitioned entries, sub-range by sub-range
-  } else if (run_build) launch_tile_runs<kRunScatter>(run_lanes, lds_grid, run_lds, h->stream, b, tile0, n_ranges);
-  else if (lds_build) hipLaunchKernelGGL(k_tile_scatter_lds, lds_grid, dim3(1024), 0, h->stream, b, tile0, n_ranges);
-  else hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)blocks), dim3(threads), 0, h->stream, b);
-  if (ix.coarse && ix.cb <= 32768 && h->dbgcfg.bank_order)
-    hipLaunchKernelGGL(k_seg_bank_order, dim3((unsigned)ceil_div((n_tiles - tile0) * stride * kWave, 256)), dim3(256), 0, h->stream,
-                       (const uint2 *)ix.seg.p, stride, (const int64_t *)ix.base.p, ix.post_c.p, tile0, n_tiles, h->cfg.dim);
-  if (scaled)
-    hipLaunchKernelGGL(k_tile_min_sub, dim3((unsigned)(n_tiles - tile0)), dim3(1024), 0, h->stream,
-                       (const float *)h->sub.p, h->idx_rows, (int32_t)cb, tmin.p, tile0);
+    HIPCHK(h, hipMemsetAsync(ix.post_c.p + base, 0, (size_t)(ix.post_used - base + 64) * sizeof(uint32_t), h->stream));
+  const int64_t up0 = app ? tile0 + 1 : tile0;  // (the appended tile's own base stays)
+  HIPCHK(h, hipMemcpyAsync(ix.base.p + up0, ix.h_base.data() + up0, (size_t)(bd.n_tiles + 1 - up0) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  bd.b.tile_post_base = ix.base.p;  // (the posting array may have moved)
+  bd.b.post = ix.post.p;
+  bd.b.post_c = ix.post_c.p;
+  return APSS_OK;
+}
+
+// the postings into their segments; the cursor increments rebuild tile_seg[..].y
+int32_t scatter_postings(apss_handle *h, Build &bd) {
+  apss_handle::IndexSet &ix = bd.ix;
+  switch (bd.plan.kind) {
+  case BuildKind::Append: {  // the tile's old postings move to their segments' new starts (k_tile_shift), the new ones go behind them
+    const int64_t base = ix.h_base[(size_t)bd.tile0];
+    const char *old = h->app_post.p;
+    // (seg_old, seg_new, old_c, old_x, new_c, new_x, dim)
+    const ShiftArgs sa{h->app_seg.p, ix.seg.p + bd.tile0 * (int64_t)h->cfg.dim, ix.coarse ? (const uint32_t *)old : nullptr, ix.coarse ? nullptr : (const Posting *)old,
+                       ix.coarse ? ix.post_c.p + base : nullptr, ix.coarse ? nullptr : ix.post.p + base, h->cfg.dim};
+    hipLaunchKernelGGL(k_tile_shift, dim3((unsigned)ceil_div((int64_t)h->cfg.dim * kGroup, 256)), dim3(256), 0, h->stream, sa);
+  }
+    [[fallthrough]];
+  case BuildKind::Atomic: hipLaunchKernelGGL(k_tile_scatter, bd.row_grid(kWave), dim3(256), 0, h->stream, bd.b); break;
+  case BuildKind::Stream: hipLaunchKernelGGL(k_tile_scatter_lds, bd.tile_grid(bd.plan.n_ranges), dim3(1024), 0, h->stream, bd.b, bd.tile0, bd.plan.n_ranges); break;
+  case BuildKind::Bucketed: APSS_TRY(for_bucket_groups(h, bd, true)); break;
+  case BuildKind::Runs:  // (two passes: the partitioned entries, sub-range by sub-range)
+    if (bd.plan.run_sub) hipLaunchKernelGGL(k_tile_place_sub, bd.tile_grid(bd.plan.n_sub), dim3(kPlaceBlock), 0, h->stream, bd.b, bd.tile0);
+    else launch_tile_runs<kRunScatter>(h, bd);
+  }
+  return APSS_OK;
+}
+
+int32_t finish_build(apss_handle *h, Build &bd) {
+  if (bd.scaled)
+    hipLaunchKernelGGL(k_tile_min_sub, bd.tile_grid(1), dim3(1024), 0, h->stream, (const float *)h->sub.p, h->idx_rows, (int32_t)bd.ix.cb, bd.tmin.p, bd.tile0);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHK(h, hipEventSynchronize(h->ev1));
+  HIPCHK(h, hipEventSynchronize(h->ev1));  // (the host vector the tile bases were copied from lives on; the event gives the build its time)
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  ix.build_ms = ms + appended_ms;
+  bd.ix.build_ms = ms + bd.appended_ms;
   return APSS_OK;
+}
+
+int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
+  const int64_t cb = ix.cb, n_tiles = ceil_div(h->idx_rows, cb);
+  Build bd{ix, ix.coarse ? h->tile_min_c : h->tile_min, h->sharded || h->head_k > 0};
+  int64_t &tile0 = bd.tile0 = row0 / cb;
+  const auto stages = [&]() -> int32_t {
+    for (const auto stage : {count_segments, place_segments, scatter_postings, finish_build}) APSS_TRY(stage(h, bd));
+    return APSS_OK;
+  };
+  if (row0 % cb != 0 && ix.built_rows == row0 && ix.n_tiles == tile0 + 1 && (int64_t)ix.h_base.size() == tile0 + 2 && !h->dbgcfg.no_append) {
+    // the batch lands in the last, partly filled tile of an up-to-date rendering: the stages over that tile as an Append, the tiles beyond as ever
+    const int64_t base = ix.h_base[(size_t)tile0];
+    const size_t old_total = (size_t)(ix.h_base[(size_t)tile0 + 1] - base), elt = ix.coarse ? sizeof(uint32_t) : sizeof(Posting);
+    if (bd.scaled) APSS_TRY(ensure(h, bd.tmin, (size_t)n_tiles, (size_t)tile0 + 1));
+    APSS_TRY(ensure(h, ix.total, (size_t)n_tiles, (size_t)tile0 + 1));
+    APSS_TRY(ensure(h, h->app_seg, (size_t)h->cfg.dim));
+    APSS_TRY(ensure(h, h->app_post, std::max<size_t>(old_total, 1) * elt));
+    bd.plan.kind = BuildKind::Append;
+    bd.n_tiles = tile0 + 1;
+    fill_build_args(h, bd, row0, std::min<int64_t>(h->idx_rows, (tile0 + 1) * cb));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->app_seg.p, ix.seg.p + tile0 * (int64_t)h->cfg.dim, (size_t)h->cfg.dim * sizeof(uint2), hipMemcpyDeviceToDevice, h->stream));
+    if (old_total > 0)
+      HIPCHK(h, hipMemcpyAsync(h->app_post.p, ix.coarse ? (const void *)(ix.post_c.p + base) : (const void *)(ix.post.p + base), old_total * elt,
+                               hipMemcpyDeviceToDevice, h->stream));
+    APSS_TRY(stages());
+    bd.appended_ms = ix.build_ms;
+    row0 = ++tile0 * cb;
+    if (h->idx_rows <= row0) {
+      ix.built_rows = h->idx_rows;
+      return APSS_OK;
+    }
+  }
+  ix.n_tiles = bd.n_tiles = n_tiles;
+  ix.built_rows = h->idx_rows;
+  if (n_tiles == tile0) return APSS_OK;
+  APSS_TRY(begin_build(h, bd));
+  return stages();
 }
 
 // Which renderings of the index a handle keeps: the coarse one (two-pass speed path) is built at insert time when the
@@ -1170,7 +1059,7 @@ int32_t pick_cx_tile(const apss_handle *h, int64_t rows, int64_t nnz, int64_t ma
 
 // Will the index build that follows a plain store batch of n rows / nnz entries at row dst_row0 read runs (build_tiles), and in
 // which form?  Decided before the batch's own summaries are known, so it is a forecast: build_tiles compares the form of the
-// cuts on hand with the one it takes and computes its own when they differ.
+// cuts on hand with the one it takes and computes its own when they differ.  (*rt and *n_ranges: the run form, on a true return only.)
 bool ingest_wants_cuts(const apss_handle *h, int64_t dst_row0, int64_t n, int64_t nnz, int32_t *cb, int32_t *rt, int32_t *n_ranges) {
   if (h->head_k) return false;  // (the build reads the tail view, not the store)
   const int64_t rows = dst_row0 + n, entries = h->nnz + nnz;
@@ -1180,10 +1069,12 @@ bool ingest_wants_cuts(const apss_handle *h, int64_t dst_row0, int64_t n, int64_
     *cb = pick_cx_tile(h, rows, entries, h->store_max_nnz, h->store_max_norm2);
   if (*cb <= 0) return false;
   // build_tiles' own decision, for the tiles this batch is expected to (re)build and the store as it will be
-  const BuildForm form = build_form(h, *cb, std::min(h->idx_rows, dst_row0) / *cb, ceil_div(rows, *cb), rows, entries, h->store_max_nnz);
-  *rt = form.run_rt;
-  *n_ranges = form.n_ranges;
-  return form.run_build && form.n_ranges <= 2 * kGroup - 1;  // (k_ingest_plain: two cut counts per lane)
+  const BuildPlan plan = build_plan(BuildShape{h->cfg.dim, h->cfg.term_lo, h->cfg.term_hi, *cb, ix.coarse, std::min(h->idx_rows, dst_row0) / *cb,
+                                               ceil_div(rows, *cb), rows, entries, h->store_max_nnz},
+                                    h->dbgcfg.build);
+  *rt = plan.range_terms;
+  *n_ranges = plan.n_ranges;
+  return plan.kind == BuildKind::Runs && plan.n_ranges <= 2 * kGroup - 1;  // (k_ingest_plain: two cut counts per lane)
 }
 
 // ---- dense-head block (apss_head.hpp) ----

@@ -1,4 +1,4 @@
-"""GPU tests of the run-reading LDS index build (k_row_cuts + k_tile_runs, apss_kernels.hpp): a (tile, term range) workgroup
+"""GPU tests of the run-reading LDS index build (k_row_cuts + k_tile_runs, apss_build.hpp): a (tile, term range) workgroup
 reads the runs of its range out of the term-sorted rows instead of the whole tile.  Checked against the two builds it stands
 beside -- the whole-tile streaming LDS kernels (APSS_DEBUG=build_stream) and the global-atomic kernels (build_atomic) -- on the
 same input: same pair keys, same work counters; and against the CPU oracle.  `build_lds,build_runs` makes small inputs take
@@ -168,10 +168,13 @@ def test_run_build_from_a_tail_view(engine, oracle, monkeypatch, capfd):
 
 
 @pytest.mark.parametrize("hook", ["", ",no_append"])
-def test_second_batch_on_a_run_built_index(engine, oracle, monkeypatch, capfd, hook):
+@pytest.mark.parametrize("path", ["two_pass", "exact_wave"])
+def test_second_batch_on_a_run_built_index(engine, oracle, monkeypatch, capfd, hook, path):
     """two batches: the second lands in the partly filled last tile of a run-built index -- appended to (k_tile_shift), or with
     no_append rebuilt whole by the run-reading kernels from a tile that is not the first -- and fills tiles beyond it; every
-    batch's pairs are the oracle worker's"""
+    batch's pairs are the oracle worker's.  On the coarse rendering (two_pass) and on the exact one (exact_wave)."""
+    from apss import _lib
+    flags = {"two_pass": 0, "exact_wave": _lib.FLAG_EXACT_ACCUM}[path]
     dim, theta, tr = 100_000, 0.6, 256
     rp, idx, val = _corner_vectors(dim, seed=4242)
     n = len(rp) - 1
@@ -179,7 +182,7 @@ def test_second_batch_on_a_run_built_index(engine, oracle, monkeypatch, capfd, h
     w = oracle.Worker(dim, theta)
     capfd.readouterr()
     monkeypatch.setenv("APSS_DEBUG", RUNS + hook)
-    with engine.ApssIndex(dim, theta, tile_rows=tr) as ix:
+    with engine.ApssIndex(dim, theta, tile_rows=tr, flags=flags) as ix:
         for b0, b1 in ((0, m), (m, n)):
             sl = slice(rp[b0], rp[b1])
             args = (np.arange(b0, b1), rp[b0:b1 + 1] - rp[b0], idx[sl], val[sl])

@@ -221,7 +221,7 @@ def test_rejected_query_batch_ends_the_earlier_results(runs):
 
 def test_default_decision_takes_the_cuts_of_the_ingest(runs, inputs, oracle):
     """nothing forced: 24 coarse tiles of 128 rows, three ranges, 50 entries per row -- build_tiles takes the run form by its own rule
-    (build_form), the ingest foresaw it with the same rule and its cuts are reused"""
+    (build_plan), the ingest foresaw it with the same rule and its cuts are reused"""
     rp, idx, val = inputs["zipf"]
     f, u = runs["fused"]["default_runs"], runs["unfused"]["default_runs"]
     builds = [ln for ln in f["diag"] if ln.startswith("[apss] build ")]
