@@ -44,10 +44,38 @@
 // The two workgroup barriers of round v - 2 separate the strip writes from their readers; the ring of three keeps the
 // strip of round v readable during round v while round v + 2 is being staged.
 //
+// TWO PLANES, ONE BARRIER PER ROUND (TWO: k_probe_planes, the plain 512-thread handle over <= 32768-row tiles whose sums fit a
+// byte -- acc8_scale() in apss_hip.hip).  The second barrier of a round exists only because the clears write the plane the
+// next round adds into.  With two planes of 8-bit sums in the same 64 KB, round v adds into plane v mod 2, and round v - 1 is
+// cleared on the OTHER plane at the top of round v, directly ahead of round v's adds, from the posting registers that still
+// hold it (the wfa / wfb set that round v's loads for v + 1 have not yet overwritten): one barrier and one drain of the LDS
+// queue per round instead of two.  The barrier of round v separates adds(v) from clears(v), which run in round v + 1; the
+// barrier of round v + 1 separates clears(v) from adds(v + 2), the next adds on that plane.  A `rare` round's whole-plane clear
+// moves the same way and touches its own plane only.  Behind an item's last barrier comes the last round's clear, then the
+// barrier every item ends with: the next item of a persistent workgroup finds both planes zero (`first` clears both).
+// The kernel reads the index as k_probe_even<512, .., false, false, false> does (slot << 1 in a posting's low half), and a
+// handle goes back to that kernel without a rebuild (drop_planes).  The planes are INTERLEAVED BY BYTE: slot s of plane p is
+// byte 2 s + p, i.e. the two bytes of the 16-bit kernel's accumulator are the slot's two planes.  The add's word address is then
+// the 16-bit kernel's (pcw & 0xfffc: the same banks), its shift 16 (s % 2) + 8 p is (pcw << 3) + 8 p (one v_lshl_add_u32 in
+// place of the shift), and a clear is a byte store at (pcw & 0xffff) + p with p in the instruction's immediate offset: no
+// vector instruction more than the 16-bit kernel issues.  (First built with plane p in the bytes [32768 p, 32768 p + cb): the
+// word address (pcw >> 1) & 0x7ffc costs one instruction per posting more, and that took back all the barrier gave --
+// profiles/even_planes.md.)  The price is the `rare` round's whole-plane clear: the other plane's bytes of the same words are
+// live, so it is an atomic AND over the tile's words instead of 16-byte stores.
+// THE RING OF THREE under one barrier.  Between the barriers of rounds v - 1 and v every wave is in round v, and there the
+// adding waves read ring slot v + 1 (their next strip and its facts; they invalidate the window entries they read) and,
+// on `rare` paths, ring slot v (chunks past the window, long segments); the staging waves write ring slot v + 2 (strips,
+// longs, the facts' counters) and zero facts[v], which was last read in round v - 1 and is counted into again in round
+// v + 1 -- a barrier away on either side.  v, v + 1, v + 2 are distinct modulo 3, so no slot is read and written between the
+// same two barriers, and what is staged in round v is read from round v + 1 on.  One exception: the adding waves' FIRST strip
+// read (ring slot 0, in the prologue) already shares its interval with the staging waves' round v0, which zeroes facts[0] --
+// so the facts of an item's first round are counted in facts[3], a slot no later round uses (zeroed at the item's start).
+//
 // A round whose chunks exceed the strips (A x SLOTS) or whose long segments exceed LONGCAP is flagged at staging and
 // swept by the adding waves straight from the index (one term per wave at a time): slow, unbounded, never wrong.
 // Queries of more than 64 x NW / 4 terms are not served (they stay with k_probe_coarse; apss_hip.hip chooses).
 #pragma once
+#include <type_traits>
 #include "apss_kernels.hpp"
 
 namespace apss {
@@ -55,7 +83,7 @@ namespace apss {
 // the launch's arguments where the kernel finds them: the kernarg segment (scalar loads), see probe_even_body
 using ProbeArgsK = const __attribute__((address_space(4))) ProbeArgs;
 
-template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE>
+template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE, bool TWO = false>
 __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, const int v0, const int v1, const bool own_tile, const bool first) {
   // one ITEM of the launch: the rounds [v0, v1) against candidate tile `tile` (`first`: this workgroup's first item)
   // (Tried for C3's full rounds: workgroups of TEN waves -- the eight adding waves of the 512-thread kernel plus two staging
@@ -84,6 +112,9 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
   // an idle lane adds 1 to the low accumulator of its spare word, which the NW - 1 adding waves' lanes of that number share:
   // set to 1 every round, it stays non-zero inside its ABITS bits
   static_assert(1 + (NW - 1) * 2 * U < (1 << (ACC8 ? 8 : 16)), "the spare words' low accumulators must not wrap within a round");
+  // TWO PLANES (k_probe_planes, see the header): 8-bit sums over <= 32768-row tiles, read from the 16-bit rendering of the index
+  // (slot << 1 in the low half of a posting); the planes are interleaved by BYTE: slot s of plane p is byte 2 s + p of acc
+  static_assert(!TWO || (BLOCK == 512 && ACC8 && !MERGE && !SIGNED && !SHARD), "two planes: the plain 512-thread kernel, 8-bit sums");
   __shared__ __attribute__((aligned(16))) uint32_t acc[CBMAX / APW + kWave];  // (+ one spare word per lane: idle lanes add there)
   __shared__ __attribute__((aligned(16))) uint2 strips[3 * NS * SSZ + kWave];  // [3][NS][GPW][GS] {byte offset of the chunk's first posting, weight bits} (+ one spare entry per lane)
   __shared__ uint2 longs[3 * LONGCAP];
@@ -167,8 +198,11 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
 
   // (a later item of a persistent workgroup: the accumulators are zero behind the last round's second barrier; the strip
   // entries are made stale, the facts zero and the spare words 1 again)
-  if (first)
+  if (first) {
     for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + i) = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (TWO)  // (two bytes per slot: the second cb bytes)
+      for (int i = tid * 4; i < cb / APW; i += BLOCK * 4) *reinterpret_cast<uint4 *>(acc + cb / APW + i) = make_uint4(0u, 0u, 0u, 0u);
+  }
   if (tid < kWave) acc[CBMAX / APW + tid] = 1u;  // the spare words (LEAN: never zero in their low accumulator)
   if (LEAN) {  // no strip entry is valid before it is staged
     for (int i = tid; i < 3 * NS * SSZ; i += BLOCK) strips[i].x = kStale;
@@ -227,7 +261,8 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
   // it has none (a select on the address, not an exec mask).  Everything unusual -- a long segment, a term of more than
   // 2 G chunks, a round that does not fit -- takes one branch.
   uint2 *const spare_item = strips + 3 * NS * SSZ + ln;
-  auto flatten = [&](const Seg &g, const int ring) {
+  // (`fs`: the facts' slot of the round, its ring slot but for an item's first round with TWO: see ONE BARRIER PER ROUND)
+  auto flatten = [&](const Seg &g, const int ring, const int fs) {
     uint32_t len = g.len;
     my_visits += sub == 0u ? len : 0u;
     const bool is_long = len > (uint32_t)kLongLen;
@@ -238,7 +273,7 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
     const uint32_t mine = sub == 0u ? nch : 0u;  // a term counts once, in the first lane of its group
     const uint32_t incl = wave_incl_scan(mine);
     uint32_t base = 0;
-    if (ln == kWave - 1) base = atomicAdd(&facts_w[2 * ring], incl);
+    if (ln == kWave - 1) base = atomicAdd(&facts_w[2 * fs], incl);
     uint32_t j0 = (uint32_t)__builtin_amdgcn_readlane((int)base, kWave - 1) + incl - mine;
     if (LOGG == 2) j0 = (uint32_t)__builtin_amdgcn_update_dpp((int)j0, (int)j0, 0x00, 0xf, 0xf, false);       // quad_perm [0,0,0,0]
     else if (LOGG == 1) j0 = (uint32_t)__builtin_amdgcn_update_dpp((int)j0, (int)j0, 0xa0, 0xf, 0xf, false);  // quad_perm [0,0,2,2]
@@ -264,7 +299,7 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
     if (__any(is_long || unfit || nch > two)) {
       bool bad = unfit;
       if (is_long && sub == 0u) {
-        const uint32_t k = atomicAdd(&facts_w[2 * ring + 1], 2u) >> 1;
+        const uint32_t k = atomicAdd(&facts_w[2 * fs + 1], 2u) >> 1;
         if (k < (uint32_t)LONGCAP) {
           longs[ring * LONGCAP + k] = make_uint2(g.s, g.len);
           long_w[ring * LONGCAP + k] = g.w;
@@ -273,15 +308,15 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
         }
       }
       // the round is swept straight from the index; whatever was staged is ignored
-      if (bad) atomicOr(&facts_w[2 * ring + 1], 1u);
+      if (bad) atomicOr(&facts_w[2 * fs + 1], 1u);
       for (uint32_t k = two + sub; __any(k < nch); k += (uint32_t)G) put(k);
     }
   };
   // the next round of this wave, first half: the round's facts and this wave's strip (LDS reads, issued ahead of the
   // current round's adds so that one LDS round trip serves both)
   struct StripRead { uint2 fc; uint2 it[U]; };
-  auto strip_read = [&](StripRead &sr, const int ring, const int rank) {
-    sr.fc = facts[ring];
+  auto strip_read = [&](StripRead &sr, const int ring, const int rank, const int fs) {
+    sr.fc = facts[fs];
     const uint2 *const st = strips + (ring * NS + rank) * SSZ + (ln / LPC) * GS;
     if constexpr (GS % 2 == 0) {
 #pragma unroll
@@ -343,11 +378,19 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
   // odd count ends after its last round), then the epilogue's.  No path inside a round skips a barrier (`rare` rounds clear
   // the whole tile between the same two).  tests/test_gpu_even.py::test_chunk_shapes_pin_the_barrier_pairing runs chunks of
   // one, two and three queries, a short last chunk and one- and two-row batches.
+  // TWO: the same with ONE barrier per query on both sides -- 2 in the prologue, 1 per v in [v0, v1) (staging: behind the
+  // round's staging; adding: behind the round's adds and tests, the only one in `round`), then the same epilogue; the clears
+  // are in no barrier's way (tests/test_gpu_even_planes.py runs the same chunk shapes).
   // (Tried: a staging wave taking TWO sets of terms per round -- half the staging waves, one more adding wave; C3 7 x 5
   // window steps instead of 6 x 6.  The second set's registers tipped the kernel into scratch: 140 vs 101 ms.)
   const bool stager = wv < F;
   const int rank = wv - F;  // an adding wave's rank
   WaveWork wfa, wfb;
+  if constexpr (TWO) {  // "the round before the item's first": no chunks, idle lanes (its clear writes zeros over zeros)
+    wfb.info = 0u;
+#pragma unroll
+    for (int u = 0; u < U; ++u) wfb.pc[u] = apss_u32x2{0u, 0u};
+  }
   constexpr int slack = 2;  // (k_probe_coarse: the soundness argument of the coarse threshold)
   const int thr_c = (int)a.cx_theta - slack;
   const uint32_t thr1 = (uint32_t)max(thr_c, 1) - 1u;
@@ -357,13 +400,13 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
     const Seg P0 = load_P(I0), P1 = load_P(I1);
     __syncthreads();
     if (stager) {
-      flatten(P0, 0);
-      flatten(P1, 1);
+      flatten(P0, 0, TWO ? 3 : 0);
+      flatten(P1, 1, 1);
     }
     __syncthreads();
     if (!stager) {
       StripRead sr;
-      strip_read(sr, 0, rank);
+      strip_read(sr, 0, rank, TWO ? 3 : 0);
       strip_loads(wfa, sr, rank);
     }
   }
@@ -380,10 +423,15 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
       const RowExt R5 = load_R(v + 5);
       const TermW In = load_I(R4, wv, v + 4);
       const Seg Pn = load_P(Ic);
-      flatten(Pc, r2);
-      __syncthreads();  // every add of the round has landed
-      if (tid == 0) facts[r0] = make_uint2(0u, 0u);  // (read one round ago; staged again in the next round)
-      __syncthreads();  // cleared: the next query starts from zero
+      flatten(Pc, r2, r2);
+      if constexpr (TWO) {
+        if (tid == 0) facts[r0] = make_uint2(0u, 0u);  // (read one round ago; staged again in the next round: a barrier either way)
+        __syncthreads();  // the round's one barrier
+      } else {
+        __syncthreads();  // every add of the round has landed
+        if (tid == 0) facts[r0] = make_uint2(0u, 0u);  // (read one round ago; staged again in the next round)
+        __syncthreads();  // cleared: the next query starts from zero
+      }
       R4 = R5;
       Ic = In;
       Pc = Pn;
@@ -392,7 +440,30 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
   } else {
     // ---- adding waves ----
     const int atid = tid - F * kWave, ABLOCK = A * kWave;  // thread index / count among the adding waves (sweeps, whole-tile clears)
-    auto round = [&](WaveWork &w0, WaveWork &w2, const int v, const int r0) {
+    // TWO: the clear of a round whose postings `w` still holds, on that round's plane P (0 | 1), and the spare words' reset
+    // (1 in either plane's byte)
+    auto clear_round = [&](const WaveWork &w, const uint32_t P) {
+      *reinterpret_cast<uint32_t *>(smem_raw + (uint32_t)(CBMAX / APW) * 4u + (uint32_t)ln * 4u) = 0x0101u;
+      if ((w.info & kRare) != 0u) {
+        // its postings were not all in registers: the whole plane -- its bytes of every word, by an atomic AND that leaves the
+        // other plane's live sums alone (no value comes back: ds_and_b32)
+        const uint32_t keep = P ? 0x00ff00ffu : 0xff00ff00u;
+        for (int i = atid; i < cb / 2; i += ABLOCK) __hip_atomic_fetch_and(acc + i, keep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {
+        const int n = (int)((w.info >> 16) & 0xfu);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (u >= kFirstSkippable && u >= n) break;
+          // (an idle lane clears slot 0 of the plane: that round's sum, or zero)
+          smem_raw[(w.pc[u].x & 0xffffu) + P] = 0;
+          smem_raw[(w.pc[u].y & 0xffffu) + P] = 0;
+        }
+      }
+    };
+    auto round = [&](auto plane, WaveWork &w0, WaveWork &w2, const int v, const int r0) {
+      // TWO: this round's plane, a constant of each half of the loop below: it goes into the shift of an add and into the
+      // immediate offset of a clear
+      constexpr uint32_t P = TWO ? (uint32_t)decltype(plane)::value : 0u;
       const int r1 = r0 == 2 ? 0 : r0 + 1;
       const int q = v;
       // a crossing, reported by the wave that sees it (uniform control flow: one global atomic per wave and call)
@@ -417,13 +488,14 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
           }
         }
       };
-      auto slot_of = [&](const uint32_t pcw) { return WIDE ? pcw >> 15 : (SLOT2 && !ACC8 ? (pcw & 0xffffu) >> 1 : pcw & 0xffffu); };
+      auto slot_of = [&](const uint32_t pcw) { return WIDE ? pcw >> 15 : (SLOT2 && (!ACC8 || TWO) ? (pcw & 0xffffu) >> 1 : pcw & 0xffffu); };
       auto prod = [&](const uint32_t pcw, const float wqs) {
         const float x = __builtin_fmaf(wqs, __half2float(__ushort_as_half((unsigned short)(WIDE ? pcw & 0x7fffu : pcw >> 16))), 1.0f);
         return SIGNED ? (uint32_t)max((int)x, 1) : (uint32_t)x;
       };
       auto half_of = [&](const uint32_t old_word, const uint32_t pcw) {
         if (WIDE) return __builtin_amdgcn_ubfe(old_word, (pcw >> 12) & 24u, 8u);
+        if (TWO) return __builtin_amdgcn_ubfe(old_word, (pcw << 3) + 8u * P, 8u);  // (bit 0 of a posting is zero: 16 (slot % 2) + 8 P in the low five bits)
         return SLOT2 ? __builtin_amdgcn_ubfe(old_word, pcw << 3, ABITS) : (old_word >> ((pcw & 1u) << 4)) & 0xffffu;
       };
       constexpr int BATCH = 3;  // (one batch of all six steps of C3's window: no change, 101.1 ms)
@@ -434,6 +506,11 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
       // (LEAN, window path: not replaced -- the spare word's low accumulator is in [1, 2 U (NW - 1)], see check_batch)
       const uint32_t spare = (uint32_t)(CBMAX / APW) * 4u + (uint32_t)ln * 4u;
       auto add_or_spare = [&](const uint32_t pcw, const uint32_t p) -> uint32_t {
+        if constexpr (TWO) {
+          // byte 2 slot + P: the word of the 16-bit kernel's address, shift 16 (slot % 2) + 8 P -- instruction for instruction
+          // the 16-bit add ((pcw << 3) + 8 P is one v_lshl_add_u32); an idle lane adds 1 to its spare word's byte P
+          return atomicAdd(reinterpret_cast<uint32_t *>(smem_raw + (pcw ? pcw & 0xfffcu : spare)), p << (((pcw << 3) + 8u * P) & 31u));
+        }
         const uint32_t addr = WIDE ? (pcw >> 15) & 0x1fffcu : (SLOT2 ? pcw & 0xfffcu : ((pcw & 0xffffu) >> 1) * 4u);
         const uint32_t sh = WIDE ? (pcw >> 12) & 24u : (SLOT2 ? (pcw << 3) & 31u : (pcw & 1u) << 4);
         return atomicAdd(reinterpret_cast<uint32_t *>(smem_raw + (pcw ? addr : spare)), p << sh);
@@ -528,8 +605,11 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
           }
         }
       };
+      // TWO: the round before this one is cleared here, on the OTHER plane, from the registers that still hold its postings
+      // (strip_loads below overwrites them), directly ahead of this round's adds: one drain serves both
+      if constexpr (TWO) clear_round(w2, P ^ 1u);
       StripRead sr;
-      strip_read(sr, r1, rank);
+      strip_read(sr, r1, rank, r1);
       {
         uint32_t p0[BATCH], p1[BATCH], o0[BATCH], o1[BATCH];
         issue_batch(0, p0, p1, o0, o1);
@@ -588,6 +668,7 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
         }
       }
       __syncthreads();  // every add of the round has landed
+      if constexpr (TWO) return;  // (the round's one barrier: its clear is the next round's first act)
 
       if (LEAN) *reinterpret_cast<uint32_t *>(smem_raw + spare) = 1u;  // the idle lanes' word starts every round at 1
       if (rare) {  // (long or direct sweeps, or chunks past the window: their postings are not in registers) whole-tile clear
@@ -616,12 +697,18 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
       __syncthreads();  // cleared: the next query starts from zero
     };
     int r0 = 0;
+    constexpr std::integral_constant<int, 0> even_round{};
+    constexpr std::integral_constant<int, TWO ? 1 : 0> odd_round{};
     for (int v = v0; v < v1; v += 2) {
-      round(wfa, wfb, v, r0);
+      round(even_round, wfa, wfb, v, r0);
       r0 = r0 == 2 ? 0 : r0 + 1;
       if (v + 1 >= v1) break;
-      round(wfb, wfa, v + 1, r0);
+      round(odd_round, wfb, wfa, v + 1, r0);
       r0 = r0 == 2 ? 0 : r0 + 1;
+    }
+    if constexpr (TWO) {  // the last round's clear, behind its barrier: a later item of this workgroup finds both planes zero
+      if ((v1 - v0) & 1) clear_round(wfa, 0u);
+      else clear_round(wfb, 1u);
     }
   }
   __syncthreads();
@@ -649,7 +736,7 @@ __device__ __forceinline__ void probe_even_item(ProbeArgsK &a, const int tile, c
 // own_tile, the buffer descriptors -- is re-derived from the item, on the scalar unit.  Statistics are flushed per item
 // (`twice` depends on the item's tile).  Without a list (APSS_DEBUG=no_persist) workgroup b runs the one cell that blockIdx
 // names, derived here as work_cell() derives it on the host, and leaves.
-template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE>
+template <int BLOCK, int U, int LONGCAP, bool SHARD, bool SIGNED, bool ACC8, bool MERGE, bool TWO = false>
 __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
   // the grid launch's one cell, worked out before the loop and handed to it in three scalars (left inside the loop the
   // derivation is a loop invariant: hoisted with its intermediate values, 64-bit quotients among them, and kept across the item)
@@ -693,7 +780,7 @@ __device__ __forceinline__ void probe_even_body(const ProbeArgs &a) {
     // (DESIGN.md 5a): 48 scalar spills in the flagship instantiation against 11 this way (the grid launch had 3).
     ProbeArgsK *ak = reinterpret_cast<ProbeArgsK *>(reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()));
     asm volatile("" : "+s"(ak));
-    probe_even_item<BLOCK, U, LONGCAP, SHARD, SIGNED, ACC8, MERGE>(*ak, tile, v0, v1, own_tile, first);
+    probe_even_item<BLOCK, U, LONGCAP, SHARD, SIGNED, ACC8, MERGE, TWO>(*ak, tile, v0, v1, own_tile, first);
   }
 }
 
@@ -706,6 +793,12 @@ __global__ __launch_bounds__(BLOCK, BLOCK <= 512 ? 2 * BLOCK / 256 : BLOCK / 256
 template <int U, bool ACC8>
 __global__ __launch_bounds__(512, 4) void k_probe_even_merged(const ProbeArgs a) {
   probe_even_body<512, U, 128, true, false, ACC8, true>(a);
+}
+
+// the plain 512-thread rounds with TWO PLANES of 8-bit sums over <= 32768-row tiles and one barrier per round (see the header)
+template <int U>
+__global__ __launch_bounds__(512, 4) void k_probe_planes(const ProbeArgs a) {
+  probe_even_body<512, U, 128, false, false, true, false, true>(a);
 }
 
 }  // namespace apss

@@ -94,6 +94,8 @@ struct DebugCfg {
   int tiles_per_launch = 0;    // tiles_per_launch=N
   bool no_tail = false;        // no_tail        every insert extends the tile index at once (no tail of waiting rows)
   bool no_acc8 = false;        // no_acc8        term shards keep 16-bit accumulators over 32768-row tiles
+  bool no_planes = false;      // no_planes      a plain 512-thread handle keeps k_probe_even's 16-bit sums and two barriers per round (never k_probe_planes); no_acc8 implies it
+  bool planes = false;         // planes         ... and takes k_probe_planes whatever the length of its query chunks (default: chunks of kPlanesMinChunk rounds or more)
   int flat_group = -1;         // flat_group=L   k_probe_even: 2^L staging lanes per term (default: as many as keep the staging waves <= 1/4)
   int pad_lds = 0;             // pad_lds=N      N bytes of dynamic LDS on the filter launch (occupancy experiments)
   bool longpf = false;         // longpf         prefetched, group-parallel long-segment sweeps on a plain handle too (experiment)
@@ -151,6 +153,8 @@ DebugCfg parse_debug_env() {
     else if (key == "tiles_per_launch") d.tiles_per_launch = val;
     else if (key == "no_tail") d.no_tail = val != 0;
     else if (key == "no_acc8") d.no_acc8 = val != 0;
+    else if (key == "no_planes") d.no_planes = val != 0;
+    else if (key == "planes") d.planes = val != 0;
     else if (key == "no_even") d.no_even = val != 0;
     else if (key == "even_wide") d.even_wide = val != 0;
     else if (key == "longpf") d.longpf = val != 0;
@@ -1638,6 +1642,7 @@ struct CxVariant {
   bool acc8;    // 8-bit accumulators over 65536-row tiles: thin rounds of a term shard
   bool even;    // k_probe_even: a round is staged by ceil(longest query / 64) waves and its chunks dealt out evenly
   bool merge;   // k_probe_even<.., MERGE>: neighbouring query rows share a round (term shards)
+  bool planes;  // k_probe_planes: two planes of 8-bit sums over the 16-bit rendering of <= 32768-row tiles, one barrier per round (acc8 is set too)
 };
 
 // k_probe_even's instantiations: (threads, window steps, shard rule, signed weights, 8-bit accumulators)
@@ -1675,10 +1680,20 @@ struct CxVariant {
 #define APSS_EVEN_MERGE_VARIANTS(X) \
   X(7, false) X(6, false) X(5, false) X(4, false) X(3, false) X(2, false) \
   X(7, true) X(6, true) X(5, true) X(4, true) X(3, true) X(2, true)
+// ... and with two planes of 8-bit sums (k_probe_planes): every window a plain 512-thread handle takes (2 .. 6 steps; 7 only
+// under APSS_DEBUG=even_wide, which keeps k_probe_even: at 7 steps the clears ahead of the adds cost the kernel 20 B of scratch)
+#define APSS_EVEN_PLANES_VARIANTS(X) X(6) X(5) X(4) X(3) X(2)
 
 // THE lookup: the instantiation of a variant (fn == null: not listed).  The only walk of the three tables
 KernelRef cx_kernel(const CxVariant &v) {
   const bool even_shape = v.chunk == 16 && !v.vrows && !v.longpf;  // (what every k_probe_even is built for)
+  if (v.even && v.planes) {
+#define X(U) \
+    if (v.block == 512 && v.u == U && !v.shard && !v.sgn && v.acc8 && !v.merge && even_shape) return {kernel_addr(&k_probe_planes<U>), 512};
+    APSS_EVEN_PLANES_VARIANTS(X)
+#undef X
+    return {nullptr, 0};
+  }
   if (v.even && v.merge) {
 #define X(U, A8) \
     if (v.block == 512 && v.u == U && v.shard && !v.sgn && v.acc8 == A8 && even_shape) return {kernel_addr(&k_probe_even_merged<U, A8>), 512};
@@ -1856,6 +1871,7 @@ struct FilterFacts {
   int64_t s_max_nnz, s_nnz_end;  // longest staged query row, elements staged
   int64_t nq, idx_nnz;           // query rows, postings in the inverted index
   int max_merge_log2;            // k_probe_even: up to 2^this query rows may share a round (0: none)
+  double planes_scale;           // k_probe_planes: units per 1.0 at which this call's sums fit a byte (acc8_scale; 0: they do not)
 };
 
 // ---- which instantiation of the filter kernel: the register window (U steps of 8 chunks per wave) is sized for the
@@ -1965,6 +1981,19 @@ int32_t plan_filter(apss_handle *h, const FilterFacts &f, CxVariant &cxv, ProbeA
     a.flat_waves = (int32_t)flat_waves;
     a.flat_group_log2 = flat_group_log2;
     a.merge_log2 = m;
+  }
+  // TWO PLANES (apss_even.hpp): exactly where the plain 512-thread k_probe_even is taken -- same U, F and work list, the
+  // same 16-bit rendering of the index -- when the tiles fit a plane and this call's norms and row lengths leave room for byte
+  // sums; the caller launches it on the 8-bit scale.  A launch that turns out unselective latches the handle back (drop_planes).
+  // Only for query chunks of kPlanesMinChunk rounds or more: what the kernel saves, it saves per round, and what two planes cost
+  // they cost per item.  Measured (profiles/even_planes.md): the whole-store join of C3, chunks of 977 rounds (the last items
+  // in pieces of 128): filter kernel -2.2 %; C3 streamed in batches of 16,384 rows, chunks of 16 to 124 rounds: +0.6 %.
+  constexpr int kPlanesMinChunk = 256;
+  if (cxv.even && !cxv.merge && cxv.block == 512 && !cxv.shard && !cxv.sgn && !cxv.acc8 && h->cx.cb <= 32768 && f.planes_scale > 0 &&
+      (a.q_chunk >= kPlanesMinChunk || dbg.planes) && !dbg.no_planes && !dbg.no_acc8 && !h->no_acc8) {
+    CxVariant pv = cxv;
+    pv.acc8 = pv.planes = true;
+    if (cx_variant_exists(pv)) cxv = pv;
   }
   if (!cx_variant_exists(cxv)) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
   return APSS_OK;
@@ -2175,6 +2204,13 @@ int32_t stage_rows(apss_handle *h, Probe &pr) {
   s.c_max_nnz = h->head_k > 0 ? h->tv.max_nnz : h->store_max_nnz;  // longest indexed row
   s.idx_nnz = h->head_k > 0 ? std::max<int64_t>(h->tv.nnz, 1) : h->nnz;  // postings in the inverted index
   return APSS_OK;
+}
+
+// k_probe_planes passed too much: back to k_probe_even's 16-bit sums, for good; the call runs again on the index as it is
+int32_t drop_planes(apss_handle *h) {
+  h->no_acc8 = true;
+  h->downgrades |= APSS_DOWNGRADE_ACC8;
+  return kProbeAgain;
 }
 
 // back to 16-bit accumulators over smaller tiles, for good; the call runs again
@@ -2390,7 +2426,13 @@ int32_t plan_merged_rounds(apss_handle *h, Probe &pr) {
       ++max_merge_log2;
   pr.cxv = CxVariant{};
   if (pr.p.coarse_path)
-    APSS_TRY(plan_filter(h, FilterFacts{pr.p.a8_scale > 0, pr.p.shard_rule, pr.p.cx_signed, pr.p.hybrid, pr.s.max_nnz, pr.s.nnz_end, pr.q.nq, pr.s.idx_nnz, max_merge_log2}, pr.cxv, pr.a));
+    APSS_TRY(plan_filter(h, FilterFacts{pr.p.a8_scale > 0, pr.p.shard_rule, pr.p.cx_signed, pr.p.hybrid, pr.s.max_nnz, pr.s.nnz_end, pr.q.nq, pr.s.idx_nnz, max_merge_log2,
+                                             pr.p.mode == 0 && pr.s.max_nnz <= 512 ? acc8_scale(pr.p.bound, pr.p.cx_shared, pr.p.theta) : 0.0}, pr.cxv, pr.a));
+  if (pr.cxv.planes) {  // (the threshold in the units of byte sums, as a term shard's 8-bit filter takes it)
+    const double S = acc8_scale(pr.p.bound, pr.p.cx_shared, pr.p.theta);
+    pr.a.cx_scale = (float)S;
+    pr.a.cx_theta = (float)std::floor(pr.p.theta * S * (1.0 - 1.0 / 2048 - 1e-6));
+  }
   if (pr.a.merge_log2 > 0) {
     const double S = merged_scale(pr.p, pr.a.merge_log2);
     pr.a.cx_scale = (float)S;
@@ -2563,7 +2605,9 @@ void name_probe_kernel(apss_handle *h, const Probe &pr) {
   char *nm = h->st.probe_kernel;
   const size_t cap = sizeof(h->st.probe_kernel);
   if (pr.p.coarse_path && pr.cxv.even)
-    if (pr.cxv.merge) snprintf(nm, cap, "k_probe_even_merged<%d, %s>", pr.cxv.u, tf(pr.cxv.acc8));
+    // (k_probe_planes<U> to rocprofv3; here it reads as what it is, the plain 512-thread instantiation with one more flag)
+    if (pr.cxv.planes) snprintf(nm, cap, "k_probe_even<512, %d, 128, false, false, true, planes>", pr.cxv.u);
+    else if (pr.cxv.merge) snprintf(nm, cap, "k_probe_even_merged<%d, %s>", pr.cxv.u, tf(pr.cxv.acc8));
     else snprintf(nm, cap, "k_probe_even<%d, %d, %d, %s, %s, %s>", pr.cxv.block, pr.cxv.u, pr.cxv.block <= 512 ? 128 : 256, tf(pr.cxv.shard), tf(pr.cxv.sgn), tf(pr.cxv.acc8));
   else if (pr.p.coarse_path)
     snprintf(nm, cap, "k_probe_coarse<%d, %d, %d, %d, %s, %d, %s, %s, %s, %s>", pr.cxv.block, pr.cxv.u, pr.cxv.block <= 512 ? 128 : 256,
@@ -2810,7 +2854,7 @@ int32_t run_attempt(apss_handle *h, Probe &pr, int64_t *n_results) {
   // the 8-bit filter turned out unselective on this data (skewed terms: chance pairs share dozens of them, and every
   // shared term adds its unit of round-up): correct, but the survivors would swamp the exact pass.  Back to 16-bit
   // accumulators, for good, and run the call again.
-  if (pr.cxv.acc8 && (int64_t)n.c[kCtrResults] > std::max<int64_t>(64 * pr.q.nq, 4000000)) return drop_acc8(h, pr.p.shard_rule);
+  if (pr.cxv.acc8 && (int64_t)n.c[kCtrResults] > std::max<int64_t>(64 * pr.q.nq, 4000000)) return pr.cxv.planes ? drop_planes(h) : drop_acc8(h, pr.p.shard_rule);
   if (std::max(n.c[kCtrResults], n.c[kCtrOver]) > pr.a.res_cap) return grow_candidates(h, pr, n);
   return finish_call(h, pr, n, n_results);
 }

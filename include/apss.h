@@ -114,7 +114,10 @@ typedef struct apss_stats {
   char probe_kernel[96];    /* the probe kernel instantiation the last query-type call launched, as rocprofv3 prints its name up
                                to the template arguments' spelling, e.g. "k_probe_even<512, 6, 128, false, false, false>" (threads, window steps,
                                long-segment list, shard rule, signed, 8-bit accumulators) or "k_probe_even_merged<4, true>" (a term shard's rounds
-                               with two query rows each: window steps, 8-bit accumulators; queries_per_round); "" before any probe */
+                               with two query rows each: window steps, 8-bit accumulators; queries_per_round); "" before any probe.
+                               One name is not rocprofv3's: "k_probe_even<512, 6, 128, false, false, true, planes>" is the plain
+                               512-thread instantiation with two planes of 8-bit sums and one barrier per round, the kernel
+                               k_probe_planes<6> */
   int64_t device_posting_visits; /* posting visits the kernels of the last call actually made: equal to posting_visits except
                                     on a symmetric whole-store join, where posting_visits / candidate_pairs keep counting what
                                     the reference's two-directional probe visits and the device visits about half of it */
@@ -144,7 +147,9 @@ typedef struct apss_stats {
 #define APSS_SYM_CHUNK 6u        /* the query chunk does not divide a tile (query_chunk, filter_tile_rows) */
 
 #define APSS_DOWNGRADE_ACC8 1u /* 8-bit accumulators over 65536 / 131072-row tiles given up (a long row, a large norm, an
-                                  unselective byte filter): 16-bit accumulators over smaller tiles */
+                                  unselective byte filter): 16-bit accumulators over smaller tiles.  Also set when the two-plane
+                                  byte sums of a plain handle over <= 32768-row tiles proved unselective: back to 16-bit sums
+                                  over the same tiles, the one downgrade that rebuilds nothing */
 #define APSS_DOWNGRADE_HEAD 2u /* the dense-head block was given up (signed weights, norms out of range): its terms are back
                                   in the inverted index */
 
