@@ -33,6 +33,8 @@ SYMBOLS = [
     "apss_set_top_k_tile_cut", "apss_topk_tile_cut_get",
     # removal of stored vectors (csrc/apss_remove.hpp)
     "apss_remove", "apss_remove_dev", "apss_compact", "apss_set_auto_compact", "apss_removal_get",
+    # stored vectors as a query batch, by external id (csrc/apss_query_stored.hpp)
+    "apss_query_stored", "apss_query_stored_dev", "apss_stored_query_get",
 ]
 TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
 TILE_CUT_REMOVED = 4
@@ -112,6 +114,12 @@ class RemovalInfo(C.Structure):
                 ("removed_total", C.c_int64), ("pairs_dropped", C.c_int64), ("compacted_rows", C.c_int64),
                 ("auto_compact", C.c_double), ("mark_ms", C.c_double), ("drop_ms", C.c_double), ("compact_ms", C.c_double),
                 ("drop_launches", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class StoredQueryInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("launches", C.c_int32), ("ids_given", C.c_int64), ("ids_distinct", C.c_int64),
+                ("ids_missing", C.c_int64), ("rows_selected", C.c_int64), ("nnz_selected", C.c_int64),
+                ("select_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
 def build_sources():
@@ -286,5 +294,11 @@ def lib():
     L.apss_set_auto_compact.argtypes = [vp, C.c_double]
     L.apss_removal_get.restype = i32
     L.apss_removal_get.argtypes = [vp, C.POINTER(RemovalInfo)]
+    for name in ("apss_query_stored", "apss_query_stored_dev"):
+        f = getattr(L, name)
+        f.restype = i32
+        f.argtypes = [vp, i64, vp, pi64, pi64]
+    L.apss_stored_query_get.restype = i32
+    L.apss_stored_query_get.argtypes = [vp, C.POINTER(StoredQueryInfo)]
     _lib = L
     return L

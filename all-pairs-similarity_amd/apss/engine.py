@@ -216,6 +216,29 @@ class ApssIndex:
         self._chk(self._L.apss_removal_get(self._h, C.byref(ri)))
         return {k: getattr(ri, k) for k, _ in _lib.RemovalInfo._fields_}
 
+    def query_stored(self, ids, fetch=True):
+        """what is similar to the vectors already stored under `ids` (numpy / a sequence, or an int64 torch tensor on this
+        handle's GPU): every live stored row with one of these ids becomes a row of the query batch, in stored order, gathered on
+        the device exactly as it is stored (no second normalisation, prune or admission).  Ids that are not stored, removed or
+        repeated select nothing more.  Returns the pairs (fetch=True) or (rows of the batch, pairs)"""
+        rows, n = C.c_int64(0), C.c_int64(0)
+        if hasattr(ids, "data_ptr"):
+            import torch
+            assert ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+            ptr = C.c_void_p(ids.data_ptr()) if ids.numel() else C.c_void_p(0)
+            self._chk(self._L.apss_query_stored_dev(self._h, ids.numel(), ptr, C.byref(rows), C.byref(n)))
+        else:
+            ids = _np(ids, np.int64)
+            self._chk(self._L.apss_query_stored(self._h, ids.size, _ptr(ids), C.byref(rows), C.byref(n)))
+        return self.fetch() if fetch else (rows.value, n.value)
+
+    def stored_query_info(self):
+        """what the last query_stored selected and gathered (apss_stored_query_info)"""
+        qi = _lib.StoredQueryInfo()
+        qi.struct_size = C.sizeof(_lib.StoredQueryInfo)
+        self._chk(self._L.apss_stored_query_get(self._h, C.byref(qi)))
+        return {k: getattr(qi, k) for k, _ in _lib.StoredQueryInfo._fields_}
+
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`
         multiplies its share of the candidate tiles); fold_columns: how many of a wide head's 256 columns are folded ones

@@ -22,6 +22,7 @@
 #include "apss_topk.hpp"
 #include "apss_window.hpp"
 #include "apss_remove.hpp"
+#include "apss_query_stored.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -117,7 +118,8 @@ struct DebugCfg {
   bool no_persist = false;     // no_persist     k_probe_even launches one workgroup per (tile, chunk) cell, never resident workgroups over a work list
   int persist_wgs = 0;         // persist_wgs=N  ... the persistent launch has N workgroups (default: as many as the chip holds at a time)
   int persist_fine = 0;        // persist_fine=R ... and the last items of its list are R rounds long (a power of two; default kPersistFine)
-  int rm_grid = 0;             // rm_grid=N      at most N workgroups for k_rm_mark, k_rm_drop and k_rm_rows (tests of their grid-stride loops; default 4096 / 16384 / 4096)
+  int rm_grid = 0;             // rm_grid=N      at most N workgroups for k_rm_mark, k_rm_drop and k_rm_rows (tests of their grid-stride loops; default 4096 / 16384 / 4096),
+                               //                and for k_qs_select, k_qs_ids and k_qs_slots (apss_query_stored.hpp; default 4096 each)
 };
 
 DebugCfg parse_debug_env() {
@@ -366,6 +368,13 @@ struct apss_handle {
   hipEvent_t rm_ev0 = nullptr, rm_ev1 = nullptr;  // (created by the first apss_remove)
   double auto_compact = 0.0;
   apss_removal_info ri{};
+  // stored rows as a query batch (apss_query_stored.hpp): the found bytes of the sorted id list (which lives in rm_sorted), the id
+  // counters, the compact slot list, the events of the two phases, what the last call did
+  DevBuf<uint8_t> qs_found;
+  DevBuf<unsigned long long> qs_ctr;  // [2] distinct ids / distinct ids that selected nothing
+  DevBuf<int32_t> qs_slots;
+  hipEvent_t qs_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (created by the first apss_query_stored)
+  apss_stored_query_info qsi{};
   // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
@@ -3466,6 +3475,143 @@ int32_t auto_compact(apss_handle *h) {
   return compact_impl(h);
 }
 
+// apss_query_stored: the live stored rows named by d_ids[0, n) (device) become the staged query batch -- selected, scanned and
+// gathered on the device (apss_query_stored.hpp), never through ingest: they were normalised, pruned and admitted when they came
+// in -- and the batch is probed as the outside batch apss_query_dev would stage from the same rows.
+int32_t query_stored_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *n_rows, int64_t *n_results) {
+  // a query-type call: the last results and query batch are gone from here on (the staging is rewritten), also when it fails
+  h->n_res = -1;
+  h->res_q_ext = nullptr;
+  h->last_q_rowptr = nullptr;
+  h->last_q_idx = nullptr;
+  h->last_q_val = nullptr;
+  h->last_nq = 0;
+  h->qsi = apss_stored_query_info{};
+  h->qsi.ids_given = n;
+  const int64_t rows = h->n_rows;
+  int64_t sel_rows = 0, sel_nnz = 0;
+  if (n > 0) {
+    for (hipEvent_t &e : h->qs_ev)
+      if (!e) HIPCHK(h, hipEventCreate(&e));
+    if (h->rm_marked > 0) APSS_TRY(rm_extend(h));
+    APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
+    APSS_TRY(ensure(h, h->qs_found, (size_t)n));
+    APSS_TRY(ensure(h, h->qs_ctr, 2));
+    size_t tmp_bytes = 0;
+    HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+    APSS_TRY(ensure(h, h->rm_tmp, tmp_bytes + 256));
+    if (rows > 0) {
+      APSS_TRY(ensure(h, h->s_keep, (size_t)rows + 1));
+      APSS_TRY(ensure(h, h->s_cnt, (size_t)rows + 1));
+      APSS_TRY(ensure(h, h->s_rowdst, (size_t)rows + 1));
+      APSS_TRY(ensure(h, h->s_nnzdst, (size_t)rows + 1));
+    }
+    HIPCHK(h, hipEventRecord(h->qs_ev[0], h->stream));
+    HIPCHK(h, hipMemsetAsync(h->qs_found.p, 0, (size_t)n, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->qs_ctr.p, 0, 2 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+    if (rows > 0) {
+      QsSelectArgs s{};
+      s.ext = h->ext.p;
+      s.rowptr = h->rowptr.p;
+      s.rows = rows;
+      s.dead = h->rm_marked > 0 ? h->dead.p : nullptr;  // (nothing marked: nothing of the map is read)
+      s.ids = h->rm_sorted.p;
+      s.n_ids = n;
+      s.found = h->qs_found.p;
+      s.keep = h->s_keep.p;
+      s.cnt = h->s_cnt.p;
+      const int64_t blocks = ceil_div(ceil_div(rows, 2), kQsThreads);
+      hipLaunchKernelGGL(k_qs_select, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream, s);
+      HIPCHK(h, hipGetLastError());
+      ++h->qsi.launches;
+      APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, rows));
+      APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, rows));
+    }
+    hipLaunchKernelGGL(k_qs_ids, dim3((unsigned)std::min<int64_t>(ceil_div(n, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
+                       (const int64_t *)h->rm_sorted.p, n, (const uint8_t *)h->qs_found.p, h->qs_ctr.p);
+    HIPCHK(h, hipGetLastError());
+    ++h->qsi.launches;
+    HIPCHK(h, hipEventRecord(h->qs_ev[1], h->stream));
+    // the ONE readback between selection and gather: the two scan totals and the id counts
+    int64_t back_stack[4] = {0, 0, 0, 0};
+    int64_t *back = h->pin ? reinterpret_cast<int64_t *>(h->pin + kPinBytes + 640) : back_stack;
+    back[0] = back[1] = 0;
+    if (rows > 0) {
+      HIPCHK(h, hipMemcpyAsync(&back[0], h->s_rowdst.p + rows, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(&back[1], h->s_nnzdst.p + rows, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(&back[2], h->qs_ctr.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the caller's id array may be reused from here on)
+    sel_rows = back[0];
+    sel_nnz = back[1];
+    h->qsi.ids_distinct = back[2];
+    h->qsi.ids_missing = back[3];
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->qs_ev[0], h->qs_ev[1]));
+    h->qsi.select_ms = ms;
+    if (sel_rows < 0 || sel_rows > rows || sel_nnz < 0 || sel_nnz > h->nnz) return fail(h, APSS_E_STATE, "apss_query_stored: the selection and the store disagree");
+  }
+  h->qsi.rows_selected = sel_rows;
+  h->qsi.nnz_selected = sel_nnz;
+  if (n_rows) *n_rows = sel_rows;
+  h->q_nonneg = true;
+  h->q_max_nnz = 0;
+  h->q_max_norm2 = 0.f;
+  if (sel_rows > 0) {
+    APSS_TRY(ensure(h, h->qs_slots, (size_t)sel_rows));
+    APSS_TRY(ensure(h, h->q_rowptr, (size_t)sel_rows + 1));
+    APSS_TRY(ensure(h, h->q_ext, (size_t)sel_rows));
+    APSS_TRY(ensure(h, h->q_idx, (size_t)std::max<int64_t>(sel_nnz, 1)));
+    APSS_TRY(ensure(h, h->q_val, (size_t)std::max<int64_t>(sel_nnz, 1)));
+    APSS_TRY(ensure(h, h->flagword, 4));
+    HIPCHK(h, hipEventRecord(h->qs_ev[2], h->stream));
+    HIPCHK(h, hipMemsetAsync(h->flagword.p, 0, 4 * sizeof(unsigned int), h->stream));
+    hipLaunchKernelGGL(k_qs_slots, dim3((unsigned)std::min<int64_t>(ceil_div(rows, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
+                       (const int64_t *)h->s_keep.p, (const int64_t *)h->s_rowdst.p, rows, h->qs_slots.p);
+    HIPCHK(h, hipGetLastError());
+    QsGatherArgs g{};
+    g.slots = h->qs_slots.p;
+    g.n_sel = sel_rows;
+    g.rowptr = h->rowptr.p;
+    g.ext = h->ext.p;
+    g.idx = h->idx.p;
+    g.val = h->val.p;
+    g.nnz_dst = h->s_nnzdst.p;
+    g.o_rowptr = h->q_rowptr.p;
+    g.o_ext = h->q_ext.p;
+    g.o_idx = h->q_idx.p;
+    g.o_val = h->q_val.p;
+    g.flags_out = h->flagword.p;
+    // (one wave per SELECTED row: the grid does not know how many rows are stored)
+    hipLaunchKernelGGL(k_qs_gather, dim3((unsigned)ceil_div(sel_rows * kQsWave, kQsThreads)), dim3(kQsThreads), 0, h->stream, g);
+    HIPCHK(h, hipGetLastError());
+    h->qsi.launches += 2;
+    HIPCHK(h, hipEventRecord(h->qs_ev[3], h->stream));
+    // the batch summaries: the probe plans on the host with them, before its first launch
+    unsigned int flags_stack[4] = {0, 0, 0, 0};
+    unsigned int *flags_host = h->pin ? reinterpret_cast<unsigned int *>(h->pin + kPinBytes) : flags_stack;
+    HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->qs_ev[2], h->qs_ev[3]));
+    h->qsi.gather_ms = ms;
+    APSS_TRY(take_ingest_flags(h, flags_host, false));
+    // the batch's rows of the dense-head block and its tail ratios, as query_dev_impl packs them
+    if (h->head_k && !h->sharded) APSS_TRY(pack_query_head(h, h->q_rowptr.p, h->q_idx.p, h->q_val.p, sel_rows));
+  }
+  return probe(h, sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz, n_results);
+}
+
+int32_t check_stored_query(apss_handle *h, const char *what, int64_t n, const int64_t *ids, int64_t *n_rows, int64_t *n_results) {
+  if (n_rows) *n_rows = 0;
+  if (n_results) *n_results = 0;
+  if (h->sharded) return fail(h, APSS_E_UNSUPPORTED, std::string(what) + ": not on a term shard (it holds slices of rows; a query batch needs whole ones)");
+  if (n < 0 || (n > 0 && !ids)) return fail(h, APSS_E_INVALID, std::string(what) + ": n >= 0 ids");
+  if (n > 0x7fffffffLL) return fail(h, APSS_E_INVALID, std::string(what) + ": more than 2^31 - 1 ids in one call");
+  return APSS_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -3587,6 +3733,9 @@ void apss_destroy(apss_handle *h) {
   release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
   if (h->rm_ev0) (void)hipEventDestroy(h->rm_ev0);
   if (h->rm_ev1) (void)hipEventDestroy(h->rm_ev1);
+  release(h->qs_found); release(h->qs_ctr); release(h->qs_slots);
+  for (hipEvent_t e : h->qs_ev)
+    if (e) (void)hipEventDestroy(e);
   if (h->pin) (void)hipHostFree(h->pin);
   release(h->wl_dev);
   if (h->wl_pin) (void)hipHostFree(h->wl_pin);
@@ -3940,6 +4089,33 @@ int32_t apss_removal_get(apss_handle *h, apss_removal_info *out) {
   h->ri.rows_live = h->n_rows - h->rm_marked;
   h->ri.auto_compact = h->auto_compact;
   std::memcpy(out, &h->ri, (size_t)n);
+  return APSS_OK;
+}
+
+int32_t apss_query_stored(apss_handle *h, int64_t n, const int64_t *ext_ids, int64_t *n_rows, int64_t *n_results) {
+  APSS_TRY(enter(h));
+  APSS_TRY(check_stored_query(h, "apss_query_stored", n, ext_ids, n_rows, n_results));
+  if (n > 0) {
+    APSS_TRY(ensure(h, h->rm_ids, (size_t)n));
+    HIPCHK(h, hipMemcpyAsync(h->rm_ids.p, ext_ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  }
+  return query_stored_impl(h, n, h->rm_ids.p, n_rows, n_results);  // (synchronises when n > 0: the caller's array may be reused on return)
+}
+
+int32_t apss_query_stored_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int64_t *n_rows, int64_t *n_results) {
+  APSS_TRY(enter(h));
+  APSS_TRY(check_stored_query(h, "apss_query_stored_dev", n, d_ext_ids, n_rows, n_results));
+  return query_stored_impl(h, n, d_ext_ids, n_rows, n_results);
+}
+
+int32_t apss_stored_query_get(apss_handle *h, apss_stored_query_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_stored_query_info.struct_size must be set to sizeof(apss_stored_query_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_stored_query_info));
+  h->qsi.struct_size = n;
+  std::memcpy(out, &h->qsi, (size_t)n);
   return APSS_OK;
 }
 

@@ -294,6 +294,36 @@ bool GpuIndexingWorker::compact() {
   return true;
 }
 
+SimilarityOutput GpuIndexingWorker::similarTo(const std::vector<std::string> &ids) {
+  SimilarityOutput out;
+  out.outputMoment = now_ms();
+  if (g_) {
+    last_error_ = "similarTo: a term-sharded worker holds slices of vectors (cpslab.allpair.gpu.devices with one entry)";
+    return out;
+  }
+  std::vector<int64_t> ext;
+  for (const std::string &s : ids) {
+    const auto it = id_of_.find(s);
+    if (it != id_of_.end()) ext.push_back(it->second);
+  }
+  int64_t n_rows = 0, n_res = 0;
+  if (apss_query_stored(h_, (int64_t)ext.size(), ext.data(), &n_rows, &n_res) != APSS_OK) {
+    last_error_ = std::string("apss_query_stored: ") + apss_last_error(h_);
+    return out;
+  }
+  std::vector<int64_t> q((size_t)n_res), c((size_t)n_res);
+  std::vector<float> s((size_t)n_res);
+  if (n_res && apss_fetch_results(h_, 0, n_res, q.data(), c.data(), s.data()) != APSS_OK) {
+    last_error_ = std::string("apss_fetch_results: ") + apss_last_error(h_);
+    return out;
+  }
+  // every known name gets an entry, possibly empty (as handle() gives every query one; IndexingWorkerActor.scala:106-107)
+  for (const int64_t id : ext) out.output[name_of_[(size_t)id]];
+  for (int64_t i = 0; i < n_res; ++i) out.output[name_of_[(size_t)q[i]]][name_of_[(size_t)c[i]]] = (double)s[i];
+  out.outputMoment = now_ms();
+  return out;
+}
+
 int64_t GpuIndexingWorker::liveVectors() const {
   if (g_) return storedVectors();
   apss_removal_info ri{};

@@ -132,6 +132,12 @@ class GpuIndexingWorker {
   // rebuild store and index from the live vectors on the device (apss_compact); false and lastError() when refused
   bool compact();
   int64_t liveVectors() const;  // storedVectors() minus the removed ones
+  // "What is similar to these vectors that you already hold?" (apss_query_stored; the reference answers a vector only at the
+  // moment it arrives, IndexingWorkerActor.scala:123-137).  The reply is what an IndexData with stopUpdateIndex set replies for
+  // those vectors as they are stored, with an entry, possibly empty, for every name the worker was ever sent (a withdrawn
+  // vector's stays empty); nothing is inserted.  Unknown names are ignored.  A term-sharded worker refuses: an empty reply and
+  // lastError()
+  SimilarityOutput similarTo(const std::vector<std::string> &ids);
   const std::string &lastError() const { return last_error_; }
 
  private:

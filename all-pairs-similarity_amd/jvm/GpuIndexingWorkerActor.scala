@@ -83,6 +83,26 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
   def removeVectors(names: Iterable[String]): Long =
     if (grouped) throw new UnsupportedOperationException("removal needs one GPU (cpslab.allpair.gpu.devices with one entry)")
     else NativeApss.remove(handle, names.flatMap(idOf.get).toArray)
+  /** "what is similar to these vectors that you already hold?" (apss_query_stored): the stored vectors named here are queried
+    * against the store as they are stored, nothing is inserted, and the SimilarityOutput is replied the way the IndexData handler
+    * replies its own.  Unknown names are ignored; every known name gets an entry, possibly empty */
+  def similarTo(names: Iterable[String]): Unit = {
+    if (grouped) throw new UnsupportedOperationException("similarTo needs one GPU (cpslab.allpair.gpu.devices with one entry)")
+    val ids = names.flatMap(idOf.get).toArray
+    val n = NativeApss.queryStored(handle, ids)
+    if (n < 0) throw new IllegalArgumentException(lastError)
+    val q = new Array[Long](n.toInt); val c = new Array[Long](n.toInt); val s = new Array[Float](n.toInt)
+    if (n > 0) fetch(n, q, c, s)
+    val out = new mutable.HashMap[String, mutable.HashMap[String, Double]]
+    ids.foreach(i => out.getOrElseUpdate(nameOf(i.toInt), new mutable.HashMap[String, Double]))
+    for (i <- 0 until n.toInt) out(nameOf(q(i).toInt)) += nameOf(c(i).toInt) -> s(i).toDouble
+    reply(out)
+  }
+  private def reply(out: mutable.HashMap[String, mutable.HashMap[String, Double]]): Unit =
+    if (replyTo.isDefined) {
+      if (outputWritingDuration <= 0) replyTo.get ! SimilarityOutput(out, System.currentTimeMillis())
+      else for ((q, m) <- out; (c, s) <- m) writeBuffer.getOrElseUpdate(q, new mutable.HashMap[String, Double]) += c -> s
+    }
   private def submit(mode: Int, rowptr: Array[Long], indices: Array[Int], values: Array[Double], ids: Array[Long]): Long =
     if (grouped) NativeApss.groupSubmit(handle, mode, rowptr, indices, values, ids)
     else NativeApss.submit(handle, mode, rowptr, indices, values, ids)
@@ -138,11 +158,7 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
   def receive: Receive = {
     case IndexData(vectors) =>
       try {
-        val out = runBatch(vectors)
-        if (replyTo.isDefined) {
-          if (outputWritingDuration <= 0) replyTo.get ! SimilarityOutput(out, System.currentTimeMillis())
-          else for ((q, m) <- out; (c, s) <- m) writeBuffer.getOrElseUpdate(q, new mutable.HashMap[String, Double]) += c -> s
-        }
+        reply(runBatch(vectors))
       } catch {
         case e: Exception => e.printStackTrace()
       }

@@ -34,6 +34,12 @@ object NativeApss {
   /** cpslab.allpair.gpu.autoCompact: compact before an insert once more than `fraction` (in [0, 1); 0 = off) of the stored
     * vectors is removed.  0 or a negative status */
   def setAutoCompact(h: Long, fraction: Double): Int = submit(h, 5, Array(0L, 1L), Array(0), Array(fraction), Array(0L)).toInt
+  /** "what is similar to these vectors that you already hold?" (include/apss.h, apss_query_stored; one handle only): every live
+    * stored vector whose id is in `ids` is queried against the store exactly as it is stored, on the device; nothing is
+    * inserted.  Travels through `submit` (mode 6 of apss_jni.c).  Returns #results (then `fetch`) or a negative status; ids that
+    * are unknown, removed or repeated ask nothing more */
+  def queryStored(h: Long, ids: Array[Long]): Long =
+    submit(h, 6, new Array[Long](ids.length + 1), new Array[Int](0), new Array[Double](0), ids)
   /** name the dense-head block's terms instead of the library's policy (include/apss.h, apss_set_head_terms; a handle made by
     * `create` holds the whole term space: part = 0, nParts = 1); empty handle only.  Returns 0 or a negative status.
     * (Term-sharded deployments do not call this: a group -- createGroup -- gives its members their shares itself.) */

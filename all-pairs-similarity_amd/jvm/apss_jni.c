@@ -130,6 +130,9 @@ static int32_t handle_submit(void *t, int mode, int64_t n, const int64_t *rp, co
   if (mode == 3) return apss_remove((apss_handle *)t, n, id, n_res);
   if (mode == 4) return apss_compact((apss_handle *)t);
   if (mode == 5) return apss_set_auto_compact((apss_handle *)t, n == 1 && rp[1] == 1 ? vl[0] : -1.0);
+  /* ... and so does the query of stored vectors by id (NativeApss.queryStored): mode 6 = apss_query_stored of the n ids (the CSR
+   * is n empty rows); the result triples are fetched as after any query */
+  if (mode == 6) return apss_query_stored((apss_handle *)t, n, id, NULL, n_res);
   return apss_insert_and_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
 }
 

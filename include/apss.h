@@ -411,6 +411,58 @@ int32_t apss_compact(apss_handle *h);
 int32_t apss_set_auto_compact(apss_handle *h, double fraction);
 int32_t apss_removal_get(apss_handle *h, apss_removal_info *out);
 
+/* ---- query stored vectors by external id, gathered on the device ----
+ * "What is similar to these items that you already hold?"  The reference never asks: its actor answers a vector only at the
+ * moment it arrives (IndexingWorkerActor.scala:123-137) and keeps nothing but a String -> Long id map on the JVM side.  Plain
+ * handles only.
+ *
+ * The batch.
+ *  - It holds every live stored row whose external id is in the list, in stored (slot) order.
+ *  - A row that is marked removed is not selected.
+ *  - An id carried by two live rows selects both.
+ *  - An id that is repeated in the list, not stored, or stored only as marked rows selects nothing more.
+ *  - *n_rows (may be NULL) is the number of rows in the batch.
+ * The answer.
+ *  - It is what apss_query_dev gives for those rows exactly as apss_get_store_dev shows them.
+ *  - Normalisation, value prune and admission are not applied again.
+ *  - Self-exclusion is by external id, so a selected row never pairs with its twin under the same id.
+ *  - Pairs with marked candidates are dropped by the existing k_rm_drop, before the top-k cut.
+ *  - apss_set_top_k, apss_set_top_k_window and apss_set_top_k_tile_cut apply as to any outside batch.
+ *  - The call takes no symmetric join even when every stored id is named: apss_stats.symmetric = 0,
+ *    symmetric_declined = APSS_SYM_NOT_WHOLE.
+ *  - It builds nothing.  Rows waiting outside the tile index are met the way apss_query meets them.
+ *  - It is not an insert-type call, so auto-compaction does not run.
+ * Results.
+ *  - It is a query-type call.
+ *  - It invalidates the last results on entry, as apss_query_dev does, including when it fails afterwards.
+ *  - apss_results_dev gives the query row within the batch.
+ *  - apss_ext_ids_dev's d_query_ext gives the batch's ids.
+ * Edge cases.
+ *  - n == 0, an empty store, or nothing selected: APSS_OK, *n_rows = 0, *n_results = 0, apss_result_count answers 0.
+ * Errors.
+ *  - APSS_E_INVALID: NULL handle, n < 0, NULL ids with n > 0, n > 2^31 - 1.
+ *  - APSS_E_UNSUPPORTED ("term shard"): a term shard.  It holds slices of rows.
+ *  - apss_group has no such call: its members hold slices of rows (term ranges) or of the store (row ranges).
+ *
+ * The rows are selected and copied on the device and cross no ingest: the id list is sorted (rocprim radix sort), ONE pass over
+ * the store's external ids selects (k_qs_select; it reads the marks only while rows are marked), one pass over the sorted list
+ * counts (k_qs_ids), and a gather whose grid is sized by the rows SELECTED (k_qs_slots, k_qs_gather) writes them into the query
+ * staging together with the batch summaries the probe plans with.  The call then takes the path apss_query_dev of the same rows
+ * takes.  _dev: d_ext_ids int64[n] on the handle's device, read on the handle's stream.  Both forms synchronise that stream. */
+typedef struct apss_stored_query_info {
+  int32_t struct_size;     /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t launches;        /* k_qs_* launches of the last apss_query_stored[_dev] (the id sort is not counted) */
+  int64_t ids_given;       /* n */
+  int64_t ids_distinct;    /* distinct ids in the list */
+  int64_t ids_missing;     /* distinct ids with no LIVE stored row */
+  int64_t rows_selected;   /* rows of the query batch */
+  int64_t nnz_selected;    /* their entries */
+  double select_ms, gather_ms; /* device time, HIP events */
+} apss_stored_query_info;    /* 64 bytes */
+int32_t apss_query_stored(apss_handle *h, int64_t n, const int64_t *ext_ids, int64_t *n_rows, int64_t *n_results);
+int32_t apss_query_stored_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int64_t *n_rows, int64_t *n_results);
+int32_t apss_stored_query_get(apss_handle *h, apss_stored_query_info *out);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
