@@ -35,6 +35,8 @@ SYMBOLS = [
     "apss_remove", "apss_remove_dev", "apss_compact", "apss_set_auto_compact", "apss_removal_get",
     # stored vectors as a query batch, by external id (csrc/apss_query_stored.hpp)
     "apss_query_stored", "apss_query_stored_dev", "apss_stored_query_get",
+    # the global top-K of a call (csrc/apss_top_pairs.hpp)
+    "apss_set_top_pairs", "apss_top_pairs_get",
 ]
 TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
 TILE_CUT_REMOVED = 4
@@ -44,6 +46,7 @@ EXCHANGE_NONE, EXCHANGE_COPIES, EXCHANGE_RCCL = 0, 1, 2
 GROUP_MAX_MEMBERS = 64
 DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
 TOP_K_MAX = 1024
+TOP_PAIRS_MAX = 1 << 20
 SYM_RAN, SYM_FLAG, SYM_NOT_WHOLE, SYM_PATH, SYM_LONG_ROWS, SYM_ONE_TILE, SYM_CHUNK = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -120,6 +123,12 @@ class StoredQueryInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("launches", C.c_int32), ("ids_given", C.c_int64), ("ids_distinct", C.c_int64),
                 ("ids_missing", C.c_int64), ("rows_selected", C.c_int64), ("nnz_selected", C.c_int64),
                 ("select_ms", C.c_double), ("gather_ms", C.c_double)]
+
+
+class TopPairsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("launches", C.c_int32), ("k_pairs", C.c_int64), ("pairs_in", C.c_int64),
+                ("kept", C.c_int64), ("above", C.c_int64), ("tied", C.c_int64), ("tied_kept", C.c_int64),
+                ("kth_score", C.c_double), ("select_ms", C.c_double)]
 
 
 def build_sources():
@@ -300,5 +309,9 @@ def lib():
         f.argtypes = [vp, i64, vp, pi64, pi64]
     L.apss_stored_query_get.restype = i32
     L.apss_stored_query_get.argtypes = [vp, C.POINTER(StoredQueryInfo)]
+    L.apss_set_top_pairs.restype = i32
+    L.apss_set_top_pairs.argtypes = [vp, i64]
+    L.apss_top_pairs_get.restype = i32
+    L.apss_top_pairs_get.argtypes = [vp, C.POINTER(TopPairsInfo)]
     _lib = L
     return L

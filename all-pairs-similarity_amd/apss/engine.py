@@ -27,7 +27,7 @@ def _ptr(a):
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
                  capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False,
-                 auto_compact=0.0):
+                 auto_compact=0.0, top_pairs=0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -48,7 +48,7 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
-        if top_k or top_k_window or top_k_tile_cut or auto_compact:
+        if top_k or top_k_window or top_k_tile_cut or auto_compact or top_pairs:
             try:
                 if auto_compact:
                     self.set_auto_compact(auto_compact)
@@ -58,6 +58,8 @@ class ApssIndex:
                     self.set_top_k_tile_cut(True)
                 if top_k:
                     self.set_top_k(top_k)
+                if top_pairs:
+                    self.set_top_pairs(top_pairs)
             except ApssError:
                 self.close()
                 raise
@@ -238,6 +240,18 @@ class ApssIndex:
         qi.struct_size = C.sizeof(_lib.StoredQueryInfo)
         self._chk(self._L.apss_stored_query_get(self._h, C.byref(qi)))
         return {k: getattr(qi, k) for k, _ in _lib.StoredQueryInfo._fields_}
+
+    def set_top_pairs(self, K):
+        """global top-K for the query-type calls made from now on (0: off): a call's final list becomes its K best pairs in rank
+        order (score descending, then query id, candidate id, query row, slot ascending), selected on the device"""
+        self._chk(self._L.apss_set_top_pairs(self._h, int(K)))
+
+    def top_pairs_info(self):
+        """what the global top-K did in the last query-type call (apss_top_pairs_info)"""
+        ti = _lib.TopPairsInfo()
+        ti.struct_size = C.sizeof(_lib.TopPairsInfo)
+        self._chk(self._L.apss_top_pairs_get(self._h, C.byref(ti)))
+        return {k: getattr(ti, k) for k, _ in _lib.TopPairsInfo._fields_}
 
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`

@@ -23,6 +23,7 @@
 #include "apss_window.hpp"
 #include "apss_remove.hpp"
 #include "apss_query_stored.hpp"
+#include "apss_top_pairs.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -120,6 +121,7 @@ struct DebugCfg {
   int persist_fine = 0;        // persist_fine=R ... and the last items of its list are R rounds long (a power of two; default kPersistFine)
   int rm_grid = 0;             // rm_grid=N      at most N workgroups for k_rm_mark, k_rm_drop and k_rm_rows (tests of their grid-stride loops; default 4096 / 16384 / 4096),
                                //                and for k_qs_select, k_qs_ids and k_qs_slots (apss_query_stored.hpp; default 4096 each)
+  int tp_grid = 0;             // tp_grid=N      at most N workgroups for the grid-stride kernels of the global top-K (apss_top_pairs.hpp; default kTpGridCap)
 };
 
 DebugCfg parse_debug_env() {
@@ -180,6 +182,7 @@ DebugCfg parse_debug_env() {
     else if (key == "persist_wgs") d.persist_wgs = val;
     else if (key == "persist_fine") d.persist_fine = val;
     else if (key == "rm_grid") d.rm_grid = val;
+    else if (key == "tp_grid") d.tp_grid = val;
     else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
@@ -375,6 +378,10 @@ struct apss_handle {
   DevBuf<int32_t> qs_slots;
   hipEvent_t qs_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (created by the first apss_query_stored)
   apss_stored_query_info qsi{};
+  // global top-K (apss_top_pairs.hpp): the setting, the stage's buffers, what the last query-type call did
+  int64_t top_pairs = 0;
+  TpWork tp;
+  apss_top_pairs_info tpi{};
   // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
@@ -3056,9 +3063,9 @@ int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
 // A query-type call: the join (probe_inner runs its pass again after a downgrade or a rebuild; what it leaves is the call's final
 // list), then, while rows are marked removed, ONE filter of that list (apss_remove.hpp), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
 // apss_set_top_k_window, join and pass window by window over the query rows (apss_window.hpp), the kept lists concatenated.
-int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-              int64_t q_nnz_end, int64_t *n_results) {
+int32_t probe_lists(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+                    int64_t q_nnz_end, int64_t *n_results) {
   h->tk = apss_topk_info{};
   h->tw = apss_topk_window_info{};
   h->tw.max_pairs = h->top_k_window;
@@ -3186,6 +3193,46 @@ int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t
   h->st.result_pairs = n_out;
   if (n_results) *n_results = n_out;
   return APSS_OK;
+}
+
+// The global cut of the call's final list (apss_top_pairs.hpp): h->out_* / h->n_res become its K best pairs in rank order.
+int32_t cut_top_pairs(apss_handle *h, int64_t nq, const int64_t *q_ext, int64_t *n_results) {
+  h->tpi.pairs_in = h->n_res;
+  if (h->n_res <= 0) return APSS_OK;
+  if (h->n_res > 0xffffffffLL) {
+    h->n_res = -1;
+    return fail(h, APSS_E_UNSUPPORTED, "global top-K: a final list of 2^32 pairs or more");
+  }
+  unsigned long long words_stack[kTpWords];
+  unsigned long long *words = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 768) : words_stack;
+  const size_t before = h->tp.bytes;
+  const char *bad = nullptr;
+  const hipError_t e = tp_run(h->tp, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, q_ext, nq, h->ext.p, h->n_rows, h->top_pairs,
+                              h->dbgcfg.tp_grid > 0 ? h->dbgcfg.tp_grid : kTpGridCap, words, &h->tpi, &bad);
+  h->bytes_reserved += h->tp.bytes - before;
+  if (e != hipSuccess) {
+    h->n_res = -1;
+    h->err = std::string("global top-K: ") + (bad ? bad : hipGetErrorString(e));
+    return bad ? APSS_E_STATE : e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
+  }
+  h->out_q = h->tp.out_q;
+  h->out_c = h->tp.out_c;
+  h->out_s = h->tp.out_s;
+  h->n_res = h->tpi.kept;
+  h->st.result_pairs = h->n_res;
+  if (n_results) *n_results = h->n_res;
+  return APSS_OK;
+}
+
+// A query-type call: its final list (probe_lists), then, with apss_set_top_pairs, ONE global cut of that list.
+int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
+              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
+              int64_t q_nnz_end, int64_t *n_results) {
+  h->tpi = apss_top_pairs_info{};
+  h->tpi.k_pairs = h->top_pairs;
+  APSS_TRY(probe_lists(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
+  if (h->top_pairs <= 0 || h->sharded) return APSS_OK;
+  return cut_top_pairs(h, nq, q_ext, n_results);
 }
 
 int32_t validate_host_csr(apss_handle *h, int64_t n, const int64_t *rowptr, const int32_t *indices,
@@ -3728,6 +3775,7 @@ void apss_destroy(apss_handle *h) {
   release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
   release(h->head_ctr); h->uq.release(); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
+  tp_release(h->tp);
   release(h->win_df); release(h->win_b); h->win.release();
   release(h->row_pairs);
   release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
@@ -4004,6 +4052,28 @@ int32_t apss_set_top_k(apss_handle *h, int32_t k) {
   if (k > 0 && h->sharded)
     return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_k: a term shard reports candidates with partial scores; the group cuts behind its exchange");
   h->top_k = k;
+  return APSS_OK;
+}
+
+int32_t apss_set_top_pairs(apss_handle *h, int64_t k_pairs) {
+  if (!h) return APSS_E_INVALID;
+  // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
+  if (k_pairs < 0 || k_pairs > APSS_TOP_PAIRS_MAX)
+    return fail(h, APSS_E_INVALID, g_create_error = "apss_set_top_pairs: k_pairs must be in [0, 2^20] (0: off)");
+  if (k_pairs > 0 && h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_top_pairs: a term shard reports candidates with partial scores; it has no final list to cut");
+  h->top_pairs = k_pairs;
+  return APSS_OK;
+}
+
+int32_t apss_top_pairs_get(apss_handle *h, apss_top_pairs_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_top_pairs_info.struct_size must be set to sizeof(apss_top_pairs_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_top_pairs_info));
+  h->tpi.struct_size = n;
+  std::memcpy(out, &h->tpi, (size_t)n);
   return APSS_OK;
 }
 

@@ -233,6 +233,10 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
         throw std::runtime_error(msg);
       }
     }
+    if (conf.topPairs != 0) {  // a group's list lies behind its exchange: no global cut there
+      last_error_ = "cpslab.allpair.gpu.topPairs ignored: a term-sharded worker has no global top-K (apss_set_top_pairs: plain handles only)";
+      conf_.topPairs = 0;
+    }
     return;
   }
   if (conf.devices.size() == 1) c.device_id = conf.devices[0];
@@ -252,6 +256,12 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
   }
   if (conf.topK != 0 && apss_set_top_k(h_, conf.topK) != APSS_OK) {
     const std::string msg = std::string("apss_set_top_k: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
+  if (conf.topPairs != 0 && apss_set_top_pairs(h_, conf.topPairs) != APSS_OK) {
+    const std::string msg = std::string("apss_set_top_pairs: ") + apss_last_error(h_);
     apss_destroy(h_);
     h_ = nullptr;
     throw std::runtime_error(msg);

@@ -109,6 +109,10 @@ struct Config {
   // slots until more than the fraction f of the stored vectors is removed; the next IndexData then compacts the store first
   // (apss_set_auto_compact).  Groups have no removal
   double autoCompact = 0.0;
+  // cpslab.allpair.gpu.topPairs: 0 (default) = off; K in 1 .. 2^20 = a reply holds the K best pairs of its whole batch, by (score
+  // descending, query id, candidate id ascending) -- apss_set_top_pairs, the global cut behind topK's per-query one.  A bad value
+  // fails construction, as a refused topK does; a term-sharded worker has no such cut: reported through lastError(), it runs with 0
+  long topPairs = 0;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

@@ -72,6 +72,14 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     else if (grouped) NativeApss.createGroup(vectorDim, similarityThreshold, indexThreshold, flags, devices, headTerms, groupFlags, topK)
     else NativeApss.create(vectorDim, similarityThreshold, indexThreshold, flags, devices(0), topKTileCut, headTerms, topKWindowPairs, topK)
   require(handle != 0L, if (grouped) NativeApss.groupLastError(0L) else NativeApss.lastError(0L))
+  // cpslab.allpair.gpu.topPairs = K (default 0: off; one GPU only): a reply holds the K best pairs of its whole batch, by (score
+  // descending, query id, candidate id ascending) -- apss_set_top_pairs, behind topK's per-query cut when both are set.  A value
+  // the library refuses fails the construction; with several GPUs the worker says so and runs with 0
+  private val topPairs = if (conf.hasPath("cpslab.allpair.gpu.topPairs")) conf.getLong("cpslab.allpair.gpu.topPairs") else 0L
+  if (grouped && topPairs != 0L)
+    System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.topPairs needs one GPU (cpslab.allpair.gpu.devices with one entry); running with 0")
+  if (!grouped && topPairs != 0L)
+    require(NativeApss.setTopPairs(handle, topPairs) == 0, NativeApss.lastError(handle))
   // cpslab.allpair.gpu.autoCompact = f (default 0: off; one GPU only): vectors withdrawn with NativeApss.remove keep their slots
   // until more than the fraction f of the stored vectors is removed; the next IndexData then compacts the store first
   // (apss_set_auto_compact).  The reference has no removal: it stops indexing after expDuration instead (below)

@@ -17,6 +17,13 @@ object NativeApss {
     * that can be among a query's topK before it writes them (apss_set_top_k_tile_cut): the same reply, a shorter list to cut */
   @native def create(dim: Int, theta: Double, indexThreshold: Double, flags: Int, device: Int, topKTileCut: Int,
                      headTerms: Int, topKWindowPairs: Long, topK: Int): Long
+  val TOP_PAIRS_MAX = 1 << 20
+  /** the global top-K (include/apss.h, apss_set_top_pairs; one handle only, a group has none): 0 = off; 1 .. TOP_PAIRS_MAX = every
+    * later reply holds the `pairs` best pairs of its whole batch, by (score descending, query id, candidate id ascending), in
+    * that order -- behind topK's per-query cut when both are set.  Travels through `submit` (mode 7 of apss_jni.c): no further
+    * native entry point.  Returns 0 or a negative status (lastError(h) says why) */
+  def setTopPairs(h: Long, pairs: Long): Int =
+    submit(h, 7, Array(0L, 0L), new Array[Int](0), new Array[Double](0), Array(pairs)).toInt
   @native def destroy(h: Long): Unit
   @native def lastError(h: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

@@ -133,6 +133,8 @@ static int32_t handle_submit(void *t, int mode, int64_t n, const int64_t *rp, co
   /* ... and so does the query of stored vectors by id (NativeApss.queryStored): mode 6 = apss_query_stored of the n ids (the CSR
    * is n empty rows); the result triples are fetched as after any query */
   if (mode == 6) return apss_query_stored((apss_handle *)t, n, id, NULL, n_res);
+  /* ... and the global top-K setting (NativeApss.setTopPairs): mode 7 = apss_set_top_pairs of ids(0) (the CSR is one empty row) */
+  if (mode == 7) return apss_set_top_pairs((apss_handle *)t, n == 1 ? id[0] : -1);
   return apss_insert_and_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
 }
 

@@ -463,6 +463,65 @@ int32_t apss_query_stored(apss_handle *h, int64_t n, const int64_t *ext_ids, int
 int32_t apss_query_stored_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int64_t *n_rows, int64_t *n_results);
 int32_t apss_stored_query_get(apss_handle *h, apss_stored_query_info *out);
 
+/* ---- global top-K: a call's K best pairs, selected on the device ----
+ * BASELINE.md's parity rule calls "top-k" the first k of the result set sorted by (-score, qId, cId): a cut over the WHOLE call,
+ * where apss_set_top_k cuts every query row's own list.  Plain handles only.
+ *
+ * The setting.
+ *  - k_pairs = 0 (the default): off.  A call launches nothing new, reads nothing new and allocates nothing.
+ *  - k_pairs in 1 .. APSS_TOP_PAIRS_MAX: every query-type call made afterwards ends with the cut: apss_query[_dev],
+ *    apss_insert_and_query[_dev], apss_self_join and apss_query_stored[_dev].
+ *  - It may change at any time, takes effect at the next query-type call, leaves the last call's results alone and survives
+ *    apss_clear, exactly like apss_set_top_k.
+ * The order is total.  Ascending rank means:
+ *  1. fp32 score descending, as the device reports it.  -0.0f counts as +0.0f and is reported as +0.0f (topk_key).
+ *  2. Query external id ascending (signed int64).
+ *  3. Candidate external id ascending.
+ *  4. Query row within the batch ascending (two batch rows may carry one id).
+ *  5. Candidate slot ascending.
+ * The answer.
+ *  - The final list is the first min(K, n) pairs of the call's final list (n pairs) in that order, stored in rank order.
+ *  - Everything that reads the results sees it: n_results, apss_result_count, apss_fetch_results, apss_results_dev,
+ *    apss_results_copy_dev, apss_stats.result_pairs.
+ *  - With n <= K nothing is dropped, but the list is still put into rank order.
+ *  - Score bits are unchanged.
+ * Where the cut runs.  It is the last stage of the call:
+ *  - after the join;
+ *  - after k_rm_drop: a row marked removed never takes a place among the K;
+ *  - after the per-query cut if k > 0: the K best are chosen among the kept per-query lists, and the global rank order
+ *    replaces "grouped by query";
+ *  - in a windowed call (apss_set_top_k_window) once, after the windows' lists are concatenated.
+ *  - apss_topk_info, apss_topk_window_info, apss_topk_tile_cut_info and apss_removal_info keep reporting their own stages;
+ *    apss_top_pairs_info.pairs_in is what they handed over.
+ *  - The symmetric whole-store join is untouched: both directions of a pair are two pairs of the list.
+ * Errors.
+ *  - APSS_E_INVALID: NULL handle, k_pairs < 0 or > APSS_TOP_PAIRS_MAX.
+ *  - APSS_E_UNSUPPORTED ("term shard"): k_pairs > 0 on a term shard.  Its candidates carry partial scores.
+ *  - APSS_E_UNSUPPORTED from the query-type call: a final list of 2^32 pairs or more (the stage names a pair by 32 bits).
+ *  - A failure inside the stage leaves the results invalid (APSS_E_STATE from the result calls).
+ *  - apss_group has no such call: a group's final list lies behind its exchange, and this stage runs on one handle's stream.
+ *
+ * The stage reads the list where it lies (csrc/apss_top_pairs.hpp): a radix select over the 32-bit score key (k_tp_hist,
+ * k_tp_pick; no host read between its passes), one collecting pass (k_tp_collect), a radix select down the ids for the pairs that
+ * tie the K-th score -- one 32-bit index per tied pair is all it keeps of them, and a store of duplicates ties them all --
+ * (k_tp_tie_hist, k_tp_tie_collect), then stable rocprim sorts over the min(K, n) kept pairs (k_tp_keys, k_tp_write).  It waits
+ * for the handle's stream twice. */
+#define APSS_TOP_PAIRS_MAX (1 << 20)
+typedef struct apss_top_pairs_info {
+  int32_t struct_size;   /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t launches;      /* k_tp_* launches of the last query-type call (rocprim sorts not counted; 0: nothing ran) */
+  int64_t k_pairs;       /* the setting the last call ran with (0: off) */
+  int64_t pairs_in;      /* length of the call's final list before this cut */
+  int64_t kept;          /* min(k_pairs, pairs_in) */
+  int64_t above;         /* pairs whose score key is strictly above the K-th pair's (0 when nothing was cut) */
+  int64_t tied;          /* pairs of the list that share the K-th pair's score key (0 when nothing was cut) */
+  int64_t tied_kept;     /* kept - above (0 when nothing was cut) */
+  double kth_score;      /* the K-th pair's fp32 score (0 when nothing was cut) */
+  double select_ms;      /* device time of the whole stage, HIP events */
+} apss_top_pairs_info;   /* 72 bytes */
+int32_t apss_set_top_pairs(apss_handle *h, int64_t k_pairs);
+int32_t apss_top_pairs_get(apss_handle *h, apss_top_pairs_info *out);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
