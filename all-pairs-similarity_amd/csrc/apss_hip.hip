@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +20,7 @@
 #include "apss_kernels.hpp"
 #include "apss_head.hpp"
 #include "apss_even.hpp"
+#include "apss_stage.hpp"
 #include "apss_topk.hpp"
 #include "apss_window.hpp"
 #include "apss_remove.hpp"
@@ -62,7 +64,7 @@ struct PairList {
     x.in_c = c.p;
     x.in_s = s.p;
   }
-  // the out_* fields of a kernel's arguments, or of the handle (where the last call's results live)
+  // the out_* fields of a kernel's arguments (the handle's own are adopt_list's to write)
   template <class A>
   void as_out(A &x) const {
     x.out_q = q.p;
@@ -189,6 +191,23 @@ DebugCfg parse_debug_env() {
   return d;
 }
 
+constexpr size_t kPinBytes = 256 << 10;   // pinned staging of a small batch / a small answer ...
+constexpr size_t kPinScalars = 1024;      // ... + this much behind it for the small device-to-host reads:
+
+// one member per readback, each in cache lines of its own (a read lands while the host works on another)
+struct PinScalars {
+  alignas(128) unsigned int ingest_flags[4];               // the flag words of an ingest kernel / of k_qs_gather
+  alignas(128) unsigned long long chain_ctr[kCtrCount];    // the chained exact pass's counters
+  alignas(128) unsigned long long attempt_ctr[kCtrCount];  // the filter's counters of one attempt
+  alignas(512) unsigned long long removal_kept;            // pairs k_rm_drop kept
+  alignas(128) int64_t stored_back[4];                     // apss_query_stored: the two scan totals, the two id counters
+  alignas(128) unsigned long long top_pairs[kTpWords];     // the global top-K's state words
+};
+static_assert(sizeof(PinScalars) <= kPinScalars, "the scalar slots end inside the pinned reservation");
+static_assert(offsetof(PinScalars, chain_ctr) == 128 && offsetof(PinScalars, attempt_ctr) == 256 && offsetof(PinScalars, removal_kept) == 512 &&
+                  offsetof(PinScalars, stored_back) == 640 && offsetof(PinScalars, top_pairs) == 768,
+              "every readback keeps the cache lines it had");
+
 }  // namespace
 
 struct apss_handle {
@@ -295,7 +314,9 @@ struct apss_handle {
   DevBuf<unsigned int> flagword;
   // small messages (single vectors, batches of a few dozen: the reference's LoadGenerator sends ONE vector per message): the
   // batch crosses PCIe as one packed copy out of pinned memory and the answer comes back the same way
-  char *pin = nullptr;             // pinned host staging, kPinBytes
+  char *pin = nullptr;             // pinned host staging, kPinBytes + kPinScalars
+  PinScalars own_scalars{};        // (without pinned memory: pageable copies of the scalar slots)
+  PinScalars *scalars = &own_scalars;  // where the small device-to-host reads land: behind `pin`, or own_scalars
   DevBuf<char> pack;               // its device twin
   const int64_t *up_rowptr = nullptr, *up_ext = nullptr;  // where upload() left the batch (the in_* arrays, or views into `pack`)
   const int32_t *up_idx = nullptr;
@@ -368,7 +389,7 @@ struct apss_handle {
   DevBuf<char> rm_tmp;
   DevBuf<unsigned long long> rm_ctr;  // [1] rows newly marked / pairs kept
   PairList rm_out;
-  hipEvent_t rm_ev0 = nullptr, rm_ev1 = nullptr;  // (created by the first apss_remove)
+  hipEvent_t rm_ev0 = nullptr, rm_ev1 = nullptr;  // (created where they are first recorded: begin_timed / end_timed_read)
   double auto_compact = 0.0;
   apss_removal_info ri{};
   // stored rows as a query batch (apss_query_stored.hpp): the found bytes of the sorted id list (which lives in rm_sorted), the id
@@ -376,7 +397,7 @@ struct apss_handle {
   DevBuf<uint8_t> qs_found;
   DevBuf<unsigned long long> qs_ctr;  // [2] distinct ids / distinct ids that selected nothing
   DevBuf<int32_t> qs_slots;
-  hipEvent_t qs_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (created by the first apss_query_stored)
+  hipEvent_t qs_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (created where they are first recorded)
   apss_stored_query_info qsi{};
   // global top-K (apss_top_pairs.hpp): the setting, the stage's buffers, what the last query-type call did
   int64_t top_pairs = 0;
@@ -465,8 +486,6 @@ int32_t enter(apss_handle *h) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-constexpr size_t kPinBytes = 256 << 10;   // pinned staging of a small batch / a small answer ...
-constexpr size_t kPinScalars = 1024;      // ... + this much behind it for the small device-to-host reads (flags, counters)
 
 // ---- ingest: validate (+ optional normalise / admission / value prune / term-range filter) and append ----
 // Source arrays are device pointers (batch-relative rowptr).  Destination: the store (to_store) or the query
@@ -585,9 +604,8 @@ int32_t ingest_plain(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_ro
   // (the workgroups loop over their rows: few workgroups = few same-address atomics on the batch summaries)
   hipLaunchKernelGGL(k_ingest_plain, dim3((unsigned)std::min<int64_t>(blocks, 4096)), dim3(threads), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  unsigned int flags_stack[4] = {0, 0, 0, 0};
-  unsigned int *flags_host = h->pin ? reinterpret_cast<unsigned int *>(h->pin + kPinBytes) : flags_stack;
-  HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));  // (pinned or stack)
+  unsigned int *flags_host = h->scalars->ingest_flags;
+  HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
   if (sample) HIPCHK(h, hipMemcpyAsync(h->df_host.data(), h->df.p, (size_t)dim * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (h->dbgcfg.diag)
@@ -660,9 +678,8 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
   // destination
   int64_t dst_row0 = to_store ? h->n_rows : 0, dst_nnz0 = to_store ? h->nnz : 0;
   int64_t kept_rows = n, kept_nnz = nnz;
-  unsigned int flags_stack[4] = {0, 0, 0, 0};
   // (read back into pinned memory when the handle has it: a copy into pageable memory is staged by the runtime)
-  unsigned int *flags_host = h->pin ? reinterpret_cast<unsigned int *>(h->pin + kPinBytes) : flags_stack;
+  unsigned int *flags_host = h->scalars->ingest_flags;
   if (transform) {
     APSS_TRY(ensure(h, h->s_rowdst, (size_t)n + 1));
     APSS_TRY(ensure(h, h->s_nnzdst, (size_t)n + 1));
@@ -672,7 +689,7 @@ int32_t ingest(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, 
     HIPCHK(h, hipMemcpyAsync(&kept_rows, h->s_rowdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(&kept_nnz, h->s_nnzdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   }
-  HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));  // (pinned or stack)
+  HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   APSS_TRY(take_ingest_flags(h, flags_host, to_store));
 
@@ -1275,6 +1292,49 @@ struct QueryRows {
   const float *val;
   const int64_t *ext;
 };
+
+// ... as a query-type call hands it down: slot_first: slot of row 0 when the batch is rows of the store, else -1; max_nnz,
+// max_norm2: the longest row and the largest squared row norm (of the whole batch, whatever rows of it are probed); nnz_end: the
+// entries behind the offsets
+struct QueryBatch : QueryRows {
+  int64_t slot_first, max_nnz;
+  float max_norm2;
+  int64_t nnz_end;
+  // rows [r0, r1) as a batch of their own (a window): the offsets stay absolute
+  QueryBatch rows(int64_t r0, int64_t r1) const {
+    return QueryBatch{{r1 - r0, rowptr + r0, idx, val, ext + r0}, slot_first < 0 ? -1 : slot_first + r0, max_nnz, max_norm2, nnz_end};
+  }
+};
+
+// the last query-type call's results and batch are gone (they may point into arrays that are about to be rewritten or
+// reallocated): apss_fetch_results / apss_partial_scores_dev answer APSS_E_STATE until the next query-type call
+void forget_last_call(apss_handle *h) {
+  h->n_res = -1;
+  h->res_q_ext = nullptr;
+  h->last_q_rowptr = nullptr;
+  h->last_q_idx = nullptr;
+  h->last_q_val = nullptr;
+  h->last_nq = 0;
+}
+
+// the batch the handle's results speak of (apss_fetch_results looks its ids up, apss_partial_scores_dev reads its rows)
+void name_last_batch(apss_handle *h, const QueryRows &q) {
+  h->res_q_ext = q.ext;
+  h->last_q_rowptr = q.rowptr;
+  h->last_q_idx = q.idx;
+  h->last_q_val = q.val;
+  h->last_nq = q.nq;
+}
+
+// (q, c, s)[0, n) is the call's list from here on: the ONE writer of where the results live, how many there are, and the statistic
+void adopt_list(apss_handle *h, const int32_t *q, const int32_t *c, const float *s, int64_t n) {
+  h->out_q = q;
+  h->out_c = c;
+  h->out_s = s;
+  h->n_res = n;
+  h->st.result_pairs = n;
+}
+inline void adopt_list(apss_handle *h, const PairList &l, int64_t n) { adopt_list(h, l.q.p, l.c.p, l.s.p, n); }
 
 // k_rescore's arguments: the pairs (cand_q, cand_c) of query rows and store slots are re-scored from the fp32 store, and those
 // that reach theta go to h->fin, counted at out_count.  n_pairs_dev (chained launch): the pair count is read on the device
@@ -2102,8 +2162,7 @@ int32_t exact_pass(apss_handle *h, bool hybrid, double theta, const QueryRows &q
     h->st.device_posting_visits += (int64_t)tc[kCtrVisits];
     h->st.candidate_pairs += (int64_t)tc[kCtrCands];
   }
-  h->fin.as_out(*h);
-  h->st.result_pairs = h->n_res;
+  adopt_list(h, h->fin, h->n_res);
   return APSS_OK;
 }
 
@@ -2142,13 +2201,9 @@ struct ProbePath {
   const float *q_sub;
 };
 
-// one pass's state: probe_inner's arguments (q_slot_first: slot of query row 0 when the batch is rows of the store, else -1),
-// then what each stage settles for the ones behind it
+// one pass's state: probe_inner's batch, then what each stage settles for the ones behind it
 struct Probe {
-  QueryRows q;
-  int64_t q_slot_first, q_max_nnz;
-  float q_max_norm2;
-  int64_t q_nnz_end;
+  QueryBatch q;
   StagedRows s;
   ProbePath p;
   ProbeArgs a;
@@ -2162,19 +2217,14 @@ struct Probe {
 // what one attempt's launches count and leave in the counters: read back in one go
 struct AttemptCounts {
   int64_t n_launches = 0, thin_launches = 0;
-  unsigned long long cc_stack[kCtrCount] = {}, c_stack[kCtrCount];
-  unsigned long long *c, *cc;  // the filter's counters; the chained exact pass's
+  unsigned long long *c, *cc;  // the filter's counters; the chained exact pass's (the handle's scalar slots)
   unsigned long long sparse_results = 0, head_c[4] = {0, 0, 0, 0};
 };
 
 inline apss_handle::IndexSet &probe_index(apss_handle *h, const ProbePath &p) { return p.coarse_path ? h->cx : h->ex; }
 
-int32_t reset_call(apss_handle *h, const Probe &pr, int64_t *n_results) {
-  h->res_q_ext = pr.q.ext;
-  h->last_q_rowptr = pr.q.rowptr;
-  h->last_q_idx = pr.q.idx;
-  h->last_q_val = pr.q.val;
-  h->last_nq = pr.q.nq;
+int32_t reset_call(apss_handle *h, const Probe &pr) {
+  name_last_batch(h, pr.q);
   h->n_res = 0;
   h->st.posting_visits = h->st.candidate_pairs = h->st.result_pairs = 0;
   h->st.device_posting_visits = 0;
@@ -2194,7 +2244,6 @@ int32_t reset_call(apss_handle *h, const Probe &pr, int64_t *n_results) {
   h->st.head_terms = h->head_k ? (int64_t)h->head_terms.size() : 0;
   h->st.head_columns = (uint32_t)h->head_k;
   h->st.head_int8 = h->head_k && h->head_i8 ? 1 : 0;
-  if (n_results) *n_results = 0;
   APSS_TRY(ensure(h, h->counters, kCtrCount));
   h->st.filter_survivors = 0;
   h->st.rescore_ms = 0;
@@ -2206,12 +2255,12 @@ int32_t reset_call(apss_handle *h, const Probe &pr, int64_t *n_results) {
 // Exact rescoring, the waiting rows' direct scoring and apss_partial_scores_dev keep reading the whole rows.
 int32_t stage_rows(apss_handle *h, Probe &pr) {
   StagedRows &s = pr.s;
-  s = StagedRows{pr.q.rowptr, pr.q.idx, pr.q.val, pr.q_max_nnz, pr.q_nnz_end, 0, 0};
+  s = StagedRows{pr.q.rowptr, pr.q.idx, pr.q.val, pr.q.max_nnz, pr.q.nnz_end, 0, 0};
   if (h->head_k > 0) {
-    const bool stored = pr.q_slot_first >= 0 && pr.q_slot_first < h->idx_rows;
+    const bool stored = pr.q.slot_first >= 0 && pr.q.slot_first < h->idx_rows;
     if (!stored) APSS_TRY(build_tail_view(h, h->qtv, pr.q.rowptr, pr.q.idx, pr.q.val, 0, pr.q.nq, 0, false));
     const apss_handle::TailView &v = stored ? h->tv : h->qtv;
-    s.rowptr = stored ? v.rowptr.p + pr.q_slot_first : v.rowptr.p;
+    s.rowptr = stored ? v.rowptr.p + pr.q.slot_first : v.rowptr.p;
     s.idx = v.idx.p;
     s.val = v.val.p;
     s.max_nnz = v.max_nnz;
@@ -2245,12 +2294,12 @@ int32_t choose_path(apss_handle *h, Probe &pr) {
   ProbePath &p = pr.p;
   const double theta = p.theta = h->cfg.theta;
   if (!(theta > 0.0)) p.mode = 2;
-  else if (!h->nonneg || (pr.q_slot_first < 0 && !h->q_nonneg) || (h->cfg.flags & APSS_FLAG_FORCE_SCAN)) p.mode = 1;
+  else if (!h->nonneg || (pr.q.slot_first < 0 && !h->q_nonneg) || (h->cfg.flags & APSS_FLAG_FORCE_SCAN)) p.mode = 1;
   else p.mode = 0;
 
   // every partial score must fit the fixed-point accumulators: by Cauchy-Schwarz a partial sum of non-negative
   // products is at most |q| * |c| <= the product of the largest row norms
-  const double bound = p.bound = std::sqrt((double)pr.q_max_norm2) * std::sqrt((double)h->store_max_norm2) * 1.0001 + 1e-6;
+  const double bound = p.bound = std::sqrt((double)pr.q.max_norm2) * std::sqrt((double)h->store_max_norm2) * 1.0001 + 1e-6;
   p.fx_scale = bound < 3.9 ? 1073741824.0 : (bound < 15.6 ? 268435456.0 : 0.0);
   p.forced_general = (h->cfg.flags & APSS_FLAG_FORCE_GENERAL) || h->dbgcfg.force_general;
 
@@ -2298,7 +2347,7 @@ int32_t choose_path(apss_handle *h, Probe &pr) {
     return kProbeAgain;
   }
   // a stored batch that still waits in the tail is not in the index: for the join over the index it is an outside batch
-  p.q_slot_base = pr.q_slot_first >= 0 && pr.q_slot_first < h->idx_rows ? pr.q_slot_first : -1;
+  p.q_slot_base = pr.q.slot_first >= 0 && pr.q.slot_first < h->idx_rows ? pr.q.slot_first : -1;
   if (hybrid_wanted && !(p.coarse_path && p.mode == 0 && (h->head_i8 || p.head_thr >= 0.5 * theta))) {  // (the INT8 rows carry no rounding bound)
     // this call cannot take the hybrid path (signed or very long queries, norms out of range ...): the dense block's
     // terms go back into the inverted index, for good, and the call runs as on a handle without a block
@@ -2399,7 +2448,7 @@ int32_t choose_exact_kernel(apss_handle *h, Probe &pr) {
   pr.xk.longcap = pr.xk.variant == 'A' ? 256 : 128;
   pr.xk.survcap = pr.xk.variant == 'A' ? 1024 : 512;
   // chunk descriptors pack (first posting * 8 + count - 1) into 32 bits: a tile's postings must number < 2^28
-  pr.xk.wave = !pr.p.coarse_path && pr.p.mode == 0 && pr.p.fx_scale > 0 && pr.q_max_nnz <= wave_block && !pr.p.forced_general &&
+  pr.xk.wave = !pr.p.coarse_path && pr.p.mode == 0 && pr.p.fx_scale > 0 && pr.q.max_nnz <= wave_block && !pr.p.forced_general &&
                h->store_max_nnz * (int64_t)h->ex.cb + (int64_t)kSegAlign * h->cfg.dim < (1LL << 28);
   // ---- path 3: general kernel (k_probe): signed fixed point when the norms are bounded, else fp32 atomics ----
   pr.xk.fx = !pr.p.coarse_path && !pr.xk.wave && pr.p.fx_scale > 0;
@@ -2825,37 +2874,31 @@ int32_t grow_candidates(apss_handle *h, const Probe &pr, const AttemptCounts &n)
 }
 
 // the attempt's list held everything: the call's final list and its last statistics
-int32_t finish_call(apss_handle *h, const Probe &pr, const AttemptCounts &n, int64_t *n_results) {
+int32_t finish_call(apss_handle *h, const Probe &pr, const AttemptCounts &n) {
   if (pr.chain) {  // the exact pass has run already: its list is final
     h->st.filter_survivors = (int64_t)n.c[kCtrResults];
-    h->n_res = (int64_t)n.cc[kCtrResults];
     h->st.posting_visits += (int64_t)n.cc[kCtrVisits];
     h->st.device_posting_visits += (int64_t)n.cc[kCtrVisits];
     h->st.candidate_pairs += (int64_t)n.cc[kCtrCands];
-    h->st.result_pairs = h->n_res;
-    h->fin.as_out(*h);
-    if (n_results) *n_results = h->n_res;
+    adopt_list(h, h->fin, (int64_t)n.cc[kCtrResults]);
     return APSS_OK;
   }
-  h->n_res = (int64_t)n.c[kCtrResults];
+  adopt_list(h, h->res, (int64_t)n.c[kCtrResults]);
   if (pr.xk.cut) {  // (kCtrPre, kCtrSnap: the uncut total and the rounds cut -- words k_probe<2> leaves alone otherwise)
     h->cut_ran = true;
     h->cut_uncut = (int64_t)n.c[kCtrPre];
     h->cut_rounds = (int64_t)n.c[kCtrSnap];
   }
-  h->res.as_out(*h);
   if (pr.p.coarse_path && h->sharded) h->st.filter_survivors = h->n_res;  // a shard's survivors are its candidates (phase 2 scores them)
   if (pr.p.coarse_path && !h->sharded) APSS_TRY(exact_pass(h, pr.p.hybrid, pr.p.theta, pr.q, pr.p.tail_n));
-  if (n_results) *n_results = h->n_res;
   return APSS_OK;
 }
 
 // One attempt.  APSS_OK: the call is finished; kAttemptAgain: the list was grown; kProbeAgain: the 8-bit filter was dropped
-int32_t run_attempt(apss_handle *h, Probe &pr, int64_t *n_results) {
+int32_t run_attempt(apss_handle *h, Probe &pr) {
   AttemptCounts n;
-  // (the small reads land in the pinned staging's scalar slots where there is one)
-  n.cc = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 128) : n.cc_stack;
-  n.c = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 256) : n.c_stack;
+  n.cc = h->scalars->chain_ctr;
+  n.c = h->scalars->attempt_ctr;
   APSS_TRY(begin_attempt(h, pr));
   name_probe_kernel(h, pr);
   APSS_TRY(launch_tile_groups(h, pr, n));
@@ -2872,14 +2915,14 @@ int32_t run_attempt(apss_handle *h, Probe &pr, int64_t *n_results) {
   // accumulators, for good, and run the call again.
   if (pr.cxv.acc8 && (int64_t)n.c[kCtrResults] > std::max<int64_t>(64 * pr.q.nq, 4000000)) return pr.cxv.planes ? drop_planes(h) : drop_acc8(h, pr.p.shard_rule);
   if (std::max(n.c[kCtrResults], n.c[kCtrOver]) > pr.a.res_cap) return grow_candidates(h, pr, n);
-  return finish_call(h, pr, n, n_results);
+  return finish_call(h, pr, n);
 }
 
 // One pass of the call.  kProbeAgain: a downgrade was latched and the index rebuilt (no room for 8-bit sums, waiting rows folded
 // into the index, dense head blocked, 8-bit filter unselective) -- the call runs again
-int32_t probe_pass(apss_handle *h, Probe &pr, int64_t *n_results) {
-  APSS_TRY(reset_call(h, pr, n_results));
-  if (pr.q.nq == 0 || h->n_rows == 0 || pr.q_nnz_end <= 0 || h->nnz == 0) return APSS_OK;  // nothing can share a term
+int32_t probe_pass(apss_handle *h, Probe &pr) {
+  APSS_TRY(reset_call(h, pr));
+  if (pr.q.nq == 0 || h->n_rows == 0 || pr.q.nnz_end <= 0 || h->nnz == 0) return APSS_OK;  // nothing can share a term
   if (pr.q.nq > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "query batch too large");
   APSS_TRY(stage_rows(h, pr));
   APSS_TRY(choose_path(h, pr));
@@ -2893,70 +2936,72 @@ int32_t probe_pass(apss_handle *h, Probe &pr, int64_t *n_results) {
   APSS_TRY(size_launches(h, pr));
   APSS_TRY(prepare_work_lists(h, pr));
   for (int attempt = 0; attempt < 3; ++attempt) {
-    const int32_t rc = run_attempt(h, pr, n_results);
+    const int32_t rc = run_attempt(h, pr);
     if (rc != kAttemptAgain) return rc;
   }
   return fail(h, APSS_E_STATE, "result buffer kept overflowing");
 }
 
 // Every repeat follows a one-way latch (no_acc8, head_blocked, idx_rows == n_rows): at most three of them
-int32_t probe_inner(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-                    int64_t q_nnz_end, int64_t *n_results) {
-  Probe pr{QueryRows{nq, q_rowptr, q_idx, q_val, q_ext}, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end};
+// (*n_results, where the caller wants it, is zero from here on: what an error return leaves; probe writes the call's count)
+int32_t probe_inner(apss_handle *h, const QueryBatch &batch, int64_t *n_results) {
+  if (n_results) *n_results = 0;
+  Probe pr{batch};
   for (int pass = 0; pass < 4; ++pass) {
-    const int32_t rc = probe_pass(h, pr, n_results);
+    const int32_t rc = probe_pass(h, pr);
     if (rc != kProbeAgain) return rc;
   }
   return fail(h, APSS_E_STATE, "the call kept downgrading the index");
 }
 
-// The cut of one final list (the call's, or a window's): h->out_* / h->n_res become the kept list, *info says what was done.
+// ---- the list stages behind the join (apss_stage.hpp): each takes the call's list where adopt_list left it and adopts its own ----
+// One stage that owns its device memory (`mem`) and reports a hipError_t -- or, through *bad, that its own counts disagree: the
+// handle's reservation follows the stage's, and a failure takes the call's list with it
+template <class F>
+int32_t run_stage(apss_handle *h, const char *what, StageMem &mem, F fn) {
+  const size_t before = mem.bytes;
+  const char *bad = nullptr;
+  const hipError_t e = fn(&bad);
+  h->bytes_reserved += mem.bytes - before;
+  if (e == hipSuccess) return APSS_OK;
+  h->n_res = -1;
+  h->err = std::string(what) + ": " + (bad ? bad : hipGetErrorString(e));
+  return bad ? APSS_E_STATE : e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
+}
+
+// The cut of one final list (the call's, or a window's): the kept list is adopted, *info says what was done.
 int32_t cut_final_list(apss_handle *h, int64_t nq, apss_topk_info *info) {
-  const size_t before = h->topk.bytes;
   // (a probe that cut its rounds: the list is what it emitted, the rows' uncut counts say what the call found)
-  const hipError_t e = topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info,
-                                h->cut_ran ? h->row_pairs.p : nullptr, h->cut_uncut);
-  h->bytes_reserved += h->topk.bytes - before;
-  if (e != hipSuccess) {
-    h->n_res = -1;
-    h->err = std::string("per-query top-k: ") + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
-  }
-  if (h->n_res > 0) {
-    h->out_q = h->topk.out_q;
-    h->out_c = h->topk.out_c;
-    h->out_s = h->topk.out_s;
-    h->n_res = info->kept;
-  }
+  APSS_TRY(run_stage(h, "per-query top-k", h->topk.mem, [&](const char **) {
+    return topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info,
+                    h->cut_ran ? h->row_pairs.p : nullptr, h->cut_uncut);
+  }));
+  if (h->n_res > 0) adopt_list(h, h->topk.out_q, h->topk.out_c, h->topk.out_s, info->kept);
   return APSS_OK;
 }
 
 // Windows of a query-type call (apss_window.hpp): b(q) on the device, the greedy cuts on the host.  Fills h->win_cuts and the
 // planning fields of h->tw; b (and, with `bits`, the rows' non-empty bits behind it) is left in `hb`.
-int32_t plan_windows(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const int64_t *sv_rowptr,
-                     std::vector<int32_t> &hb) {
+int32_t plan_windows(apss_handle *h, const QueryBatch &batch, const int64_t *sv_rowptr, std::vector<int32_t> &hb) {
   const int32_t dim = h->cfg.dim;
+  const int64_t nq = batch.nq;
   APSS_TRY(ensure(h, h->win_df, (size_t)dim));
   APSS_TRY(ensure(h, h->win_b, (size_t)(2 * nq)));
   HIPCHK(h, hipMemsetAsync(h->win_df.p, 0, (size_t)dim * sizeof(unsigned int), h->stream));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, begin_timed(h->stream, h->ev0));
   if (h->nnz >= (1LL << 40)) return fail(h, APSS_E_UNSUPPORTED, "windowed top-k: more than 2^40 stored entries");  // (k_win_df's grid)
   if (h->nnz > 0) {
     hipLaunchKernelGGL(k_win_df, dim3((unsigned)ceil_div(h->nnz, kTopkBlock)), dim3(kTopkThreads), 0, h->stream, (const int32_t *)h->idx.p, h->nnz, dim,
                        h->win_df.p);
     ++h->tw.plan_launches;
   }
-  hipLaunchKernelGGL(k_win_bound, dim3((unsigned)ceil_div(nq * kWinWave, kWinThreads)), dim3(kWinThreads), 0, h->stream, q_rowptr, q_idx, nq,
+  hipLaunchKernelGGL(k_win_bound, dim3((unsigned)ceil_div(nq * kWinWave, kWinThreads)), dim3(kWinThreads), 0, h->stream, batch.rowptr, batch.idx, nq,
                      (const unsigned int *)h->win_df.p, dim, h->n_rows, sv_rowptr, h->win_b.p, h->win_b.p + nq);
   ++h->tw.plan_launches;
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   hb.resize((size_t)(sv_rowptr ? 2 * nq : nq));
-  HIPCHK(h, hipMemcpyAsync(hb.data(), h->win_b.p, hb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  HIPCHK(h, end_timed_read(h->stream, h->ev0, h->ev1, {{hb.data(), h->win_b.p, hb.size() * sizeof(int32_t)}}, &ms));
   h->tw.plan_ms = ms;
   // a window: the longest run of rows from its start whose bounds sum to <= max_pairs; a row over the budget is a window of one
   const int64_t budget = h->top_k_window;
@@ -3016,14 +3061,8 @@ int32_t rm_extend(apss_handle *h) {
 // makes a small store take their loops' later trips
 int64_t rm_grid_cap(const apss_handle *h, int64_t cap) { return h->dbgcfg.rm_grid > 0 ? h->dbgcfg.rm_grid : cap; }
 
-int32_t rm_events(apss_handle *h) {
-  if (!h->rm_ev0) HIPCHK(h, hipEventCreate(&h->rm_ev0));
-  if (!h->rm_ev1) HIPCHK(h, hipEventCreate(&h->rm_ev1));
-  return APSS_OK;
-}
-
-// The final list of a query-type call (or of one window) without the pairs that touch a marked row: h->out_* / h->n_res become
-// the filtered list.  Runs only while rows are marked; q_slot_first >= 0: the query rows are stored rows from that slot on.
+// The final list of a query-type call (or of one window) without the pairs that touch a marked row: the filtered list is
+// adopted.  Runs only while rows are marked; q_slot_first >= 0: the query rows are stored rows from that slot on.
 int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
   if (h->rm_marked <= 0 || h->n_res <= 0) return APSS_OK;
   APSS_TRY(rm_extend(h));
@@ -3040,32 +3079,35 @@ int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
   a.q_slot_first = q_slot_first;
   h->rm_out.as_out(a);
   a.kept = h->rm_ctr.p;
-  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
+  HIPCHK(h, begin_timed(h->stream, h->rm_ev0));
   const int64_t blocks = ceil_div(h->n_res, (int64_t)kRmThreads * kRmItems);
   hipLaunchKernelGGL(k_rm_drop, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 16384))), dim3(kRmThreads), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
-  unsigned long long kept_stack = 0;
-  unsigned long long *kept = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 512) : &kept_stack;
-  HIPCHK(h, hipMemcpyAsync(kept, h->rm_ctr.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  unsigned long long *kept = &h->scalars->removal_kept;
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  HIPCHK(h, end_timed_read(h->stream, h->rm_ev0, h->rm_ev1, {{kept, h->rm_ctr.p, sizeof(*kept)}}, &ms));
   if ((int64_t)*kept > h->n_res) return fail(h, APSS_E_STATE, "the removal filter kept more pairs than it was given");
   h->ri.pairs_dropped += h->n_res - (int64_t)*kept;
   h->ri.drop_ms += ms;
   ++h->ri.drop_launches;
-  h->rm_out.as_out(*h);
-  h->n_res = (int64_t)*kept;
+  adopt_list(h, h->rm_out, (int64_t)*kept);
   return APSS_OK;
 }
 
-// A query-type call: the join (probe_inner runs its pass again after a downgrade or a rebuild; what it leaves is the call's final
-// list), then, while rows are marked removed, ONE filter of that list (apss_remove.hpp), then, with apss_set_top_k, ONE pass of the per-query top-k over that list (apss_topk.hpp) -- or, with
-// apss_set_top_k_window, join and pass window by window over the query rows (apss_window.hpp), the kept lists concatenated.
-int32_t probe_lists(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-                    const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-                    int64_t q_nnz_end, int64_t *n_results) {
+// What the join of `batch` (the call's, or one window's) left, finished: while rows are marked removed, ONE filter of that list
+// (apss_remove.hpp); then, with apss_set_top_k, ONE pass of the per-query top-k over it (apss_topk.hpp), reported in *info.
+int32_t finish_list(apss_handle *h, const QueryBatch &batch, apss_topk_info *info) {
+  APSS_TRY(drop_removed(h, batch.slot_first));
+  info->pairs_over_theta = info->kept = h->n_res;
+  if (h->top_k <= 0 || h->sharded) return APSS_OK;
+  return cut_final_list(h, batch.nq, info);
+}
+
+// A query-type call's list: the join (probe_inner runs its pass again after a downgrade or a rebuild; what it leaves is the final
+// list of its rows) and finish_list -- once over the whole batch, or, with apss_set_top_k_window, window by window over the query
+// rows (apss_window.hpp), the kept lists concatenated.
+int32_t probe_lists(apss_handle *h, const QueryBatch &batch, int64_t *n_results) {
+  const int64_t nq = batch.nq;
   h->tk = apss_topk_info{};
   h->tw = apss_topk_window_info{};
   h->tw.max_pairs = h->top_k_window;
@@ -3089,27 +3131,17 @@ int32_t probe_lists(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
   };
   const bool windowed = h->top_k > 0 && h->top_k_window > 0 && !h->sharded && nq <= 0x7fffffffLL && nq * h->n_rows > h->top_k_window;
   if (!windowed) {
-    APSS_TRY(probe_inner(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
+    APSS_TRY(probe_inner(h, batch, n_results));
     note_cut();
-    if (h->rm_marked > 0) {
-      APSS_TRY(drop_removed(h, q_slot_first));
-      h->st.result_pairs = h->n_res;
-      if (n_results) *n_results = h->n_res;
-    }
-    h->tk.pairs_over_theta = h->tk.kept = h->n_res;
-    if (h->top_k <= 0 || h->sharded) return APSS_OK;
-    APSS_TRY(cut_final_list(h, nq, &h->tk));
-    h->st.result_pairs = h->n_res;
-    if (n_results) *n_results = h->n_res;
-    return APSS_OK;
+    return finish_list(h, batch, &h->tk);
   }
   // ---- the plan.  A stored batch of a handle with a dense-head block: the rows' tail view tells which of them the sparse
   // filter / the block see at all (the per-window self-touch corrections); a batch the view does not cover (it waits outside the
   // index) is corrected by its rows with any entry at all, should a window fold it in: candidate_pairs stays a lower bound
   h->n_res = -1;  // (the last call's list may live in buffers the windows reuse: gone from here on, also when the plan fails)
-  const bool bits = h->head_k > 0 && q_slot_first >= 0 && q_slot_first + nq <= h->tv.rows && h->tv.rowptr.p;
+  const bool bits = h->head_k > 0 && batch.slot_first >= 0 && batch.slot_first + nq <= h->tv.rows && h->tv.rowptr.p;
   std::vector<int32_t> hb;
-  APSS_TRY(plan_windows(h, nq, q_rowptr, q_idx, bits ? h->tv.rowptr.p + q_slot_first : nullptr, hb));
+  APSS_TRY(plan_windows(h, batch, bits ? h->tv.rowptr.p + batch.slot_first : nullptr, hb));
   const int64_t kept_max = [&] {
     int64_t s = 0;
     for (int64_t q = 0; q < nq; ++q) s += std::min<int64_t>(hb[(size_t)q], h->top_k);
@@ -3136,19 +3168,15 @@ int32_t probe_lists(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
       h->win_head_nonempty += (ne >> 1) & 1;
     }
     const int64_t reruns = h->probe_reruns;
-    rc = probe_inner(h, r1 - r0, q_rowptr + r0, q_idx, q_val, q_ext + r0, q_slot_first < 0 ? -1 : q_slot_first + r0, q_max_nnz,
-                     q_max_norm2, q_nnz_end, nullptr);
+    const QueryBatch window = batch.rows(r0, r1);
+    rc = probe_inner(h, window, nullptr);
     if (rc != APSS_OK) break;
     if (h->probe_reruns > reruns) ++h->tw.overflow_reruns;
     note_cut();
     h->tw.pairs_window_max = std::max(h->tw.pairs_window_max, h->n_res);
     for_summed_stats(sum, h->st, [](auto &s, const auto &v) { s += v; });
-    if (h->rm_marked > 0) {  // the window's list loses its removed rows before its cut
-      rc = drop_removed(h, q_slot_first < 0 ? -1 : q_slot_first + r0);
-      if (rc != APSS_OK) break;
-    }
     apss_topk_info one{};
-    rc = cut_final_list(h, r1 - r0, &one);
+    rc = finish_list(h, window, &one);  // (the window's list loses its removed rows before its cut)
     if (rc != APSS_OK) break;
     tk.pairs_over_theta += one.pairs_over_theta;
     tk.kept += one.kept;
@@ -3176,63 +3204,47 @@ int32_t probe_lists(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const i
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) rc = fail(h, APSS_E_DEVICE, std::string("windowed top-k: ") + hipGetErrorString(e));
   }
-  // the handle names the whole batch again, whatever the last window left
-  h->res_q_ext = q_ext;
-  h->last_q_rowptr = q_rowptr;
-  h->last_q_idx = q_idx;
-  h->last_q_val = q_val;
-  h->last_nq = nq;
+  name_last_batch(h, batch);  // (the handle names the whole batch again, whatever the last window left)
   if (rc != APSS_OK) {
     h->n_res = -1;
     return rc;
   }
   for_summed_stats(h->st, sum, [](auto &s, const auto &v) { s = v; });
   h->tk = tk;
-  h->win.as_out(*h);
-  h->n_res = n_out;
-  h->st.result_pairs = n_out;
-  if (n_results) *n_results = n_out;
+  adopt_list(h, h->win, n_out);
   return APSS_OK;
 }
 
-// The global cut of the call's final list (apss_top_pairs.hpp): h->out_* / h->n_res become its K best pairs in rank order.
-int32_t cut_top_pairs(apss_handle *h, int64_t nq, const int64_t *q_ext, int64_t *n_results) {
+// The global cut of the call's final list (apss_top_pairs.hpp): its K best pairs in rank order are adopted.
+int32_t cut_top_pairs(apss_handle *h, const QueryBatch &batch) {
   h->tpi.pairs_in = h->n_res;
   if (h->n_res <= 0) return APSS_OK;
   if (h->n_res > 0xffffffffLL) {
     h->n_res = -1;
     return fail(h, APSS_E_UNSUPPORTED, "global top-K: a final list of 2^32 pairs or more");
   }
-  unsigned long long words_stack[kTpWords];
-  unsigned long long *words = h->pin ? reinterpret_cast<unsigned long long *>(h->pin + kPinBytes + 768) : words_stack;
-  const size_t before = h->tp.bytes;
-  const char *bad = nullptr;
-  const hipError_t e = tp_run(h->tp, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, q_ext, nq, h->ext.p, h->n_rows, h->top_pairs,
-                              h->dbgcfg.tp_grid > 0 ? h->dbgcfg.tp_grid : kTpGridCap, words, &h->tpi, &bad);
-  h->bytes_reserved += h->tp.bytes - before;
-  if (e != hipSuccess) {
-    h->n_res = -1;
-    h->err = std::string("global top-K: ") + (bad ? bad : hipGetErrorString(e));
-    return bad ? APSS_E_STATE : e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
-  }
-  h->out_q = h->tp.out_q;
-  h->out_c = h->tp.out_c;
-  h->out_s = h->tp.out_s;
-  h->n_res = h->tpi.kept;
-  h->st.result_pairs = h->n_res;
-  if (n_results) *n_results = h->n_res;
+  APSS_TRY(run_stage(h, "global top-K", h->tp.mem, [&](const char **bad) {
+    return tp_run(h->tp, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, batch.ext, batch.nq, h->ext.p, h->n_rows, h->top_pairs,
+                  h->dbgcfg.tp_grid > 0 ? h->dbgcfg.tp_grid : kTpGridCap, h->scalars->top_pairs, &h->tpi, bad);
+  }));
+  adopt_list(h, h->tp.out_q, h->tp.out_c, h->tp.out_s, h->tpi.kept);
   return APSS_OK;
 }
 
-// A query-type call: its final list (probe_lists), then, with apss_set_top_pairs, ONE global cut of that list.
-int32_t probe(apss_handle *h, int64_t nq, const int64_t *q_rowptr, const int32_t *q_idx, const float *q_val,
-              const int64_t *q_ext, int64_t q_slot_first, int64_t q_max_nnz, float q_max_norm2,
-              int64_t q_nnz_end, int64_t *n_results) {
+// the whole store as a query batch (apss_self_join; its last rows: apss_insert_and_query)
+QueryBatch store_batch(const apss_handle *h) {
+  return QueryBatch{{h->n_rows, h->rowptr.p, h->idx.p, h->val.p, h->ext.p}, 0, h->store_max_nnz, h->store_max_norm2, h->nnz};
+}
+
+// A query-type call: its list (probe_lists), then, with apss_set_top_pairs, ONE global cut of that list.  *n_results is written
+// here, from what the last stage adopted
+int32_t probe(apss_handle *h, const QueryBatch &batch, int64_t *n_results) {
   h->tpi = apss_top_pairs_info{};
   h->tpi.k_pairs = h->top_pairs;
-  APSS_TRY(probe_lists(h, nq, q_rowptr, q_idx, q_val, q_ext, q_slot_first, q_max_nnz, q_max_norm2, q_nnz_end, n_results));
-  if (h->top_pairs <= 0 || h->sharded) return APSS_OK;
-  return cut_top_pairs(h, nq, q_ext, n_results);
+  APSS_TRY(probe_lists(h, batch, n_results));
+  if (h->top_pairs > 0 && !h->sharded) APSS_TRY(cut_top_pairs(h, batch));
+  if (n_results) *n_results = h->n_res;
+  return APSS_OK;
 }
 
 int32_t validate_host_csr(apss_handle *h, int64_t n, const int64_t *rowptr, const int32_t *indices,
@@ -3306,14 +3318,7 @@ int32_t insert_dev_impl(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d
                         const float *d_val, const int64_t *d_ext, int64_t *first_new_row) {
   *first_new_row = h->n_rows;
   if (n == 0) return APSS_OK;
-  // the results and the query batch of the last call may point into store arrays that this insert reallocates:
-  // they are gone (apss_fetch_results / apss_partial_scores_dev answer APSS_E_STATE until the next query-type call)
-  h->n_res = -1;
-  h->res_q_ext = nullptr;
-  h->last_q_rowptr = nullptr;
-  h->last_q_idx = nullptr;
-  h->last_q_val = nullptr;
-  h->last_nq = 0;
+  forget_last_call(h);  // (the results and the query batch of the last call may point into store arrays that this insert reallocates)
   if (h->n_rows + n > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "more than 2^31 - 1 vectors in one handle");
   int64_t kept_rows = 0, kept_nnz = 0;
   const bool was_nonneg = h->nonneg;
@@ -3371,18 +3376,12 @@ int32_t query_dev_impl(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_
   // the results and the query batch of the last call live until the next query-type call: this one restages q_* (a plain
   // batch is written there before its flags are known, and the buffers may be reallocated), so they are gone from here on --
   // also when this batch is rejected (the result calls then answer APSS_E_STATE, as after an insert)
-  h->n_res = -1;
-  h->res_q_ext = nullptr;
-  h->last_q_rowptr = nullptr;
-  h->last_q_idx = nullptr;
-  h->last_q_val = nullptr;
-  h->last_nq = 0;
+  forget_last_call(h);
   int64_t kept_rows = 0, kept_nnz = 0;
   APSS_TRY(ingest(h, n, nnz, d_rowptr, d_idx, d_val, d_ext, false, &kept_rows, &kept_nnz));
   // the batch's rows of the dense-head block and its tail ratios (the store's were packed when it was indexed)
   if (h->head_k && !h->sharded && kept_rows > 0) APSS_TRY(pack_query_head(h, h->q_rowptr.p, h->q_idx.p, h->q_val.p, kept_rows));
-  return probe(h, kept_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p, -1, h->q_max_nnz, h->q_max_norm2, kept_nnz,
-               n_results);
+  return probe(h, QueryBatch{{kept_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, kept_nnz}, n_results);
 }
 
 // apss_clear: the index, the store and the marks go, the reservations and the settings stay
@@ -3394,12 +3393,7 @@ int32_t clear_impl(apss_handle *h) {
   h->n_tiles = 0;
   for (apss_handle::IndexSet *s : {&h->ex, &h->cx}) { s->n_tiles = 0; s->post_used = 0; s->h_base.clear(); s->built_rows = 0; }
   h->ex_built_rows = 0;
-  h->n_res = -1;
-  h->res_q_ext = nullptr;
-  h->last_q_rowptr = nullptr;
-  h->last_q_idx = nullptr;
-  h->last_q_val = nullptr;
-  h->last_nq = 0;
+  forget_last_call(h);
   h->nonneg = true;
   h->q_nonneg = true;
   h->no_acc8 = h->dbgcfg.no_acc8;
@@ -3426,32 +3420,35 @@ int32_t refuse_shard_removal(apss_handle *h, const char *what) {
   return fail(h, APSS_E_UNSUPPORTED, std::string(what) + ": not on a term shard (it holds slices of rows; a compaction needs whole ones)");
 }
 
+// An id list of a call, d_ids[0, n) (device, n > 0), ascending in h->rm_sorted (rocprim radix sort through h->rm_tmp).  What the
+// sort needs is reserved first; the sort itself opens the call's timed stretch (e0)
+int32_t sort_ids(apss_handle *h, const int64_t *d_ids, int64_t n, hipEvent_t &e0) {
+  APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
+  size_t tmp_bytes = 0;
+  HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+  APSS_TRY(ensure(h, h->rm_tmp, tmp_bytes + 256));
+  HIPCHK(h, begin_timed(h->stream, e0));
+  HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+  return APSS_OK;
+}
+
 // marks the stored rows whose external id is in d_ids[0, n) (device); *newly = rows that were live before
 int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *newly) {
   *newly = 0;
   if (n == 0 || h->n_rows == 0) return APSS_OK;
   if (n > 0x7fffffffLL) return fail(h, APSS_E_INVALID, "apss_remove: more than 2^31 - 1 ids in one call");
-  APSS_TRY(rm_events(h));
   APSS_TRY(rm_extend(h));
-  APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
   APSS_TRY(ensure(h, h->rm_ctr, 1));
-  size_t tmp_bytes = 0;
-  HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
-  APSS_TRY(ensure(h, h->rm_tmp, tmp_bytes + 256));
   HIPCHK(h, hipMemsetAsync(h->rm_ctr.p, 0, sizeof(unsigned long long), h->stream));
-  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
-  HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
+  APSS_TRY(sort_ids(h, d_ids, n, h->rm_ev0));
   // (two rows per thread; the workgroups loop: one global add each)
   const int64_t blocks = ceil_div(ceil_div(h->n_rows, 2), kRmThreads);
   hipLaunchKernelGGL(k_rm_mark, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 4096))), dim3(kRmThreads), 0, h->stream, (const int64_t *)h->ext.p, h->n_rows,
                      (const int64_t *)h->rm_sorted.p, n, h->dead.p, h->rm_ctr.p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
   unsigned long long marked = 0;
-  HIPCHK(h, hipMemcpyAsync(&marked, h->rm_ctr.p, sizeof(marked), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  HIPCHK(h, end_timed_read(h->stream, h->rm_ev0, h->rm_ev1, {{&marked, h->rm_ctr.p, sizeof(marked)}}, &ms));
   h->ri.mark_ms = ms;
   h->rm_marked += (int64_t)marked;
   h->ri.removed_total += (int64_t)marked;
@@ -3464,13 +3461,9 @@ int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *ne
 int32_t compact_impl(apss_handle *h) {
   if (h->rm_marked <= 0) return APSS_OK;
   const int64_t n = h->n_rows, marked = h->rm_marked;
-  APSS_TRY(rm_events(h));
   APSS_TRY(rm_extend(h));
-  APSS_TRY(ensure(h, h->s_keep, (size_t)n + 1));
-  APSS_TRY(ensure(h, h->s_cnt, (size_t)n + 1));
-  APSS_TRY(ensure(h, h->s_rowdst, (size_t)n + 1));
-  APSS_TRY(ensure(h, h->s_nnzdst, (size_t)n + 1));
-  HIPCHK(h, hipEventRecord(h->rm_ev0, h->stream));
+  for (DevBuf<int64_t> *b : {&h->s_keep, &h->s_cnt, &h->s_rowdst, &h->s_nnzdst}) APSS_TRY(ensure(h, *b, (size_t)n + 1));
+  HIPCHK(h, begin_timed(h->stream, h->rm_ev0));
   hipLaunchKernelGGL(k_rm_rows, dim3((unsigned)std::min<int64_t>(ceil_div(n, kRmThreads), rm_grid_cap(h, 4096))), dim3(kRmThreads), 0, h->stream,
                      (const uint8_t *)h->dead.p, (const int64_t *)h->rowptr.p, n, h->s_keep.p, h->s_cnt.p);
   HIPCHK(h, hipGetLastError());
@@ -3506,10 +3499,8 @@ int32_t compact_impl(apss_handle *h) {
   const int32_t rc = insert_dev_impl(h, live_rows, live_nnz, h->in_rowptr.p, h->in_idx.p, h->in_val.p, h->in_ext.p, &first);
   h->stored_rows = false;
   APSS_TRY(rc);
-  HIPCHK(h, hipEventRecord(h->rm_ev1, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->rm_ev0, h->rm_ev1));
+  HIPCHK(h, end_timed_read(h->stream, h->rm_ev0, h->rm_ev1, {}, &ms));
   h->ri.compact_ms = ms;
   h->ri.compacted_rows = marked;
   ++h->ri.compactions;
@@ -3522,132 +3513,117 @@ int32_t auto_compact(apss_handle *h) {
   return compact_impl(h);
 }
 
+// apss_query_stored, step 1: the live stored rows that d_ids[0, n) (device, n > 0) name -- the sorted list looked up per slot, the
+// keep flags and entry counts scanned into destinations, the id counters (apss_query_stored.hpp).  Ends in the ONE readback
+// between selection and gather: the two scan totals and the id counts
+int32_t select_stored_rows(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *sel_rows, int64_t *sel_nnz) {
+  const int64_t rows = h->n_rows;
+  if (h->rm_marked > 0) APSS_TRY(rm_extend(h));
+  APSS_TRY(ensure(h, h->qs_found, (size_t)n));
+  APSS_TRY(ensure(h, h->qs_ctr, 2));
+  if (rows > 0)
+    for (DevBuf<int64_t> *b : {&h->s_keep, &h->s_cnt, &h->s_rowdst, &h->s_nnzdst}) APSS_TRY(ensure(h, *b, (size_t)rows + 1));
+  APSS_TRY(sort_ids(h, d_ids, n, h->qs_ev[0]));
+  HIPCHK(h, hipMemsetAsync(h->qs_found.p, 0, (size_t)n, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->qs_ctr.p, 0, 2 * sizeof(unsigned long long), h->stream));
+  if (rows > 0) {
+    QsSelectArgs s{};
+    s.ext = h->ext.p;
+    s.rowptr = h->rowptr.p;
+    s.rows = rows;
+    s.dead = h->rm_marked > 0 ? h->dead.p : nullptr;  // (nothing marked: nothing of the map is read)
+    s.ids = h->rm_sorted.p;
+    s.n_ids = n;
+    s.found = h->qs_found.p;
+    s.keep = h->s_keep.p;
+    s.cnt = h->s_cnt.p;
+    const int64_t blocks = ceil_div(ceil_div(rows, 2), kQsThreads);
+    hipLaunchKernelGGL(k_qs_select, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream, s);
+    HIPCHK(h, hipGetLastError());
+    ++h->qsi.launches;
+    APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, rows));
+    APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, rows));
+  }
+  hipLaunchKernelGGL(k_qs_ids, dim3((unsigned)std::min<int64_t>(ceil_div(n, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
+                     (const int64_t *)h->rm_sorted.p, n, (const uint8_t *)h->qs_found.p, h->qs_ctr.p);
+  HIPCHK(h, hipGetLastError());
+  ++h->qsi.launches;
+  int64_t *back = h->scalars->stored_back;
+  back[0] = back[1] = 0;
+  const size_t total = rows > 0 ? sizeof(int64_t) : 0;
+  float ms = 0.f;  // (the wait: the caller's id array may be reused from here on)
+  HIPCHK(h, end_timed_read(h->stream, h->qs_ev[0], h->qs_ev[1], {{&back[0], h->s_rowdst.p + rows, total}, {&back[1], h->s_nnzdst.p + rows, total},
+                                                       {&back[2], h->qs_ctr.p, 2 * sizeof(unsigned long long)}}, &ms));
+  *sel_rows = back[0];
+  *sel_nnz = back[1];
+  h->qsi.ids_distinct = back[2];
+  h->qsi.ids_missing = back[3];
+  h->qsi.select_ms = ms;
+  if (*sel_rows < 0 || *sel_rows > rows || *sel_nnz < 0 || *sel_nnz > h->nnz) return fail(h, APSS_E_STATE, "apss_query_stored: the selection and the store disagree");
+  return APSS_OK;
+}
+
+// ... step 2: the selected rows, gathered into the query staging exactly as they are stored, with the batch summaries the probe
+// plans with (k_qs_slots, k_qs_gather) and, on a handle with a dense-head block, their rows of the block
+int32_t gather_stored_rows(apss_handle *h, int64_t sel_rows, int64_t sel_nnz) {
+  const int64_t rows = h->n_rows;
+  APSS_TRY(ensure(h, h->qs_slots, (size_t)sel_rows));
+  APSS_TRY(ensure(h, h->q_rowptr, (size_t)sel_rows + 1));
+  APSS_TRY(ensure(h, h->q_ext, (size_t)sel_rows));
+  APSS_TRY(ensure(h, h->q_idx, (size_t)std::max<int64_t>(sel_nnz, 1)));
+  APSS_TRY(ensure(h, h->q_val, (size_t)std::max<int64_t>(sel_nnz, 1)));
+  APSS_TRY(ensure(h, h->flagword, 4));
+  HIPCHK(h, begin_timed(h->stream, h->qs_ev[2]));
+  HIPCHK(h, hipMemsetAsync(h->flagword.p, 0, 4 * sizeof(unsigned int), h->stream));
+  hipLaunchKernelGGL(k_qs_slots, dim3((unsigned)std::min<int64_t>(ceil_div(rows, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
+                     (const int64_t *)h->s_keep.p, (const int64_t *)h->s_rowdst.p, rows, h->qs_slots.p);
+  HIPCHK(h, hipGetLastError());
+  QsGatherArgs g{};
+  g.slots = h->qs_slots.p;
+  g.n_sel = sel_rows;
+  g.rowptr = h->rowptr.p;
+  g.ext = h->ext.p;
+  g.idx = h->idx.p;
+  g.val = h->val.p;
+  g.nnz_dst = h->s_nnzdst.p;
+  g.o_rowptr = h->q_rowptr.p;
+  g.o_ext = h->q_ext.p;
+  g.o_idx = h->q_idx.p;
+  g.o_val = h->q_val.p;
+  g.flags_out = h->flagword.p;
+  // (one wave per SELECTED row: the grid does not know how many rows are stored)
+  hipLaunchKernelGGL(k_qs_gather, dim3((unsigned)ceil_div(sel_rows * kQsWave, kQsThreads)), dim3(kQsThreads), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  h->qsi.launches += 2;
+  // the batch summaries: the probe plans on the host with them, before its first launch
+  unsigned int *flags_host = h->scalars->ingest_flags;
+  float ms = 0.f;
+  HIPCHK(h, end_timed_read(h->stream, h->qs_ev[2], h->qs_ev[3], {{flags_host, h->flagword.p, 4 * sizeof(unsigned int)}}, &ms));
+  h->qsi.gather_ms = ms;
+  APSS_TRY(take_ingest_flags(h, flags_host, false));
+  // the batch's rows of the dense-head block and its tail ratios, as query_dev_impl packs them
+  if (h->head_k && !h->sharded) APSS_TRY(pack_query_head(h, h->q_rowptr.p, h->q_idx.p, h->q_val.p, sel_rows));
+  return APSS_OK;
+}
+
 // apss_query_stored: the live stored rows named by d_ids[0, n) (device) become the staged query batch -- selected, scanned and
 // gathered on the device (apss_query_stored.hpp), never through ingest: they were normalised, pruned and admitted when they came
 // in -- and the batch is probed as the outside batch apss_query_dev would stage from the same rows.
 int32_t query_stored_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *n_rows, int64_t *n_results) {
   // a query-type call: the last results and query batch are gone from here on (the staging is rewritten), also when it fails
-  h->n_res = -1;
-  h->res_q_ext = nullptr;
-  h->last_q_rowptr = nullptr;
-  h->last_q_idx = nullptr;
-  h->last_q_val = nullptr;
-  h->last_nq = 0;
+  forget_last_call(h);
   h->qsi = apss_stored_query_info{};
   h->qsi.ids_given = n;
-  const int64_t rows = h->n_rows;
   int64_t sel_rows = 0, sel_nnz = 0;
-  if (n > 0) {
-    for (hipEvent_t &e : h->qs_ev)
-      if (!e) HIPCHK(h, hipEventCreate(&e));
-    if (h->rm_marked > 0) APSS_TRY(rm_extend(h));
-    APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
-    APSS_TRY(ensure(h, h->qs_found, (size_t)n));
-    APSS_TRY(ensure(h, h->qs_ctr, 2));
-    size_t tmp_bytes = 0;
-    HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
-    APSS_TRY(ensure(h, h->rm_tmp, tmp_bytes + 256));
-    if (rows > 0) {
-      APSS_TRY(ensure(h, h->s_keep, (size_t)rows + 1));
-      APSS_TRY(ensure(h, h->s_cnt, (size_t)rows + 1));
-      APSS_TRY(ensure(h, h->s_rowdst, (size_t)rows + 1));
-      APSS_TRY(ensure(h, h->s_nnzdst, (size_t)rows + 1));
-    }
-    HIPCHK(h, hipEventRecord(h->qs_ev[0], h->stream));
-    HIPCHK(h, hipMemsetAsync(h->qs_found.p, 0, (size_t)n, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->qs_ctr.p, 0, 2 * sizeof(unsigned long long), h->stream));
-    HIPCHK(h, rocprim::radix_sort_keys((void *)h->rm_tmp.p, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
-    if (rows > 0) {
-      QsSelectArgs s{};
-      s.ext = h->ext.p;
-      s.rowptr = h->rowptr.p;
-      s.rows = rows;
-      s.dead = h->rm_marked > 0 ? h->dead.p : nullptr;  // (nothing marked: nothing of the map is read)
-      s.ids = h->rm_sorted.p;
-      s.n_ids = n;
-      s.found = h->qs_found.p;
-      s.keep = h->s_keep.p;
-      s.cnt = h->s_cnt.p;
-      const int64_t blocks = ceil_div(ceil_div(rows, 2), kQsThreads);
-      hipLaunchKernelGGL(k_qs_select, dim3((unsigned)std::min<int64_t>(blocks, rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream, s);
-      HIPCHK(h, hipGetLastError());
-      ++h->qsi.launches;
-      APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, rows));
-      APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, rows));
-    }
-    hipLaunchKernelGGL(k_qs_ids, dim3((unsigned)std::min<int64_t>(ceil_div(n, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
-                       (const int64_t *)h->rm_sorted.p, n, (const uint8_t *)h->qs_found.p, h->qs_ctr.p);
-    HIPCHK(h, hipGetLastError());
-    ++h->qsi.launches;
-    HIPCHK(h, hipEventRecord(h->qs_ev[1], h->stream));
-    // the ONE readback between selection and gather: the two scan totals and the id counts
-    int64_t back_stack[4] = {0, 0, 0, 0};
-    int64_t *back = h->pin ? reinterpret_cast<int64_t *>(h->pin + kPinBytes + 640) : back_stack;
-    back[0] = back[1] = 0;
-    if (rows > 0) {
-      HIPCHK(h, hipMemcpyAsync(&back[0], h->s_rowdst.p + rows, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipMemcpyAsync(&back[1], h->s_nnzdst.p + rows, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipMemcpyAsync(&back[2], h->qs_ctr.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // (the caller's id array may be reused from here on)
-    sel_rows = back[0];
-    sel_nnz = back[1];
-    h->qsi.ids_distinct = back[2];
-    h->qsi.ids_missing = back[3];
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->qs_ev[0], h->qs_ev[1]));
-    h->qsi.select_ms = ms;
-    if (sel_rows < 0 || sel_rows > rows || sel_nnz < 0 || sel_nnz > h->nnz) return fail(h, APSS_E_STATE, "apss_query_stored: the selection and the store disagree");
-  }
+  if (n > 0) APSS_TRY(select_stored_rows(h, n, d_ids, &sel_rows, &sel_nnz));
   h->qsi.rows_selected = sel_rows;
   h->qsi.nnz_selected = sel_nnz;
   if (n_rows) *n_rows = sel_rows;
   h->q_nonneg = true;
   h->q_max_nnz = 0;
   h->q_max_norm2 = 0.f;
-  if (sel_rows > 0) {
-    APSS_TRY(ensure(h, h->qs_slots, (size_t)sel_rows));
-    APSS_TRY(ensure(h, h->q_rowptr, (size_t)sel_rows + 1));
-    APSS_TRY(ensure(h, h->q_ext, (size_t)sel_rows));
-    APSS_TRY(ensure(h, h->q_idx, (size_t)std::max<int64_t>(sel_nnz, 1)));
-    APSS_TRY(ensure(h, h->q_val, (size_t)std::max<int64_t>(sel_nnz, 1)));
-    APSS_TRY(ensure(h, h->flagword, 4));
-    HIPCHK(h, hipEventRecord(h->qs_ev[2], h->stream));
-    HIPCHK(h, hipMemsetAsync(h->flagword.p, 0, 4 * sizeof(unsigned int), h->stream));
-    hipLaunchKernelGGL(k_qs_slots, dim3((unsigned)std::min<int64_t>(ceil_div(rows, kQsThreads), rm_grid_cap(h, 4096))), dim3(kQsThreads), 0, h->stream,
-                       (const int64_t *)h->s_keep.p, (const int64_t *)h->s_rowdst.p, rows, h->qs_slots.p);
-    HIPCHK(h, hipGetLastError());
-    QsGatherArgs g{};
-    g.slots = h->qs_slots.p;
-    g.n_sel = sel_rows;
-    g.rowptr = h->rowptr.p;
-    g.ext = h->ext.p;
-    g.idx = h->idx.p;
-    g.val = h->val.p;
-    g.nnz_dst = h->s_nnzdst.p;
-    g.o_rowptr = h->q_rowptr.p;
-    g.o_ext = h->q_ext.p;
-    g.o_idx = h->q_idx.p;
-    g.o_val = h->q_val.p;
-    g.flags_out = h->flagword.p;
-    // (one wave per SELECTED row: the grid does not know how many rows are stored)
-    hipLaunchKernelGGL(k_qs_gather, dim3((unsigned)ceil_div(sel_rows * kQsWave, kQsThreads)), dim3(kQsThreads), 0, h->stream, g);
-    HIPCHK(h, hipGetLastError());
-    h->qsi.launches += 2;
-    HIPCHK(h, hipEventRecord(h->qs_ev[3], h->stream));
-    // the batch summaries: the probe plans on the host with them, before its first launch
-    unsigned int flags_stack[4] = {0, 0, 0, 0};
-    unsigned int *flags_host = h->pin ? reinterpret_cast<unsigned int *>(h->pin + kPinBytes) : flags_stack;
-    HIPCHK(h, hipMemcpyAsync(flags_host, h->flagword.p, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->qs_ev[2], h->qs_ev[3]));
-    h->qsi.gather_ms = ms;
-    APSS_TRY(take_ingest_flags(h, flags_host, false));
-    // the batch's rows of the dense-head block and its tail ratios, as query_dev_impl packs them
-    if (h->head_k && !h->sharded) APSS_TRY(pack_query_head(h, h->q_rowptr.p, h->q_idx.p, h->q_val.p, sel_rows));
-  }
-  return probe(h, sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz, n_results);
+  if (sel_rows > 0) APSS_TRY(gather_stored_rows(h, sel_rows, sel_nnz));
+  return probe(h, QueryBatch{{sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz}, n_results);
 }
 
 int32_t check_stored_query(apss_handle *h, const char *what, int64_t n, const int64_t *ids, int64_t *n_rows, int64_t *n_results) {
@@ -3736,6 +3712,7 @@ int32_t apss_create(const apss_config *cfg, apss_handle **out) {
   }
   h->stream = h->own_stream;
   if (hipHostMalloc((void **)&h->pin, kPinBytes + kPinScalars, hipHostMallocDefault) != hipSuccess) h->pin = nullptr;  // (without it: the unpacked copies)
+  if (h->pin) h->scalars = new (h->pin + kPinBytes) PinScalars{};
   if (cfg->capacity_rows > 0) {
     if (ensure(h, h->rowptr, (size_t)cfg->capacity_rows + 1, 0, true) != APSS_OK ||
         ensure(h, h->ext, (size_t)cfg->capacity_rows, 0, true) != APSS_OK) {
@@ -3779,19 +3756,12 @@ void apss_destroy(apss_handle *h) {
   release(h->win_df); release(h->win_b); h->win.release();
   release(h->row_pairs);
   release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
-  if (h->rm_ev0) (void)hipEventDestroy(h->rm_ev0);
-  if (h->rm_ev1) (void)hipEventDestroy(h->rm_ev1);
   release(h->qs_found); release(h->qs_ctr); release(h->qs_slots);
-  for (hipEvent_t e : h->qs_ev)
-    if (e) (void)hipEventDestroy(e);
   if (h->pin) (void)hipHostFree(h->pin);
   release(h->wl_dev);
   if (h->wl_pin) (void)hipHostFree(h->wl_pin);
-  if (h->wl_ev) (void)hipEventDestroy(h->wl_ev);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev2) (void)hipEventDestroy(h->ev2);
-  if (h->ev3) (void)hipEventDestroy(h->ev3);
+  for (hipEvent_t e : {h->rm_ev0, h->rm_ev1, h->qs_ev[0], h->qs_ev[1], h->qs_ev[2], h->qs_ev[3], h->wl_ev, h->ev0, h->ev1, h->ev2, h->ev3})
+    if (e) (void)hipEventDestroy(e);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -3836,7 +3806,7 @@ int32_t apss_insert_and_query(apss_handle *h, int64_t n, const int64_t *rowptr, 
 int32_t apss_self_join(apss_handle *h, int64_t *n_results) {
   APSS_TRY(enter(h));
   if (h->idx_rows < h->n_rows) APSS_TRY(build_index(h, h->idx_rows));  // a self-join runs over the index: fold the tail in
-  return probe(h, h->n_rows, h->rowptr.p, h->idx.p, h->val.p, h->ext.p, 0, h->store_max_nnz, h->store_max_norm2, h->nnz, n_results);
+  return probe(h, store_batch(h), n_results);
 }
 
 int32_t apss_result_count(const apss_handle *h, int64_t *n_results) {
@@ -3973,10 +3943,8 @@ int32_t apss_insert_and_query_dev(apss_handle *h, int64_t n, int64_t nnz, const 
   APSS_TRY(auto_compact(h));
   int64_t first = 0;
   APSS_TRY(insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first));
-  const int64_t nq = h->n_rows - first;
   // the batch is now rows [first, n_rows) of the store: query it in place (rowptr offsets are absolute)
-  return probe(h, nq, h->rowptr.p + first, h->idx.p, h->val.p, h->ext.p + first, first, h->store_max_nnz, h->store_max_norm2, h->nnz,
-               n_results);
+  return probe(h, store_batch(h).rows(first, h->n_rows), n_results);
 }
 
 int32_t apss_clear(apss_handle *h) {

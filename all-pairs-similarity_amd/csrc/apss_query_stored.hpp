@@ -20,24 +20,14 @@
 
 #include <cstdint>
 
+#include "apss_stage.hpp"
+
 namespace apss {
 namespace {
 
 constexpr int kQsThreads = 256;
 constexpr int kQsWave = 64;
 constexpr int kQsNormLanes = 16;  // lanes that sum a row's squares: kGroup of the ingest kernels, whose bits the sum must keep
-
-// first position of `key` in the ascending list ids[0, n), or -1 (n > 0)
-__device__ inline int64_t qs_find(const int64_t *__restrict__ ids, int64_t n, int64_t lo_id, int64_t hi_id, int64_t key) {
-  if (key < lo_id || key > hi_id) return -1;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && ids[lo] == key ? lo : -1;
-}
 
 struct QsSelectArgs {
   const int64_t *ext;     // [rows] the store's external ids (16-B aligned)
@@ -56,16 +46,10 @@ __global__ __launch_bounds__(kQsThreads) void k_qs_select(const QsSelectArgs a) 
   for (int64_t p = (int64_t)blockIdx.x * kQsThreads + threadIdx.x; p < n2; p += (int64_t)gridDim.x * kQsThreads) {
     const int64_t r = 2 * p;
     const bool two = r + 1 < a.rows;
-    int64_t e0, e1 = 0;
-    if (two) {
-      const longlong2 v = *reinterpret_cast<const longlong2 *>(a.ext + r);
-      e0 = v.x;
-      e1 = v.y;
-    } else {
-      e0 = a.ext[r];
-    }
-    const int64_t p0 = a.dead && a.dead[r] ? -1 : qs_find(a.ids, a.n_ids, lo_id, hi_id, e0);
-    const int64_t p1 = !two || (a.dead && a.dead[r + 1]) ? -1 : qs_find(a.ids, a.n_ids, lo_id, hi_id, e1);
+    int64_t e0, e1;
+    load_two_ids(a.ext, r, two, e0, e1);
+    const int64_t p0 = a.dead && a.dead[r] ? -1 : sorted_find(a.ids, a.n_ids, lo_id, hi_id, e0);
+    const int64_t p1 = !two || (a.dead && a.dead[r + 1]) ? -1 : sorted_find(a.ids, a.n_ids, lo_id, hi_id, e1);
     longlong2 k, c;
     k.x = p0 >= 0 ? 1 : 0;
     k.y = p1 >= 0 ? 1 : 0;
@@ -100,10 +84,8 @@ __global__ __launch_bounds__(kQsThreads) void k_qs_ids(const int64_t *__restrict
       if (!found[i]) ++missing;
     }
   }
-  for (int off = kQsWave / 2; off > 0; off >>= 1) {
-    distinct += __shfl_xor(distinct, off);
-    missing += __shfl_xor(missing, off);
-  }
+  distinct = wave_sum(distinct);
+  missing = wave_sum(missing);
   if (threadIdx.x % kQsWave == 0) {
     part[0][threadIdx.x / kQsWave] = distinct;
     part[1][threadIdx.x / kQsWave] = missing;

@@ -19,6 +19,8 @@
 
 #include <cstdint>
 
+#include "apss_stage.hpp"
+
 namespace apss {
 namespace {
 
@@ -28,14 +30,7 @@ constexpr int kRmItems = 4;  // pairs per lane of k_rm_drop
 
 // is `key` in the ascending list ids[0, n)?  (n > 0)
 __device__ inline bool rm_listed(const int64_t *__restrict__ ids, int64_t n, int64_t lo_id, int64_t hi_id, int64_t key) {
-  if (key < lo_id || key > hi_id) return false;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ids[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && ids[lo] == key;
+  return sorted_find(ids, n, lo_id, hi_id, key) >= 0;
 }
 
 // ext[rows]: the store's external ids (16-B aligned); ids[n_ids]: the removal list, ascending, n_ids > 0; dead[rows]
@@ -48,14 +43,8 @@ __global__ __launch_bounds__(kRmThreads) void k_rm_mark(const int64_t *__restric
   for (int64_t p = (int64_t)blockIdx.x * kRmThreads + threadIdx.x; p < n2; p += (int64_t)gridDim.x * kRmThreads) {
     const int64_t r = 2 * p;
     const bool two = r + 1 < rows;
-    int64_t e0, e1 = 0;
-    if (two) {
-      const longlong2 v = *reinterpret_cast<const longlong2 *>(ext + r);
-      e0 = v.x;
-      e1 = v.y;
-    } else {
-      e0 = ext[r];
-    }
+    int64_t e0, e1;
+    load_two_ids(ext, r, two, e0, e1);
     if (!dead[r] && rm_listed(ids, n_ids, lo_id, hi_id, e0)) {
       dead[r] = 1;
       ++mine;
@@ -65,7 +54,7 @@ __global__ __launch_bounds__(kRmThreads) void k_rm_mark(const int64_t *__restric
       ++mine;
     }
   }
-  for (int off = kRmWave / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+  mine = wave_sum(mine);
   if (threadIdx.x % kRmWave == 0) part[threadIdx.x / kRmWave] = mine;
   __syncthreads();
   if (threadIdx.x == 0) {

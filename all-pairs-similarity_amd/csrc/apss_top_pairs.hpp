@@ -32,6 +32,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "../../include/apss.h"
+#include "apss_stage.hpp"
 #include "apss_topk.hpp"
 #include "apss_topk_key.hpp"
 
@@ -372,28 +373,11 @@ struct TpWork {
   float *out_s = nullptr;
   char *tmp = nullptr;  // rocprim's scratch
   size_t tie_cap = 0, sel_cap = 0, tmp_cap = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  size_t bytes = 0;  // device bytes reserved
+  StageMem mem;
 };
 
-template <class T>
-inline hipError_t tp_grow(TpWork &w, T *&p, size_t old_n, size_t n) {
-  if (p) {
-    (void)hipFree(p);  // (synchronises; the stage runs after the call's other work, nothing reads these buffers then)
-    p = nullptr;
-    w.bytes -= old_n * sizeof(T);
-  }
-  const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-  if (e == hipSuccess) w.bytes += n * sizeof(T);
-  return e;
-}
-
 inline void tp_release(TpWork &w) {
-  for (void *p : {(void *)w.state, (void *)w.hist, (void *)w.tie, (void *)w.key_a, (void *)w.key_b, (void *)w.perm_a, (void *)w.perm_b,
-                  (void *)w.out_q, (void *)w.out_c, (void *)w.out_s, (void *)w.tmp})
-    if (p) (void)hipFree(p);
-  if (w.e0) (void)hipEventDestroy(w.e0);
-  if (w.e1) (void)hipEventDestroy(w.e1);
+  w.mem.free_all({w.state, w.hist, w.tie, w.key_a, w.key_b, w.perm_a, w.perm_b, w.out_q, w.out_c, w.out_s, w.tmp});
   w = TpWork{};
 }
 
@@ -413,12 +397,10 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
   hipError_t e;
   const int64_t m = std::min<int64_t>(K, n);
   const bool cut = n > K;
-  if (!w.e0 && (e = hipEventCreate(&w.e0)) != hipSuccess) return e;
-  if (!w.e1 && (e = hipEventCreate(&w.e1)) != hipSuccess) return e;
   constexpr size_t kHistWords = (size_t)(kTpScorePasses + kTpTieDigitsMax) * kTpBins;
   if (!w.state) {
-    if ((e = tp_grow(w, w.state, 0, (size_t)kTpWords)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.hist, 0, kHistWords)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.state, 0, (size_t)kTpWords)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.hist, 0, kHistWords)) != hipSuccess) return e;
   }
   TpList l{};
   l.q = q, l.c = c, l.s = s, l.n = n, l.q_ext = q_ext, l.c_ext = c_ext, l.nq = nq, l.n_store = n_store;
@@ -433,22 +415,22 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
     return e;
   const size_t tmp_need = std::max(tmp_pos, std::max(tmp64, tmp32)) + 256;
   if (tmp_need > w.tmp_cap) {
-    if ((e = tp_grow(w, w.tmp, w.tmp_cap, tmp_need)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.tmp, w.tmp_cap, tmp_need)) != hipSuccess) return e;
     w.tmp_cap = tmp_need;
   }
   if ((size_t)m > w.sel_cap) {
     const size_t cap = std::min<size_t>((size_t)APSS_TOP_PAIRS_MAX, std::max<size_t>((size_t)m + (size_t)m / 8, 1024));
-    if ((e = tp_grow(w, w.key_a, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.key_b, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.perm_a, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.perm_b, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.out_q, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.out_c, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = tp_grow(w, w.out_s, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.key_a, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.key_b, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.perm_a, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.perm_b, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_q, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_c, w.sel_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_s, w.sel_cap, cap)) != hipSuccess) return e;
     w.sel_cap = cap;
   }
   const auto grid = [&](int64_t items, int64_t per) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per - 1) / per, grid_cap))); };
-  if ((e = hipEventRecord(w.e0, stream)) != hipSuccess) return e;
+  if ((e = begin_timed(stream, w.mem.e0)) != hipSuccess) return e;
   int64_t above = 0, tied = 0;
   const uint32_t *selection = nullptr;  // (n <= K: the whole list)
   if (cut) {
@@ -479,7 +461,7 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
     const bool ties_all = want == tied;
     if (!ties_all && (size_t)tied > w.tie_cap) {
       const size_t cap = (size_t)tied + (size_t)tied / 8 + 1024;
-      if ((e = tp_grow(w, w.tie, w.tie_cap, cap)) != hipSuccess) return e;
+      if ((e = w.mem.grow(w.tie, w.tie_cap, cap)) != hipSuccess) return e;
       w.tie_cap = cap;
     }
     // ---- 2. collect
@@ -527,15 +509,12 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
   hipLaunchKernelGGL(k_tp_write, grid(m, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)pa, m, l, w.out_q, w.out_c, w.out_s);
   ++info->launches;
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = hipEventRecord(w.e1, stream)) != hipSuccess) return e;
-  if (cut && (e = hipMemcpyAsync(words, w.state, kTpWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // the second wait ends the stage
+  float ms = 0.f;  // (the second wait ends the stage)
+  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.state, cut ? kTpWords * sizeof(unsigned long long) : 0}}, &ms)) != hipSuccess) return e;
   if (cut && (int64_t)words[kTpSelCursor] != K) {
     *bad = "the selection does not hold K pairs";
     return hipErrorUnknown;
   }
-  float ms = 0.f;
-  if ((e = hipEventElapsedTime(&ms, w.e0, w.e1)) != hipSuccess) return e;
   info->select_ms = ms;
   info->kept = m;
   return hipSuccess;

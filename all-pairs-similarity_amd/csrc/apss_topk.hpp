@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "../../include/apss.h"
+#include "apss_stage.hpp"
 #include "apss_topk_key.hpp"
 
 namespace apss {
@@ -395,29 +396,12 @@ struct TopkWork {
   int32_t *seg_c = nullptr, *out_q = nullptr, *out_c = nullptr;
   float *seg_s = nullptr, *out_s = nullptr;
   size_t rows_cap = 0, seg_cap = 0, out_cap = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  size_t bytes = 0;  // device bytes reserved
+  StageMem mem;
 };
 
 inline void topk_release(TopkWork &w) {
-  for (void *p : {(void *)w.cnt, (void *)w.seg_start, (void *)w.out_start, (void *)w.info, (void *)w.seg_c, (void *)w.out_q, (void *)w.out_c,
-                  (void *)w.seg_s, (void *)w.out_s})
-    if (p) (void)hipFree(p);
-  if (w.e0) (void)hipEventDestroy(w.e0);
-  if (w.e1) (void)hipEventDestroy(w.e1);
+  w.mem.free_all({w.cnt, w.seg_start, w.out_start, w.info, w.seg_c, w.out_q, w.out_c, w.seg_s, w.out_s});
   w = TopkWork{};
-}
-
-template <class T>
-inline hipError_t topk_grow(TopkWork &w, T *&p, size_t old_n, size_t n) {
-  if (p) {
-    (void)hipFree(p);  // (synchronises; the pass runs after the call's other work, nothing reads these buffers then)
-    p = nullptr;
-    w.bytes -= old_n * sizeof(T);
-  }
-  const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-  if (e == hipSuccess) w.bytes += n * sizeof(T);
-  return e;
 }
 
 // Runs the pass over (q, c, s)[0, n) on `stream` and waits for it (the one host read: the four info words).  The new list is
@@ -435,36 +419,31 @@ inline hipError_t topk_run(TopkWork &w, hipStream_t stream, const int32_t *q, co
   info->select_launches = 0;
   if (n <= 0 || nq <= 0) return hipSuccess;
   hipError_t e;
-  if (!w.e0 && (e = hipEventCreate(&w.e0)) != hipSuccess) return e;
-  if (!w.e1 && (e = hipEventCreate(&w.e1)) != hipSuccess) return e;
-  if (!w.info) {
-    if ((e = hipMalloc((void **)&w.info, kTopkInfoWords * sizeof(unsigned long long))) != hipSuccess) return e;
-    w.bytes += kTopkInfoWords * sizeof(unsigned long long);
-  }
+  if (!w.info && (e = w.mem.grow(w.info, 0, (size_t)kTopkInfoWords)) != hipSuccess) return e;
   if ((size_t)nq + 1 > w.rows_cap) {
     const size_t cap = std::max<size_t>((size_t)nq + 1, w.rows_cap + w.rows_cap / 2);
-    if ((e = topk_grow(w, w.cnt, w.rows_cap, cap)) != hipSuccess) return e;
-    if ((e = topk_grow(w, w.seg_start, w.rows_cap, cap)) != hipSuccess) return e;
-    if ((e = topk_grow(w, w.out_start, w.rows_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.cnt, w.rows_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.seg_start, w.rows_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_start, w.rows_cap, cap)) != hipSuccess) return e;
     w.rows_cap = cap;
   }
   if ((size_t)n > w.seg_cap) {
     const size_t cap = (size_t)n + (size_t)n / 8 + 1024;
-    if ((e = topk_grow(w, w.seg_c, w.seg_cap, cap)) != hipSuccess) return e;
-    if ((e = topk_grow(w, w.seg_s, w.seg_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.seg_c, w.seg_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.seg_s, w.seg_cap, cap)) != hipSuccess) return e;
     w.seg_cap = cap;
   }
   const size_t out_need = (size_t)std::min<int64_t>(n, nq * (int64_t)k);
   if (out_need > w.out_cap) {
     const size_t cap = out_need + out_need / 8 + 1024;
-    if ((e = topk_grow(w, w.out_q, w.out_cap, cap)) != hipSuccess) return e;
-    if ((e = topk_grow(w, w.out_c, w.out_cap, cap)) != hipSuccess) return e;
-    if ((e = topk_grow(w, w.out_s, w.out_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_q, w.out_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_c, w.out_cap, cap)) != hipSuccess) return e;
+    if ((e = w.mem.grow(w.out_s, w.out_cap, cap)) != hipSuccess) return e;
     w.out_cap = cap;
   }
   const unsigned blocks = (unsigned)((n + kTopkBlock - 1) / kTopkBlock);
   if ((e = hipMemsetAsync(w.cnt, 0, ((size_t)nq + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e;
-  if ((e = hipEventRecord(w.e0, stream)) != hipSuccess) return e;
+  if ((e = begin_timed(stream, w.mem.e0)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_topk_count, dim3(blocks), dim3(kTopkThreads), 0, stream, q, n, (int32_t)nq, w.cnt);
   hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(kTopkScanThreads), 0, stream, w.cnt, (int32_t)nq, k, w.seg_start, w.out_start, w.info,
                      uncut);
@@ -474,12 +453,9 @@ inline hipError_t topk_run(TopkWork &w, hipStream_t stream, const int32_t *q, co
                      (const int64_t *)w.out_start, (const int32_t *)w.seg_c, (const float *)w.seg_s, c_ext, n_store, k, w.out_q, w.out_c,
                      w.out_s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = hipEventRecord(w.e1, stream)) != hipSuccess) return e;
   unsigned long long words[kTopkInfoWords] = {0, 0, 0, 0};
-  if ((e = hipMemcpyAsync(words, w.info, sizeof(words), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
   float ms = 0.f;
-  if ((e = hipEventElapsedTime(&ms, w.e0, w.e1)) != hipSuccess) return e;
+  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.info, sizeof(words)}}, &ms)) != hipSuccess) return e;
   info->kept = (int64_t)words[kTopkKept];
   info->queries_cut = (int64_t)words[kTopkCut];
   info->longest_segment = (int64_t)words[kTopkLongest];

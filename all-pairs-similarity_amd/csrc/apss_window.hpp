@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kWinThreads) void k_win_bound(const int64_t *__rest
     const int32_t t = q_idx[i];
     if (t >= 0 && t < dim) sum += df[t];
   }
-  for (int off = kWinWave / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  sum = wave_sum(sum);
   if (lane == 0) {
     b[q] = (int32_t)(sum < (unsigned long long)stored_rows ? sum : (unsigned long long)stored_rows);
     if (sv_rowptr) {

@@ -305,6 +305,91 @@ def test_query_stored_and_repeated_query_ids(shape_a):
         assert (twins & (got[1][:-1] == got[1][1:])).any()  # a row and its copy, neighbours in rank order
 
 
+# ---- 5b. every stage behind the join at once: removal, per-query cut in windows, global cut; two kinds of call
+ALL_SPLIT, ALL_K, ALL_WINDOW = 1000, 8, 60000
+
+
+def insert_and_query_count(ix, ids, rp, idx, val):
+    """apss_insert_and_query's own n_results (the engine's wrapper fetches instead of returning it)"""
+    import ctypes as C
+    from apss.engine import _ptr
+    ids, rp, idx, val = ix._csr(ids, rp, idx, val)
+    n = C.c_int64(-1)
+    ix._chk(ix._L.apss_insert_and_query(ix._h, ids.size, _ptr(rp), _ptr(idx), _ptr(val), _ptr(ids), C.byref(n)))
+    return n.value
+
+
+def drive_all_stages(ix, a, named):
+    """first 1000 rows stored; then the two calls under test.  Yields after each call"""
+    lo = a["rp"][ALL_SPLIT]
+    ix.insert(a["ext"][:ALL_SPLIT], a["rp"][:ALL_SPLIT + 1], a["idx"][:lo], a["val"][:lo])
+    yield "stored", None
+    yield "insert_and_query", insert_and_query_count(ix, a["ext"][ALL_SPLIT:], a["rp"][ALL_SPLIT:] - lo, a["idx"][lo:], a["val"][lo:])
+    yield "query_stored", ix.query_stored(named, fetch=False)[1]
+
+
+def host_stages(lst, q_ext, c_ext, gone, k):
+    """what the stages make of an unstaged list, on the host, up to the global cut: the removed rows dropped (a removed query row
+    is no row of the batch: the rows after it move up), every query row cut to its k best by (score descending, candidate id,
+    slot).  Returns the list and the live rows' ids"""
+    from helpers import topk
+    q, c, s = lst
+    live = ~np.isin(q_ext, gone)
+    keep = live[q] & ~np.isin(c_ext[c], gone)
+    q, c, s = (np.cumsum(live) - 1)[q[keep]], c[keep], s[keep]
+    out = []
+    for row in np.unique(q):
+        sel = np.nonzero(q == row)[0]
+        best = topk({(int(c_ext[c[i]]), int(c[i])): float(s[i]) for i in sel}, k)
+        out += [(int(row), slot, v) for (_, slot), v in best]
+    cut = (np.array([o[0] for o in out], np.int32), np.array([o[1] for o in out], np.int32), np.array([o[2] for o in out], np.float32))
+    return cut, q_ext[live], int(keep.size - keep.sum())
+
+
+@pytest.fixture(scope="module")
+def all_stages_yardstick(shape_a):
+    """per call: the per-query-cut list a handle with NO stage on leads to, and the ids of its batch's rows"""
+    a = shape_a
+    rng = np.random.Generator(np.random.PCG64(12))
+    gone = a["ext"][:ALL_SPLIT][rng.permutation(ALL_SPLIT)[:100]]
+    distinct = a["ext"][rng.permutation(A_N)[:136]]
+    named = rng.permutation(np.concatenate([distinct, distinct[:32], 9000 + np.arange(32, dtype=np.int64)]))  # 64 repeat or are missing
+    assert named.size == 200 and 0 < np.isin(distinct, gone).sum() < 136
+    cut = {}
+    with ApssIndex(A_DIM, A_THETA, tile_rows=512) as ix:
+        for call, n in drive_all_stages(ix, a, named):
+            if call == "stored":
+                continue
+            full = device_list(ix)
+            assert n == len(full[0]) > 0
+            q_ext = a["ext"][ALL_SPLIT:] if call == "insert_and_query" else a["ext"][np.sort(5000 - np.unique(named[named < 9000]))]
+            cut[call] = host_stages(full, q_ext, a["ext"], gone, ALL_K)
+            assert cut[call][2] > 0  # the removal has pairs to drop
+    return dict(gone=gone, named=named, cut=cut)
+
+
+@pytest.mark.parametrize("K", [7, 1025])
+def test_all_stages_at_once(shape_a, all_stages_yardstick, K):
+    a, y = shape_a, all_stages_yardstick
+    with ApssIndex(A_DIM, A_THETA, tile_rows=512, top_k=ALL_K, top_k_window=ALL_WINDOW, top_pairs=K) as ix:
+        for call, n in drive_all_stages(ix, a, y["named"]):
+            if call == "stored":
+                assert ix.remove(y["gone"]) == 100
+                continue
+            per_query, q_ext, _ = y["cut"][call]
+            want = ranked(per_query, q_ext, a["ext"], K)
+            got, info, wi = device_list(ix), ix.top_pairs_info(), ix.topk_window_info()
+            print("all stages K=%d %s: n=%d windows=%d %s" % (K, call, n, wi["windows"], info))
+            assert_same_list(got, want)
+            assert n == ix.result_count() == len(got[0]) == ix.stats()["result_pairs"] == info["kept"] == min(K, len(per_query[0]))
+            # 500 / 129 or so query rows, each bounded by its terms' 700 or so postings, against 60 000 pairs a window
+            assert wi["windows"] >= 2 and ix.removal_info()["pairs_dropped"] > 0 and ix.topk_info()["k"] == ALL_K
+            if call == "query_stored":
+                qi = ix.stored_query_info()
+                assert (qi["ids_given"], qi["ids_distinct"], qi["rows_selected"]) == (200, 168, len(q_ext))
+                assert qi["ids_missing"] == 168 - len(q_ext)
+
+
 # ---- 6. the setting and the edges
 def test_setting_and_edges(shape_a):
     a = shape_a

@@ -3,12 +3,7 @@ registers: every k_probe_even / k_probe_even_merged instantiation keeps the occu
 per SIMD for all 41 of them, read from the resource remarks of the commit before the loop -- uses no scratch, stays within 128
 VGPRs, and its static LDS still fits the CU's 160 KB twice (512 threads) or once (1024).  hipcc cross-compiles for gfx950
 without a GPU."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "all-pairs-similarity_amd", "csrc")
+import resource_report
 
 # (threads, window steps, shard rule, 8-bit accumulators) of k_probe_even -- signed weights have no instantiation -- and
 # (window steps, 8-bit accumulators) of k_probe_even_merged; waves per SIMD of each in the build before the persistent loop
@@ -22,22 +17,9 @@ for u, a8 in MERGED:
     OCCUPANCY_BEFORE["_ZN4apss19k_probe_even_mergedILi%dELb%dEEEvNS_9ProbeArgsE" % (u, a8)] = 4
 
 
-def test_persistent_loop_keeps_registers_and_occupancy(tmp_path):
+def test_persistent_loop_keeps_registers_and_occupancy():
     assert len(OCCUPANCY_BEFORE) == 41
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "k.s"),
-                          os.path.join(CSRC, "apss_hip.hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    cur, res = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-        for key in ("VGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
-            m = re.search(r"\s%s: (\d+)" % key, line)
-            if m and cur:
-                res[cur][key.split(" ")[0]] = int(m.group(1))
+    res = resource_report.report()
     even = {k: v for k, v in res.items() if "k_probe_even" in k}
     assert set(even) == set(OCCUPANCY_BEFORE), set(even) ^ set(OCCUPANCY_BEFORE)
     for name, r in sorted(even.items()):

@@ -2,10 +2,10 @@
 Same compile step as tests/test_topk_window_resources.py (hipcc cross-compiles for gfx950 without a GPU)."""
 import os
 import re
-import subprocess
+
+import resource_report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "all-pairs-similarity_amd", "csrc")
 
 # kernel -> (VGPRs at most, LDS bytes per workgroup at most, waves per SIMD at least): DESIGN.md 5f, the plan's column
 STATED = {
@@ -16,21 +16,8 @@ STATED = {
 }
 
 
-def test_removal_kernels_meet_their_stated_resources(tmp_path):
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "k.s"),
-                          os.path.join(CSRC, "apss_hip.hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    cur, res = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-        for key in ("VGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
-            m = re.search(r"\s%s: (\d+)" % key, line)
-            if m and cur:
-                res[cur][key.split(" ")[0]] = int(m.group(1))
+def test_removal_kernels_meet_their_stated_resources():
+    res = resource_report.report()
     found = set()
     for name, r in res.items():
         if "k_rm_" not in name:

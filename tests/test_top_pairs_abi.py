@@ -99,7 +99,9 @@ def test_every_binding_carries_the_feature():
     actor = open(os.path.join(PKG, "jvm", "GpuIndexingWorkerActor.scala")).read()
     assert "cpslab.allpair.gpu.topPairs" in actor and "NativeApss.setTopPairs(handle, topPairs)" in actor
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert mk.count("apss_top_pairs.hpp") == 2  # the object's and the assembly's dependency lists
+    # the object's and the assembly's dependency lists: both name the one header list, and the header is in it
+    assert "apss_top_pairs.hpp" in re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    assert all("$(HDRS)" in re.search(r"^%s:(.*)$" % rule, mk, re.M).group(1).split() for rule in (r"apss_hip\.o", "asm"))
     for doc in ("README.md", "INTEGRATION.md", "DESIGN.md"):
         text = open(os.path.join(ROOT, doc)).read()
         assert "apss_set_top_pairs" in text, doc

@@ -3,10 +3,10 @@ with no scratch.  Same compile step as tests/test_query_stored_resources.py (hip
 rows are read from the document."""
 import os
 import re
-import subprocess
+
+import resource_report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "all-pairs-similarity_amd", "csrc")
 KERNELS = ("k_tp_hist", "k_tp_pick", "k_tp_collect", "k_tp_tie_hist", "k_tp_tie_collect", "k_tp_keys", "k_tp_write")
 
 
@@ -21,23 +21,10 @@ def stated_rows():
     return rows
 
 
-def test_top_pairs_kernels_meet_their_stated_resources(tmp_path):
+def test_top_pairs_kernels_meet_their_stated_resources():
     stated = stated_rows()
     assert set(stated) == set(KERNELS), stated
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "k.s"),
-                          os.path.join(CSRC, "apss_hip.hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    cur, res = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-        for key in ("VGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]", "LDS Size \\[bytes/block\\]"):
-            m = re.search(r"\s%s: (\d+)" % key, line)
-            if m and cur:
-                res[cur][key.split(" ")[0]] = int(m.group(1))
+    res = resource_report.report()
     found = set()
     for name, r in res.items():
         m = re.search(r"\d+(k_tp_[a-z_]+?)E", name)  # the mangled name holds the kernel's own, length first

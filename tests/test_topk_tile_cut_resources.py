@@ -3,30 +3,17 @@ them -- no scratch, at most 128 VGPRs, four waves per SIMD -- and the instantiat
 registers they had before the cut existed.  Same compile step as tests/test_topk_resources.py."""
 import os
 import re
-import subprocess
+
+import resource_report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "all-pairs-similarity_amd", "csrc")
 
 # k_probe<2, BLOCK, FX> without the cut: VGPRs of the commit before the cut was added (DESIGN.md 5e, "Cut inside the probe")
 BEFORE = {(512, True): 113, (1024, True): 113, (512, False): 110, (1024, False): 109}
 
 
-def test_cut_instantiations_meet_their_stated_resources(tmp_path):
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "k.s"),
-                          os.path.join(CSRC, "apss_hip.hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    cur, res = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-        for key in ("VGPRs", "ScratchSize \\[bytes/lane\\]", "Occupancy \\[waves/SIMD\\]"):
-            m = re.search(r"\s%s: (\d+)" % key, line)
-            if m and cur:
-                res[cur][key.split(" ")[0]] = int(m.group(1))
+def test_cut_instantiations_meet_their_stated_resources():
+    res = resource_report.report()
     cut, plain = {}, {}
     for name, r in res.items():
         m = re.fullmatch(r"_ZN4apss7k_probeILi2ELi(\d+)ELb([01])ELb([01])EEEvNS_9ProbeArgsE", name)
