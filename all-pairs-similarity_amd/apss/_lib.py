@@ -37,6 +37,8 @@ SYMBOLS = [
     "apss_query_stored", "apss_query_stored_dev", "apss_stored_query_get",
     # the global top-K of a call (csrc/apss_top_pairs.hpp)
     "apss_set_top_pairs", "apss_top_pairs_get",
+    # near-duplicate groups: the connected components of the join (csrc/apss_components.hpp)
+    "apss_set_components", "apss_components_get", "apss_components_dev", "apss_components_fetch",
 ]
 TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
 TILE_CUT_REMOVED = 4
@@ -47,6 +49,7 @@ GROUP_MAX_MEMBERS = 64
 DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
 TOP_K_MAX = 1024
 TOP_PAIRS_MAX = 1 << 20
+CC_RAN, CC_OFF, CC_OUTSIDE, CC_TILE_CUT = 0, 1, 2, 3
 SYM_RAN, SYM_FLAG, SYM_NOT_WHOLE, SYM_PATH, SYM_LONG_ROWS, SYM_ONE_TILE, SYM_CHUNK = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -129,6 +132,14 @@ class TopPairsInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("launches", C.c_int32), ("k_pairs", C.c_int64), ("pairs_in", C.c_int64),
                 ("kept", C.c_int64), ("above", C.c_int64), ("tied", C.c_int64), ("tied_kept", C.c_int64),
                 ("kth_score", C.c_double), ("select_ms", C.c_double)]
+
+
+class ComponentsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("on", C.c_int32), ("complete", C.c_int32), ("declined", C.c_int32),
+                ("rows", C.c_int64), ("rows_live", C.c_int64), ("components", C.c_int64), ("singletons", C.c_int64),
+                ("largest", C.c_int64), ("pairs_absorbed", C.c_int64), ("unions_total", C.c_int64), ("resets", C.c_int64),
+                ("hook_ms", C.c_double), ("label_ms", C.c_double), ("hook_launches", C.c_int32), ("label_launches", C.c_int32),
+                ("reserved", C.c_int64)]
 
 
 def build_sources():
@@ -313,5 +324,13 @@ def lib():
     L.apss_set_top_pairs.argtypes = [vp, i64]
     L.apss_top_pairs_get.restype = i32
     L.apss_top_pairs_get.argtypes = [vp, C.POINTER(TopPairsInfo)]
+    L.apss_set_components.restype = i32
+    L.apss_set_components.argtypes = [vp, i32]
+    L.apss_components_get.restype = i32
+    L.apss_components_get.argtypes = [vp, C.POINTER(ComponentsInfo)]
+    L.apss_components_dev.restype = i32
+    L.apss_components_dev.argtypes = [vp, C.POINTER(vp), pi64]
+    L.apss_components_fetch.restype = i32
+    L.apss_components_fetch.argtypes = [vp, i64, i64, vp, vp]
     _lib = L
     return L

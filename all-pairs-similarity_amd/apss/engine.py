@@ -27,7 +27,7 @@ def _ptr(a):
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
                  capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False,
-                 auto_compact=0.0, top_pairs=0):
+                 auto_compact=0.0, top_pairs=0, components=False):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -48,7 +48,8 @@ class ApssIndex:
         self._h = h
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
-        if top_k or top_k_window or top_k_tile_cut or auto_compact or top_pairs:
+        self._device = int(device)
+        if top_k or top_k_window or top_k_tile_cut or auto_compact or top_pairs or components:
             try:
                 if auto_compact:
                     self.set_auto_compact(auto_compact)
@@ -60,6 +61,8 @@ class ApssIndex:
                     self.set_top_k(top_k)
                 if top_pairs:
                     self.set_top_pairs(top_pairs)
+                if components:
+                    self.set_components(True)
             except ApssError:
                 self.close()
                 raise
@@ -252,6 +255,40 @@ class ApssIndex:
         ti.struct_size = C.sizeof(_lib.TopPairsInfo)
         self._chk(self._L.apss_top_pairs_get(self._h, C.byref(ti)))
         return {k: getattr(ti, k) for k, _ in _lib.TopPairsInfo._fields_}
+
+    def set_components(self, on):
+        """near-duplicate groups (apss_set_components): on = the connected components of the graph "stored row - stored row, edge =
+        a pair of a call's final list" are kept on the device across calls; off (the default) frees them"""
+        self._chk(self._L.apss_set_components(self._h, 1 if on else 0))
+
+    def components_info(self):
+        """the structure's state and what the last calls did to it (apss_components_info); brings the labels up to date"""
+        ci = _lib.ComponentsInfo()
+        ci.struct_size = C.sizeof(_lib.ComponentsInfo)
+        self._chk(self._L.apss_components_get(self._h, C.byref(ci)))
+        return {k: getattr(ci, k) for k, _ in _lib.ComponentsInfo._fields_}
+
+    def components(self, offset=0, count=None):
+        """(labels int32, rep_ext int64) of the slots [offset, offset + count) (default: all): the smallest slot of every slot's
+        component and that slot's external id; a removed row: -1 and its own id (apss_components_fetch)"""
+        if count is None:
+            count = self.size()[0] - offset
+        labels, rep = np.zeros(max(count, 0), np.int32), np.zeros(max(count, 0), np.int64)
+        self._chk(self._L.apss_components_fetch(self._h, int(offset), int(count), _ptr(labels), _ptr(rep)))
+        return labels, rep
+
+    def components_dev(self):
+        """the labels where they live: an int32 torch tensor over the device array, no copy (apss_components_dev; valid until the
+        next insert, query-type call, remove, compact, clear or set_components)"""
+        import torch
+        p, rows = C.c_void_p(), C.c_int64(0)
+        self._chk(self._L.apss_components_dev(self._h, C.byref(p), C.byref(rows)))
+        if not rows.value:
+            return torch.empty(0, dtype=torch.int32, device="cuda:%d" % self._device)
+
+        class _View:  # (torch reads the array interface: the tensor aliases the handle's memory)
+            __cuda_array_interface__ = {"shape": (rows.value,), "typestr": "<i4", "data": (p.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_View(), device="cuda:%d" % self._device)
 
     def set_head_terms(self, terms, part=0, n_parts=1, fold_columns=0):
         """dense-head block named by the caller (every term shard of a join gets the same terms; shard `part` of `n_parts`

@@ -26,6 +26,7 @@
 #include "apss_remove.hpp"
 #include "apss_query_stored.hpp"
 #include "apss_top_pairs.hpp"
+#include "apss_components.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -124,6 +125,7 @@ struct DebugCfg {
   int rm_grid = 0;             // rm_grid=N      at most N workgroups for k_rm_mark, k_rm_drop and k_rm_rows (tests of their grid-stride loops; default 4096 / 16384 / 4096),
                                //                and for k_qs_select, k_qs_ids and k_qs_slots (apss_query_stored.hpp; default 4096 each)
   int tp_grid = 0;             // tp_grid=N      at most N workgroups for the grid-stride kernels of the global top-K (apss_top_pairs.hpp; default kTpGridCap)
+  int cc_grid = 0;             // cc_grid=N      at most N workgroups for k_cc_hook (apss_components.hpp; default kCcGridCap): a small list takes its loop's later trips
 };
 
 DebugCfg parse_debug_env() {
@@ -185,6 +187,7 @@ DebugCfg parse_debug_env() {
     else if (key == "persist_fine") d.persist_fine = val;
     else if (key == "rm_grid") d.rm_grid = val;
     else if (key == "tp_grid") d.tp_grid = val;
+    else if (key == "cc_grid") d.cc_grid = val;
     else if (key == "relayout_fail") {}  // (read by apss_group_create: a group's re-layout hook, nothing of a handle's)
     else if (!key.empty()) fprintf(stderr, "[apss] unknown APSS_DEBUG token '%s' ignored\n", key.c_str());
   }
@@ -202,6 +205,7 @@ struct PinScalars {
   alignas(512) unsigned long long removal_kept;            // pairs k_rm_drop kept
   alignas(128) int64_t stored_back[4];                     // apss_query_stored: the two scan totals, the two id counters
   alignas(128) unsigned long long top_pairs[kTpWords];     // the global top-K's state words
+  alignas(128) unsigned long long components[kCcWords];    // apss_set_components: unions, components, singletons, largest
 };
 static_assert(sizeof(PinScalars) <= kPinScalars, "the scalar slots end inside the pinned reservation");
 static_assert(offsetof(PinScalars, chain_ctr) == 128 && offsetof(PinScalars, attempt_ctr) == 256 && offsetof(PinScalars, removal_kept) == 512 &&
@@ -403,6 +407,11 @@ struct apss_handle {
   int64_t top_pairs = 0;
   TpWork tp;
   apss_top_pairs_info tpi{};
+  // components of the join (apss_components.hpp): the setting, the forest and its labels, what the last calls did (cci.on,
+  // cci.complete, cci.resets are the structure's state; rows, the counts and unions_total are filled at a labelling)
+  bool cc_on = false;
+  CcWork cc;
+  apss_components_info cci{};
   // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
@@ -1300,9 +1309,11 @@ struct QueryBatch : QueryRows {
   int64_t slot_first, max_nnz;
   float max_norm2;
   int64_t nnz_end;
+  const int32_t *slots = nullptr;  // [nq] the slot of every row where the batch is a SELECTION of stored rows (apss_query_stored), else NULL
   // rows [r0, r1) as a batch of their own (a window): the offsets stay absolute
   QueryBatch rows(int64_t r0, int64_t r1) const {
-    return QueryBatch{{r1 - r0, rowptr + r0, idx, val, ext + r0}, slot_first < 0 ? -1 : slot_first + r0, max_nnz, max_norm2, nnz_end};
+    return QueryBatch{{r1 - r0, rowptr + r0, idx, val, ext + r0}, slot_first < 0 ? -1 : slot_first + r0, max_nnz, max_norm2, nnz_end,
+                      slots ? slots + r0 : nullptr};
   }
 };
 
@@ -3094,10 +3105,65 @@ int32_t drop_removed(apss_handle *h, int64_t q_slot_first) {
   return APSS_OK;
 }
 
+// ---- components of the join (apss_components.hpp) ----
+// every slot a singleton again and complete as an un-joined store is: nothing is launched (cc_extend initialises the slots when the
+// structure is next used).  counted: a reset the caller did not ask for (removal, compaction, a failed stage)
+void reset_components(apss_handle *h, bool counted) {
+  cc_reset(h->cc);
+  h->cci.complete = h->n_rows == 0;
+  if (counted) ++h->cci.resets;
+}
+
+// one launch sequence of the stage: the reservation follows it, a failure leaves the structure reset
+template <class F>
+int32_t components_stage(apss_handle *h, F fn) {
+  const int32_t rc = run_stage(h, "components", h->cc.mem, [&](const char **) { return fn(); });
+  if (rc != APSS_OK) reset_components(h, true);
+  return rc;
+}
+
+// The list of `batch` (the call's, or one window's) behind the removal filter goes into the forest: launches only.  probe() has
+// said whether the batch is rows of the store
+int32_t absorb_components(apss_handle *h, const QueryBatch &batch) {
+  if (h->cci.declined != APSS_CC_RAN) return APSS_OK;
+  if (h->cut_ran) {  // (the probe cut its rounds: what it left is not every pair)
+    h->cci.declined = APSS_CC_TILE_CUT;
+    return APSS_OK;
+  }
+  if (h->n_res <= 0) return APSS_OK;
+  APSS_TRY(components_stage(h, [&] {
+    return cc_hook(h->cc, h->stream, h->out_q, h->out_c, h->n_res, batch.slot_first, batch.slots, batch.nq, h->n_rows,
+                   h->dbgcfg.cc_grid > 0 ? h->dbgcfg.cc_grid : kCcGridCap, &h->cci.hook_launches, &h->cci.hook_ms);
+  }));
+  h->cci.pairs_absorbed += h->n_res;
+  return APSS_OK;
+}
+
+// label[] and the counts are those of parent[] (the lazy half of the stage: ONE synchronisation when something changed)
+int32_t label_components(apss_handle *h) {
+  h->cci.label_launches = 0;
+  if (!h->cc.dirty && h->cci.rows == h->n_rows) return APSS_OK;
+  const bool marks = h->rm_marked > 0 && h->dead.p;
+  unsigned long long *w = h->scalars->components;
+  APSS_TRY(components_stage(h, [&] {
+    return cc_label(h->cc, h->stream, h->n_rows, marks ? h->dead.p : nullptr, marks ? h->dead_rows : 0, w, &h->cci.label_launches, &h->cci.label_ms,
+                    &h->cci.hook_ms);
+  }));
+  h->cci.rows = h->n_rows;
+  h->cci.rows_live = h->n_rows - h->rm_marked;
+  h->cci.unions_total = (int64_t)w[0];
+  h->cci.components = (int64_t)w[1];
+  h->cci.singletons = (int64_t)w[2];
+  h->cci.largest = (int64_t)w[3];
+  return APSS_OK;
+}
+
 // What the join of `batch` (the call's, or one window's) left, finished: while rows are marked removed, ONE filter of that list
-// (apss_remove.hpp); then, with apss_set_top_k, ONE pass of the per-query top-k over it (apss_topk.hpp), reported in *info.
+// (apss_remove.hpp); then, with apss_set_components, the list's pairs hooked into the components (apss_components.hpp: launches
+// only); then, with apss_set_top_k, ONE pass of the per-query top-k over it (apss_topk.hpp), reported in *info.
 int32_t finish_list(apss_handle *h, const QueryBatch &batch, apss_topk_info *info) {
   APSS_TRY(drop_removed(h, batch.slot_first));
+  if (h->cc_on) APSS_TRY(absorb_components(h, batch));
   info->pairs_over_theta = info->kept = h->n_res;
   if (h->top_k <= 0 || h->sharded) return APSS_OK;
   return cut_final_list(h, batch.nq, info);
@@ -3241,6 +3307,13 @@ QueryBatch store_batch(const apss_handle *h) {
 int32_t probe(apss_handle *h, const QueryBatch &batch, int64_t *n_results) {
   h->tpi = apss_top_pairs_info{};
   h->tpi.k_pairs = h->top_pairs;
+  if (h->cc_on) {  // (finish_list absorbs the list, or every window's, when the batch is rows of the store)
+    h->cci.declined = batch.slot_first < 0 && !batch.slots && batch.nq > 0 ? APSS_CC_OUTSIDE : APSS_CC_RAN;
+    h->cci.pairs_absorbed = 0;
+    h->cci.hook_launches = 0;
+    h->cci.hook_ms = 0;
+    h->cc.hook_open = false;
+  }
   APSS_TRY(probe_lists(h, batch, n_results));
   if (h->top_pairs > 0 && !h->sharded) APSS_TRY(cut_top_pairs(h, batch));
   if (n_results) *n_results = h->n_res;
@@ -3330,6 +3403,7 @@ int32_t insert_dev_impl(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d
   const int64_t row0 = h->n_rows;
   h->n_rows += kept_rows;
   h->nnz += kept_nnz;
+  if (h->cc_on && kept_rows > 0) h->cci.complete = 0;  // (new slots, singletons once the structure is next used; their edges were never seen)
   // a small batch onto an existing index waits in the TAIL (k_tail_score scores it directly) until the tail is worth a
   // rebuild of the last tile: a single-vector message then costs no pass over the dim-wide segment table
   const bool tail_ok = h->use_coarse && !h->sharded && h->idx_rows > 0 && !h->dbgcfg.no_tail;
@@ -3413,6 +3487,7 @@ int32_t clear_impl(apss_handle *h) {
   h->df_rows = -1;
   h->rm_marked = 0;  // (the marks belong to slots, and the slots are gone)
   h->dead_rows = 0;
+  if (h->cc_on) reset_components(h, false);  // (the setting stays, the structure is empty: complete)
   return APSS_OK;
 }
 
@@ -3453,6 +3528,7 @@ int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *ne
   h->rm_marked += (int64_t)marked;
   h->ri.removed_total += (int64_t)marked;
   *newly = (int64_t)marked;
+  if (h->cc_on && marked > 0) reset_components(h, true);  // (a removed row can split a component)
   return APSS_OK;
 }
 
@@ -3504,6 +3580,7 @@ int32_t compact_impl(apss_handle *h) {
   h->ri.compact_ms = ms;
   h->ri.compacted_rows = marked;
   ++h->ri.compactions;
+  if (h->cc_on) reset_components(h, true);  // (the slots shifted: clear_impl emptied the structure, the insert made it incomplete)
   return APSS_OK;
 }
 
@@ -3623,7 +3700,9 @@ int32_t query_stored_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64
   h->q_max_nnz = 0;
   h->q_max_norm2 = 0.f;
   if (sel_rows > 0) APSS_TRY(gather_stored_rows(h, sel_rows, sel_nnz));
-  return probe(h, QueryBatch{{sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz}, n_results);
+  // (qs_slots: the slot of every selected row -- what the components stage maps the batch's rows with)
+  return probe(h, QueryBatch{{sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz,
+                             sel_rows > 0 ? h->qs_slots.p : nullptr}, n_results);
 }
 
 int32_t check_stored_query(apss_handle *h, const char *what, int64_t n, const int64_t *ids, int64_t *n_rows, int64_t *n_results) {
@@ -3753,6 +3832,7 @@ void apss_destroy(apss_handle *h) {
   release(h->head_ctr); h->uq.release(); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
   topk_release(h->topk);
   tp_release(h->tp);
+  cc_release(h->cc);
   release(h->win_df); release(h->win_b); h->win.release();
   release(h->row_pairs);
   release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
@@ -3806,7 +3886,14 @@ int32_t apss_insert_and_query(apss_handle *h, int64_t n, const int64_t *rowptr, 
 int32_t apss_self_join(apss_handle *h, int64_t *n_results) {
   APSS_TRY(enter(h));
   if (h->idx_rows < h->n_rows) APSS_TRY(build_index(h, h->idx_rows));  // a self-join runs over the index: fold the tail in
-  return probe(h, store_batch(h), n_results);
+  if (!h->cc_on) return probe(h, store_batch(h), n_results);
+  // the components of the join: the call's list is every edge there is, so the structure starts over and ends complete -- unless
+  // the probe cut its rounds (APSS_CC_TILE_CUT), which leaves singletons
+  reset_components(h, false);
+  const int32_t rc = probe(h, store_batch(h), n_results);
+  if (rc == APSS_OK && h->cci.declined == APSS_CC_RAN) h->cci.complete = 1;
+  else if (rc == APSS_OK) reset_components(h, false);
+  return rc;
 }
 
 int32_t apss_result_count(const apss_handle *h, int64_t *n_results) {
@@ -3942,9 +4029,13 @@ int32_t apss_insert_and_query_dev(apss_handle *h, int64_t n, int64_t nnz, const 
     return fail(h, APSS_E_INVALID, "null device pointer");
   APSS_TRY(auto_compact(h));
   int64_t first = 0;
+  const int32_t cc_complete = h->cci.complete;
   APSS_TRY(insert_dev_impl(h, n, nnz, d_rowptr, d_indices, d_values, d_ext_ids, &first));
   // the batch is now rows [first, n_rows) of the store: query it in place (rowptr offsets are absolute)
-  return probe(h, store_batch(h).rows(first, h->n_rows), n_results);
+  const int32_t rc = probe(h, store_batch(h).rows(first, h->n_rows), n_results);
+  // (the call reported every pair between its rows and everything stored: the components are as complete as they were)
+  if (h->cc_on && rc == APSS_OK && h->cci.declined == APSS_CC_RAN) h->cci.complete = cc_complete;
+  return rc;
 }
 
 int32_t apss_clear(apss_handle *h) {
@@ -4042,6 +4133,80 @@ int32_t apss_top_pairs_get(apss_handle *h, apss_top_pairs_info *out) {
   const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_top_pairs_info));
   h->tpi.struct_size = n;
   std::memcpy(out, &h->tpi, (size_t)n);
+  return APSS_OK;
+}
+
+int32_t apss_set_components(apss_handle *h, int32_t on) {
+  if (!h) return APSS_E_INVALID;
+  // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
+  if (on != 0 && on != 1) return fail(h, APSS_E_INVALID, g_create_error = "apss_set_components: on must be 0 or 1");
+  if (on && h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_components: a term shard reports candidates with partial scores; it has no final list whose pairs are edges");
+  if (!on) {
+    if (h->cc_on) {
+      APSS_TRY(enter(h));
+      HIPCHK(h, hipStreamSynchronize(h->stream));  // (a hook may still be running on the arrays)
+      h->bytes_reserved -= h->cc.mem.bytes;
+      cc_release(h->cc);
+    }
+    h->cc_on = false;
+    const int64_t resets = h->cci.resets;
+    h->cci = apss_components_info{};
+    h->cci.resets = resets;
+    return APSS_OK;
+  }
+  h->cc_on = true;
+  h->cci.on = 1;
+  h->cci.declined = APSS_CC_RAN;
+  reset_components(h, false);
+  return APSS_OK;
+}
+
+int32_t apss_components_get(apss_handle *h, apss_components_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_components_info.struct_size must be set to sizeof(apss_components_info) before the call");
+  if (h->cc_on) {
+    APSS_TRY(enter(h));
+    APSS_TRY(label_components(h));
+  } else {
+    h->cci.declined = APSS_CC_OFF;
+  }
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_components_info));
+  h->cci.struct_size = n;
+  std::memcpy(out, &h->cci, (size_t)n);
+  return APSS_OK;
+}
+
+int32_t apss_components_dev(apss_handle *h, const int32_t **d_label, int64_t *rows) {
+  APSS_TRY(enter(h));
+  if (!h->cc_on) return fail(h, APSS_E_STATE, "apss_components_dev: the setting is off (apss_set_components)");
+  APSS_TRY(label_components(h));
+  if (d_label) *d_label = h->n_rows > 0 ? h->cc.label : nullptr;
+  if (rows) *rows = h->n_rows;
+  return APSS_OK;
+}
+
+int32_t apss_components_fetch(apss_handle *h, int64_t offset, int64_t count, int32_t *out_label, int64_t *out_rep_ext) {
+  APSS_TRY(enter(h));
+  if (!h->cc_on) return fail(h, APSS_E_STATE, "apss_components_fetch: the setting is off (apss_set_components)");
+  if (offset < 0 || count < 0 || offset > h->n_rows || count > h->n_rows - offset) return fail(h, APSS_E_INVALID, "apss_components_fetch: a range outside [0, rows]");
+  APSS_TRY(label_components(h));
+  if (count == 0 || (!out_label && !out_rep_ext)) return APSS_OK;
+  if (out_rep_ext) {  // the ids are gathered through the handle's small staging buffer, a piece at a time (stream order keeps the pieces apart)
+    APSS_TRY(ensure(h, h->pack, kPinBytes));
+    const int64_t piece = (int64_t)(kPinBytes / sizeof(int64_t));
+    for (int64_t at = 0; at < count; at += piece) {
+      const int64_t n = std::min(piece, count - at);
+      hipLaunchKernelGGL(k_cc_rep, dim3(cc_grid(n, kCcGridCap)), dim3(kCcThreads), 0, h->stream, (const int32_t *)h->cc.label, (const int64_t *)h->ext.p,
+                         offset + at, n, h->n_rows, reinterpret_cast<int64_t *>(h->pack.p));
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipMemcpyAsync(out_rep_ext + at, h->pack.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  if (out_label) HIPCHK(h, hipMemcpyAsync(out_label, h->cc.label + offset, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return APSS_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <random>
 #include <sstream>
+#include <unordered_set>
 
 #include "../../include/apss.h"
 
@@ -237,6 +238,10 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
       last_error_ = "cpslab.allpair.gpu.topPairs ignored: a term-sharded worker has no global top-K (apss_set_top_pairs: plain handles only)";
       conf_.topPairs = 0;
     }
+    if (conf.components) {  // a group's list lies behind its exchange: no stage there
+      last_error_ = "cpslab.allpair.gpu.components ignored: a term-sharded worker keeps no components (apss_set_components: plain handles only)";
+      conf_.components = false;
+    }
     return;
   }
   if (conf.devices.size() == 1) c.device_id = conf.devices[0];
@@ -266,6 +271,12 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
     h_ = nullptr;
     throw std::runtime_error(msg);
   }
+  if (conf.components && apss_set_components(h_, 1) != APSS_OK) {
+    const std::string msg = std::string("apss_set_components: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
   if (conf.autoCompact != 0.0 && apss_set_auto_compact(h_, conf.autoCompact) != APSS_OK) {
     const std::string msg = std::string("apss_set_auto_compact: ") + apss_last_error(h_);
     apss_destroy(h_);
@@ -289,6 +300,11 @@ int64_t GpuIndexingWorker::remove(const std::vector<std::string> &ids) {
     last_error_ = std::string("apss_remove: ") + apss_last_error(h_);
     return -1;
   }
+  if (conf_.components && removed > 0) {  // (every live slot under one of the ids is marked: apss_remove)
+    const std::unordered_set<int64_t> gone(ext.begin(), ext.end());
+    for (size_t s = 0; s < slot_id_.size(); ++s)
+      if (gone.count(slot_id_[s])) slot_dead_[s] = 1;
+  }
   return removed;
 }
 
@@ -301,7 +317,46 @@ bool GpuIndexingWorker::compact() {
     last_error_ = std::string("apss_compact: ") + apss_last_error(h_);
     return false;
   }
+  drop_dead_slots();
   return true;
+}
+
+int64_t GpuIndexingWorker::compactions() const {
+  apss_removal_info ri{};
+  ri.struct_size = (int32_t)sizeof(ri);
+  return h_ && apss_removal_get(h_, &ri) == APSS_OK ? ri.compactions : 0;
+}
+
+// a compaction moved the live rows to the front, in slot order
+void GpuIndexingWorker::drop_dead_slots() {
+  size_t live = 0;
+  for (size_t s = 0; s < slot_id_.size(); ++s)
+    if (!slot_dead_[s]) slot_id_[live++] = slot_id_[s];
+  slot_id_.resize(live);
+  slot_dead_.assign(live, 0);
+}
+
+std::unordered_map<std::string, std::string> GpuIndexingWorker::groups() {
+  std::unordered_map<std::string, std::string> out;
+  if (g_ || !conf_.components) {
+    last_error_ = g_ ? "groups: a term-sharded worker keeps no components (cpslab.allpair.gpu.devices with one entry)"
+                     : "groups: cpslab.allpair.gpu.components is off";
+    return out;
+  }
+  const int64_t rows = storedVectors();
+  if (!slots_known_ || rows != (int64_t)slot_id_.size()) {
+    last_error_ = "groups: the store holds other rows than the worker sent (a vector was not admitted)";
+    return out;
+  }
+  std::vector<int32_t> label((size_t)rows);
+  std::vector<int64_t> rep((size_t)rows);
+  if (apss_components_fetch(h_, 0, rows, label.data(), rep.data()) != APSS_OK) {
+    last_error_ = std::string("apss_components_fetch: ") + apss_last_error(h_);
+    return out;
+  }
+  for (int64_t s = 0; s < rows; ++s)
+    if (label[(size_t)s] >= 0) out[name_of_[(size_t)slot_id_[(size_t)s]]] = name_of_[(size_t)rep[(size_t)s]];
+  return out;
 }
 
 SimilarityOutput GpuIndexingWorker::similarTo(const std::vector<std::string> &ids) {
@@ -380,6 +435,8 @@ SimilarityOutput GpuIndexingWorker::handle(const IndexData &m) {
   }
   int64_t n_res = 0;
   const int64_t n = (int64_t)ids.size();
+  const bool track = conf_.components && !g_ && !stop_update_index_;  // (groups(): which id went to which slot)
+  const int64_t rows_before = track ? storedVectors() : 0, compactions_before = track ? compactions() : 0;
   int32_t rc;
   if (g_)
     rc = stop_update_index_  // IndexingWorkerActor.scala:125-133
@@ -389,6 +446,17 @@ SimilarityOutput GpuIndexingWorker::handle(const IndexData &m) {
     rc = stop_update_index_
              ? apss_query(h_, n, rowptr.data(), idx.data(), val.data(), ids.data(), &n_res)
              : apss_insert_and_query(h_, n, rowptr.data(), idx.data(), val.data(), ids.data(), &n_res);
+  if (track) {
+    const bool compacted = compactions() > compactions_before;  // (apss_set_auto_compact, before the batch was stored)
+    if (compacted) drop_dead_slots();
+    const int64_t expect = (compacted ? (int64_t)slot_id_.size() : rows_before) + (rc == APSS_OK ? n : 0);
+    if (storedVectors() == expect && rc == APSS_OK) {
+      slot_id_.insert(slot_id_.end(), ids.begin(), ids.end());
+      slot_dead_.resize(slot_id_.size(), 0);
+    } else if (storedVectors() != (int64_t)slot_id_.size()) {
+      slots_known_ = false;
+    }
+  }
   if (rc != APSS_OK) throw std::runtime_error(g_ ? apss_group_last_error(g_) : apss_last_error(h_));
   std::vector<int64_t> q((size_t)n_res), c((size_t)n_res);
   std::vector<float> s((size_t)n_res);

@@ -113,6 +113,10 @@ struct Config {
   // descending, query id, candidate id ascending) -- apss_set_top_pairs, the global cut behind topK's per-query one.  A bad value
   // fails construction, as a refused topK does; a term-sharded worker has no such cut: reported through lastError(), it runs with 0
   long topPairs = 0;
+  // cpslab.allpair.gpu.components: false (default) = off; true = the worker keeps the near-duplicate groups of everything it holds
+  // -- the connected components of the graph whose edges are the pairs of its replies -- on the device (apss_set_components) and
+  // GpuIndexingWorker::groups() reads them.  A term-sharded worker has none: reported through lastError(), it runs without
+  bool components = false;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.
@@ -142,6 +146,11 @@ class GpuIndexingWorker {
   // vector's stays empty); nothing is inserted.  Unknown names are ignored.  A term-sharded worker refuses: an empty reply and
   // lastError()
   SimilarityOutput similarTo(const std::vector<std::string> &ids);
+  // The near-duplicate groups (cpslab.allpair.gpu.components): for every live stored String id, the id of its group's
+  // representative -- the member stored first.  A vector similar to nothing represents itself.  Every IndexData the worker
+  // inserted has been absorbed, so the groups are those of all it holds (until a removal starts them over: apss.h).  Empty and
+  // lastError() when the setting is off or the worker is term-sharded
+  std::unordered_map<std::string, std::string> groups();
   const std::string &lastError() const { return last_error_; }
 
  private:
@@ -153,6 +162,12 @@ class GpuIndexingWorker {
   bool stop_update_index_ = false;
   std::unordered_map<std::string, int64_t> id_of_;  // String id <-> the ABI's int64 handle
   std::vector<std::string> name_of_;
+  // (groups() only) the ABI id and the removal mark of every store slot, in slot order: the library labels slots
+  std::vector<int64_t> slot_id_;
+  std::vector<char> slot_dead_;
+  bool slots_known_ = true;  // false once the store's row count disagreed with what the worker sent
+  int64_t compactions() const;
+  void drop_dead_slots();
   std::unordered_map<std::string, std::unordered_map<std::string, double>> write_buffer_;  // :27, 113-120
   std::string last_error_;
 };

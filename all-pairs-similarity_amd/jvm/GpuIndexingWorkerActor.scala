@@ -80,6 +80,20 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.topPairs needs one GPU (cpslab.allpair.gpu.devices with one entry); running with 0")
   if (!grouped && topPairs != 0L)
     require(NativeApss.setTopPairs(handle, topPairs) == 0, NativeApss.lastError(handle))
+  // cpslab.allpair.gpu.components = true (default false: off; one GPU only): the near-duplicate groups of everything the worker
+  // holds -- the connected components of the graph whose edges are the pairs of its replies -- are kept on the device
+  // (apss_set_components) and read with NativeApss.components(handle).  With several GPUs the worker says so and runs without
+  private val components =
+    conf.hasPath("cpslab.allpair.gpu.components") && conf.getBoolean("cpslab.allpair.gpu.components")
+  if (grouped && components)
+    System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.components needs one GPU (cpslab.allpair.gpu.devices with one entry); running without")
+  if (!grouped && components)
+    require(NativeApss.setComponents(handle, true) == 0, NativeApss.lastError(handle))
+  /** the near-duplicate groups: for every store slot (smallest slot of its component | -1 for a withdrawn vector, the name of the
+    * vector in that slot); null when cpslab.allpair.gpu.components is off */
+  def groups(): (Array[Int], Array[String]) =
+    if (grouped || !components) null
+    else Option(NativeApss.components(handle)).map { case (label, rep) => (label, rep.map(i => nameOf(i.toInt))) }.orNull
   // cpslab.allpair.gpu.autoCompact = f (default 0: off; one GPU only): vectors withdrawn with NativeApss.remove keep their slots
   // until more than the fraction f of the stored vectors is removed; the next IndexData then compacts the store first
   // (apss_set_auto_compact).  The reference has no removal: it stops indexing after expDuration instead (below)

@@ -24,6 +24,22 @@ object NativeApss {
     * native entry point.  Returns 0 or a negative status (lastError(h) says why) */
   def setTopPairs(h: Long, pairs: Long): Int =
     submit(h, 7, Array(0L, 0L), new Array[Int](0), new Array[Double](0), Array(pairs)).toInt
+  /** near-duplicate groups (include/apss.h, apss_set_components; one handle only, a group has none): on = the connected
+    * components of the graph "stored vector - stored vector, edge = a pair of a reply" are kept on the device across calls; off
+    * frees them.  Travels through `submit` (mode 8 of apss_jni.c): no further native entry point.  0 or a negative status */
+  def setComponents(h: Long, on: Boolean): Int =
+    submit(h, 8, Array(0L, 0L), new Array[Int](0), new Array[Double](0), Array(if (on) 1L else 0L)).toInt
+  /** the groups as they are now: for every store slot, in slot order, (the smallest slot of its component | -1 for a removed
+    * vector, the id of the vector in that slot | the removed vector's own).  Rides on `submit` (mode 9: apss_components_get, the
+    * slots labelled) and on `fetch` with minus that count (apss_components_fetch).  null when the setting is off or on an error
+    * (lastError(h) says why) */
+  def components(h: Long): (Array[Int], Array[Long]) = {
+    val rows = submit(h, 9, Array(0L), new Array[Int](0), new Array[Double](0), new Array[Long](0))
+    if (rows < 0) return null
+    val label = new Array[Long](rows.toInt); val rep = new Array[Long](rows.toInt)
+    if (rows > 0 && fetch(h, -rows, label, rep, new Array[Float](rows.toInt)) != 0) return null
+    (label.map(_.toInt), rep)
+  }
   @native def destroy(h: Long): Unit
   @native def lastError(h: Long): String
   /** mode 0 insert, 1 query on the frozen index, 2 insert-and-query; returns #results or a negative status */

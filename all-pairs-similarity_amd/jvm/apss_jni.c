@@ -135,11 +135,36 @@ static int32_t handle_submit(void *t, int mode, int64_t n, const int64_t *rp, co
   if (mode == 6) return apss_query_stored((apss_handle *)t, n, id, NULL, n_res);
   /* ... and the global top-K setting (NativeApss.setTopPairs): mode 7 = apss_set_top_pairs of ids(0) (the CSR is one empty row) */
   if (mode == 7) return apss_set_top_pairs((apss_handle *)t, n == 1 ? id[0] : -1);
+  /* ... and the components of the join (NativeApss.setComponents / components): mode 8 = apss_set_components of ids(0) (the CSR is
+   * one empty row); 9 = apss_components_get, which brings the labels up to date: the slots labelled come back as the count, and a
+   * `fetch` with MINUS that count then reads labels and representatives (components_fetch below) */
+  if (mode == 8) return apss_set_components((apss_handle *)t, n == 1 && (id[0] == 0 || id[0] == 1) ? (int32_t)id[0] : -1);
+  if (mode == 9) {
+    apss_components_info ci = {0};
+    ci.struct_size = (int32_t)sizeof(ci);
+    const int32_t rc = apss_components_get((apss_handle *)t, &ci);
+    if (rc == APSS_OK && !ci.on) return APSS_E_STATE;
+    if (rc == APSS_OK) *n_res = ci.rows;
+    return rc;
+  }
   return apss_insert_and_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
 }
 
 static int32_t handle_fetch(void *t, int64_t count, int64_t *q, int64_t *c, float *s) {
   return apss_fetch_results((apss_handle *)t, 0, count, q, c, s);
+}
+
+/* NativeApss.components: q[i] = the label of slot i (-1: removed), c[i] = the external id of the labelled slot, s[i] = 0 */
+static int32_t components_fetch(void *t, int64_t count, int64_t *q, int64_t *c, float *s) {
+  int32_t *label = (int32_t *)malloc(sizeof(int32_t) * (size_t)count);
+  if (!label) return APSS_E_NOMEM;
+  const int32_t rc = apss_components_fetch((apss_handle *)t, 0, count, label, c);
+  for (int64_t i = 0; i < count && rc == APSS_OK; ++i) {
+    q[i] = label[i];
+    s[i] = 0.0f;
+  }
+  free(label);
+  return rc;
 }
 
 static int32_t group_submit(void *t, int mode, int64_t n, const int64_t *rp, const int32_t *ix, const double *vl, const int64_t *id,
@@ -163,6 +188,7 @@ JNIEXPORT jlong JNICALL Java_cpslab_gpu_NativeApss_submit(JNIEnv *env, jclass cl
 JNIEXPORT jint JNICALL Java_cpslab_gpu_NativeApss_fetch(JNIEnv *env, jclass cls, jlong h, jlong count, jlongArray outQ,
                                                         jlongArray outC, jfloatArray outScore) {
   (void)cls;
+  if (count < 0) return fetch_triples(env, H(h), components_fetch, -count, outQ, outC, outScore); /* (NativeApss.components) */
   return fetch_triples(env, H(h), handle_fetch, count, outQ, outC, outScore);
 }
 

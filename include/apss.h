@@ -522,6 +522,95 @@ typedef struct apss_top_pairs_info {
 int32_t apss_set_top_pairs(apss_handle *h, int64_t k_pairs);
 int32_t apss_top_pairs_get(apss_handle *h, apss_top_pairs_info *out);
 
+/* ---- near-duplicate groups: the connected components of the join, kept on the device ----
+ * What a caller of near-duplicate detection wants is groups of items, not a list of pairs.  The maintained structure is the
+ * connected components of the graph "stored row - stored row, edge = a pair of a call's final list".  It lives on the device, is
+ * kept up to date across calls, and is read as one label per stored slot.  Plain handles only.  Default off: with the setting
+ * off a call launches nothing new, reads nothing new and allocates nothing.
+ *
+ * Labels.
+ *  - label[slot] is the smallest slot of the slot's component.  This is canonical: it does not depend on launch order, so a CPU
+ *    union-find gives the same array.
+ *  - A row marked removed has label -1.
+ *  - apss_components_fetch writes, for slots [offset, offset + count), the label and the external id of the labelled slot.  For
+ *    a removed row it writes -1 and the row's own id.  Either output pointer may be NULL.
+ *  - apss_components_dev gives the device view int32[rows].  The view is valid until the next insert, query-type call, remove,
+ *    compact, clear or apss_set_components.
+ * State rules.
+ *  - apss_set_components(h, 1) turns the structure on (given while it is on: starts it over).
+ *    - Every stored slot becomes a singleton.
+ *    - complete = 1 only on an empty store.
+ *    - The setting survives apss_clear, which empties the structure and sets complete = 1.
+ *  - apss_set_components(h, 0) frees the stage's buffers.
+ *    - apss_components_dev and apss_components_fetch then answer APSS_E_STATE.
+ *    - apss_components_get answers with on = 0, declined = APSS_CC_OFF.
+ *  - Where the stage runs.
+ *    - It runs behind k_rm_drop and before the per-query cut.
+ *    - The graph is therefore every live pair at or above theta, whatever apss_set_top_k and apss_set_top_pairs keep of the list
+ *      afterwards.
+ *    - In a windowed call every window's list is absorbed before that window's cut.
+ *    - The result list of the call is untouched, element by element.
+ *  - Query row to slot.
+ *    - slot_first + row when the batch is stored rows (apss_self_join, apss_insert_and_query[_dev]).
+ *    - The selected slots for apss_query_stored[_dev].
+ *    - Otherwise the call is declined with APSS_CC_OUTSIDE and changes nothing.
+ *    - With APSS_FLAG_ADMISSION the batch rows that were not admitted have no slot: the mapping is taken from what the handle
+ *      itself names as the batch (the rows it stored), not from the caller's row numbers.
+ *  - apss_self_join resets to singletons, absorbs, and leaves complete = 1.
+ *  - apss_insert_and_query[_dev] sets new slots to singletons, absorbs, and keeps complete as it was.
+ *  - apss_query_stored[_dev] absorbs and keeps complete.  Its pairs are true edges.
+ *  - apss_insert[_dev] and apss_insert_stored_dev set new slots to singletons and set complete = 0.  Their rows' edges were never
+ *    seen.
+ *  - A call declined with APSS_CC_TILE_CUT:
+ *    - absorbs nothing (of a windowed call: nothing from its first window that cut on; what earlier windows gave are true edges);
+ *    - sets complete = 0 if it stored rows;
+ *    - resets to singletons with complete = 0 on a non-empty store if it is an apss_self_join.
+ *  - apss_remove[_dev] that marks at least one row, and every compaction that discards rows (auto-compaction included): reset to
+ *    singletons, complete = 0 unless the store is empty, resets + 1.  A removed row can split a component, and a compaction
+ *    shifts slots.  (resets counts these and the resets a failed stage forces; a self-join's own fresh start is none.)
+ *    The structure is never wrong about an edge: at every moment it is the components of a subset of the true live edges, and
+ *    complete says whether it is all of them.
+ *  - Errors.
+ *    - APSS_E_INVALID: NULL handle, on outside {0, 1}, bad struct_size, a range outside [0, rows].
+ *    - APSS_E_UNSUPPORTED ("term shard"): on = 1 on a term shard.
+ *    - A HIP error inside the stage fails the call (APSS_E_DEVICE / APSS_E_NOMEM) and leaves the structure reset with
+ *      complete = 0.
+ *    - apss_group has no such call.
+ * Cost.
+ *  - The absorbing launches (k_cc_init over the new slots, k_cc_hook over the list) run on the handle's stream and read nothing
+ *    back.  A query-type call gains no synchronisation.  (Growing the structure's arrays waits once, as growing the store does.)
+ *  - Labels, counts and unions_total are produced lazily: at the first apss_components_get, _dev or _fetch after a change
+ *    (k_cc_label, k_cc_count, ONE synchronisation).  A second read without a change launches nothing (label_launches says so).
+ *  - Memory: two 32-bit words per slot of capacity, grown by half: at most 12 B per stored slot.  It is counted in
+ *    apss_stats.hbm_bytes and freed by apss_set_components(h, 0). */
+#define APSS_CC_RAN 0
+#define APSS_CC_OFF 1        /* setting off */
+#define APSS_CC_OUTSIDE 2    /* the batch was not rows of the store (apss_query[_dev]): nothing absorbed, nothing changed */
+#define APSS_CC_TILE_CUT 3   /* the probe cut its rounds (apss_set_top_k_tile_cut applied): the list is not every pair */
+typedef struct apss_components_info {
+  int32_t struct_size;     /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t on;
+  int32_t complete;        /* 1: the structure has absorbed every pair >= theta among the live stored rows */
+  int32_t declined;        /* APSS_CC_* of the last query-type call */
+  int64_t rows;            /* slots labelled (apss_size rows) */
+  int64_t rows_live;
+  int64_t components;      /* among live rows, singletons included */
+  int64_t singletons;
+  int64_t largest;         /* rows of the largest component */
+  int64_t pairs_absorbed;  /* pairs of the last query-type call handed to the stage */
+  int64_t unions_total;    /* hooks that joined two components since the last reset: components == rows_live - unions_total */
+  int64_t resets;          /* since create */
+  double hook_ms;          /* device time of the last call's k_cc_hook launches, HIP events (known once the labels are next read) */
+  double label_ms;         /* device time of the last labelling (k_cc_label, k_cc_count) */
+  int32_t hook_launches;   /* of the last query-type call */
+  int32_t label_launches;  /* of the last labelling (0: this read found the labels up to date) */
+  int64_t reserved;        /* 0 */
+} apss_components_info;    /* 112 bytes */
+int32_t apss_set_components(apss_handle *h, int32_t on);
+int32_t apss_components_get(apss_handle *h, apss_components_info *out);
+int32_t apss_components_dev(apss_handle *h, const int32_t **d_label, int64_t *rows);
+int32_t apss_components_fetch(apss_handle *h, int64_t offset, int64_t count, int32_t *out_label, int64_t *out_rep_ext);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE
