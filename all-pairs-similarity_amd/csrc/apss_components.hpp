@@ -194,22 +194,14 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_rep(const int32_t *__restrict
 // ---- host side
 struct CcWork {
   StageMem mem;                           // parent, label, words; its event pair times the labelling
-  hipEvent_t h0 = nullptr, h1 = nullptr;  // ... and this one the hooks of a call (made where first recorded: begin_timed)
-  int32_t *parent = nullptr, *label = nullptr;
-  unsigned long long *words = nullptr;    // [kCcWords]
-  size_t cap = 0;                         // slots parent and label have room for
+  DevEvent h0, h1;                        // ... and this one the hooks of a call (made where first recorded: begin_timed)
+  DevBuf<int32_t> parent, label;
+  DevBuf<unsigned long long> words;       // [kCcWords]
   int64_t rows = 0;                       // parent[0, rows) is initialised: the rest of the store waits for k_cc_init
   bool zero_unions = true;                // words[0] is to be zeroed before it is next added to
   bool dirty = true;                      // label and the counts are older than parent
   bool hook_open = false;                 // h0 / h1 hold a stretch whose time nobody has read yet
 };
-
-inline void cc_release(CcWork &w) {
-  if (w.h0) (void)hipEventDestroy(w.h0);
-  if (w.h1) (void)hipEventDestroy(w.h1);
-  w.mem.free_all({w.parent, w.label, w.words});
-  w = CcWork{};
-}
 
 // every slot a singleton again, no union counted: nothing is launched here (cc_extend does it when the structure is next used)
 inline void cc_reset(CcWork &w) {
@@ -224,36 +216,20 @@ inline unsigned cc_grid(int64_t items, int64_t cap) { return (unsigned)std::max<
 // over the slots that have none -- the new rows of an insert, never the store
 inline hipError_t cc_extend(CcWork &w, hipStream_t stream, int64_t n_rows, int32_t *launches) {
   hipError_t e;
-  if (!w.words && (e = w.mem.grow(w.words, 0, (size_t)kCcWords)) != hipSuccess) return e;
-  if ((size_t)n_rows > w.cap) {
-    const size_t cap = std::max<size_t>((size_t)n_rows, w.cap + w.cap / 2);
-    int32_t *np = nullptr;
-    if ((e = w.mem.grow(np, 0, cap)) != hipSuccess) return e;
-    if (w.parent) {
-      if (w.rows > 0 && (e = hipMemcpyAsync(np, w.parent, (size_t)w.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-      (void)hipFree(w.parent);
-      w.mem.bytes -= w.cap * sizeof(int32_t);
-    }
-    w.parent = np;
-    if ((e = w.mem.grow(w.label, w.cap, cap)) != hipSuccess) {
-      w.cap = 0;  // (label is gone: both are made again from nothing)
-      (void)hipFree(w.parent);
-      w.parent = nullptr;
-      w.mem.bytes -= cap * sizeof(int32_t);
-      w.rows = 0;
-      return e;
-    }
-    w.cap = cap;
+  if (!w.words.p && (e = w.mem.grow((size_t)kCcWords, w.words)) != hipSuccess) return e;
+  if ((size_t)n_rows > w.label.cap) {  // (label grows last: a call that failed half way comes back here, parent keeps what it holds)
+    const size_t cap = std::max<size_t>((size_t)n_rows, w.label.cap + w.label.cap / 2);
+    if ((e = w.parent.grow(kGrowStageKeep, cap, (size_t)w.rows, stream, w.mem.ledger)) != hipSuccess) return e;
+    if ((e = w.mem.grow(cap, w.label)) != hipSuccess) return e;
     w.dirty = true;
   }
   if (w.zero_unions) {
-    if ((e = hipMemsetAsync(w.words, 0, kCcWords * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.words.p, 0, kCcWords * sizeof(unsigned long long), stream)) != hipSuccess) return e;
     w.zero_unions = false;
   }
   if (w.rows > n_rows) w.rows = 0;  // (cannot happen: a store shrinks only through a reset)
   if (w.rows < n_rows) {
-    hipLaunchKernelGGL(k_cc_init, dim3(cc_grid(n_rows - w.rows, kCcGridCap)), dim3(kCcThreads), 0, stream, w.parent, w.rows, n_rows);
+    hipLaunchKernelGGL(k_cc_init, dim3(cc_grid(n_rows - w.rows, kCcGridCap)), dim3(kCcThreads), 0, stream, w.parent.p, w.rows, n_rows);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (launches) ++*launches;
     w.rows = n_rows;
@@ -295,8 +271,8 @@ inline hipError_t cc_hook(CcWork &w, hipStream_t stream, const int32_t *q, const
   a.q_slots = q_slots;
   a.nq = nq;
   a.rows = n_rows;
-  a.parent = w.parent;
-  a.unions = w.words;
+  a.parent = w.parent.p;
+  a.unions = w.words.p;
   hipLaunchKernelGGL(k_cc_hook, dim3(cc_grid(n, grid_cap)), dim3(kCcThreads), 0, stream, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   ++*launches;
@@ -313,19 +289,19 @@ inline hipError_t cc_label(CcWork &w, hipStream_t stream, int64_t n_rows, const 
   hipError_t e;
   *launches = 0;
   if ((e = cc_extend(w, stream, n_rows, nullptr)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(w.words + 1, 0, (kCcWords - 1) * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(w.words.p + 1, 0, (kCcWords - 1) * sizeof(unsigned long long), stream)) != hipSuccess) return e;
   if ((e = begin_timed(stream, w.mem.e0)) != hipSuccess) return e;
   if (n_rows > 0) {
     const dim3 grid(cc_grid(n_rows, kCcGridCap)), block(kCcThreads);
-    hipLaunchKernelGGL(k_cc_label, grid, block, 0, stream, w.parent, w.label, n_rows, 0, dead, dead_rows);
-    hipLaunchKernelGGL(k_cc_count, grid, block, 0, stream, (const int32_t *)w.parent, w.label, n_rows, 0, dead, dead_rows, w.words);
-    hipLaunchKernelGGL(k_cc_count, grid, block, 0, stream, (const int32_t *)w.parent, w.label, n_rows, 1, dead, dead_rows, w.words);
-    hipLaunchKernelGGL(k_cc_label, grid, block, 0, stream, w.parent, w.label, n_rows, 1, dead, dead_rows);
+    hipLaunchKernelGGL(k_cc_label, grid, block, 0, stream, w.parent.p, w.label.p, n_rows, 0, dead, dead_rows);
+    hipLaunchKernelGGL(k_cc_count, grid, block, 0, stream, (const int32_t *)w.parent.p, w.label.p, n_rows, 0, dead, dead_rows, w.words.p);
+    hipLaunchKernelGGL(k_cc_count, grid, block, 0, stream, (const int32_t *)w.parent.p, w.label.p, n_rows, 1, dead, dead_rows, w.words.p);
+    hipLaunchKernelGGL(k_cc_label, grid, block, 0, stream, w.parent.p, w.label.p, n_rows, 1, dead, dead_rows);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     *launches = 4;
   }
   float ms = 0.f;
-  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{host, w.words, kCcWords * sizeof(unsigned long long)}}, &ms)) != hipSuccess) return e;
+  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{host, w.words.p, kCcWords * sizeof(unsigned long long)}}, &ms)) != hipSuccess) return e;
   *label_ms = ms;
   cc_take_hook_time(w, hook_ms);  // (the stream has been waited for: the call's hooks are over)
   w.dirty = false;

@@ -138,11 +138,7 @@ class Barrier {
   bool snap_ = false;
 };
 
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-};
+using apss::DevBuf;
 
 // ---- kernels of the exchange (everything else is the shard handles' work)
 // candidate (query row of the batch, candidate slot) -> one sortable 8-B key
@@ -320,16 +316,24 @@ inline unsigned grid_for(int64_t n, int threads = 256, int64_t cap = 4096) {
 }  // namespace
 
 struct apss_group {
-  struct Member {
-    int dev = 0;
-    apss_handle *h = nullptr;
-    hipStream_t stream = nullptr;
-    ncclComm_t comm = nullptr;
+  // (a member's, a range's and the group's arrays stand in structs of their own: apss_group_destroy assigns each an empty one
+  // with the right device current)
+  struct MemberBufs {
     // exchange buffers, on this member's device
     DevBuf<unsigned long long> keys, sorted, uniq, count;
     DevBuf<char> tmp;
     DevBuf<int32_t> uq, uc;
     DevBuf<float> partial, sum, stage;
+    // grids, device-pointer entry: the phases' batches cut out of the whole batch on this device ([0] own span, [1] outside)
+    DevBuf<int64_t> sp_rowptr[2], sp_ext[2], sp_off;
+    DevBuf<int32_t> sp_idx[2];
+    DevBuf<float> sp_val[2];
+  };
+  struct Member : MemberBufs {
+    int dev = 0;
+    apss_handle *h = nullptr;
+    apss::DevStream stream;
+    ncclComm_t comm = nullptr;
     int64_t n_cand = 0, n_union = 0;
     double member_ms = 0, partial_ms = 0;
     int32_t rc = APSS_OK;
@@ -337,22 +341,20 @@ struct apss_group {
     // the call's sums over its phases (a grid's own join and outside batch; one phase otherwise)
     int64_t visits = 0, dev_visits = 0, touched = 0, cand_sum = 0, cand_max = 0;
     double probe_ms = 0, head_ms = 0;
-    // grids, device-pointer entry: the phases' batches cut out of the whole batch on this device ([0] own span, [1] outside)
-    DevBuf<int64_t> sp_rowptr[2], sp_ext[2], sp_off;
-    DevBuf<int32_t> sp_idx[2];
-    DevBuf<float> sp_val[2];
   };
   // one row range: its T members hold the same rows; its buffers live on its first member's device
-  struct Range {
-    int64_t rows = 0;
+  struct RangeBufs {
     // results of the phase in flight (exchange modes): query row of the phase's batch, candidate slot, score
     DevBuf<int32_t> res_q, res_c;
     DevBuf<float> res_s;
-    int64_t n_phase = 0;
     // grids: the call's results as triples, phase after phase
     DevBuf<int64_t> tri_q, tri_c;
     DevBuf<float> tri_s;
-    int64_t n_tri = 0;
+  };
+  struct Range : RangeBufs {
+    int64_t rows = 0;
+    int64_t n_phase = 0;  // pairs of the phase in flight
+    int64_t n_tri = 0;    // triples of the call so far
     int64_t union_pairs = 0, gather_bytes = 0, mirrored = 0, outside_rows = 0;
     double own_ms = 0, outside_ms = 0, exchange_ms = 0;
   };
@@ -377,7 +379,9 @@ struct apss_group {
   double last_relayout_ms = 0, total_relayout_ms = 0;
   int relayout_fail = -1;  // APSS_DEBUG=relayout_fail=<member>: that member's insert of a re-layout fails (test hook)
   // results of the last query-type call: D = 1, exchange modes: rr[0].res_* on member 0's device; grids: the ranges' triples
-  DevBuf<int64_t> ext_q, ext_c;
+  struct ExtBufs {
+    DevBuf<int64_t> q, c;
+  } ext;
   int64_t n_res = -1;
   bool results_in_handle = false;  // one member, no exchange: the handle's own result list
   // per-query top-k (apss_topk.hpp; D = 1 only).  One member without an exchange: its handle holds the setting and cuts its own
@@ -404,47 +408,12 @@ int32_t gfail(apss_group *g, int32_t rc, const std::string &msg) {
     }                                                                                                \
   } while (0)
 
-template <class T>
-int32_t ensure(apss_group::Member &M, DevBuf<T> &b, size_t n) {
-  if (n <= b.cap && b.p) return APSS_OK;
-  const size_t ncap = std::max<size_t>(std::max(n, b.cap + b.cap / 2), 256);
-  if (b.p) {
-    GHIP(nullptr, M, hipStreamSynchronize(M.stream));
-    GHIP(nullptr, M, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  GHIP(nullptr, M, hipMalloc((void **)&b.p, ncap * sizeof(T)));
-  b.cap = ncap;
+// room for n elements in each of the arrays, on M's device: the old block freed first, the contents dropped (apss_owned.hpp,
+// kGrowGroup; a list that is appended to grows with kGrowGroupKeep where it does)
+template <class... A>
+int32_t ensure(apss_group::Member &M, size_t n, A &...b) {
+  GHIP(nullptr, M, apss::grow_all(apss::kGrowGroup, n, 0, M.stream, nullptr, b...));
   return APSS_OK;
-}
-
-// the same for a buffer that is appended to: the first `used` elements survive the growth
-template <class T>
-int32_t ensure_keep(apss_group::Member &M, DevBuf<T> &b, size_t n, size_t used) {
-  if (n <= b.cap && b.p) return APSS_OK;
-  const size_t ncap = std::max<size_t>(std::max(n, b.cap + b.cap / 2), 256);
-  T *np = nullptr;
-  GHIP(nullptr, M, hipMalloc((void **)&np, ncap * sizeof(T)));
-  if (b.p) {
-    hipError_t e = used ? hipMemcpyAsync(np, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, M.stream) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(M.stream);
-    if (e != hipSuccess) {
-      (void)hipFree(np);
-      GHIP(nullptr, M, e);
-    }
-    GHIP(nullptr, M, hipFree(b.p));
-  }
-  b.p = np;
-  b.cap = ncap;
-  return APSS_OK;
-}
-
-template <class T>
-void release(DevBuf<T> &b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
 }
 
 // one batch as the caller handed it in
@@ -486,6 +455,19 @@ std::vector<int32_t> equal_cuts(int32_t dim, int T) {
   return cuts;
 }
 
+// document frequencies of the terms [lo, hi) over idx[0, nnz) on M's device, into the host array out[hi - lo]: scratch that lives as
+// long as this call, one launch on M's stream, which is waited for
+hipError_t df_hist(apss_group::Member &M, const int32_t *idx, int64_t nnz, int32_t lo, int32_t hi, unsigned int *out) {
+  const size_t bytes = (size_t)(hi - lo) * sizeof(unsigned int);
+  DevBuf<unsigned int> d_df;
+  hipError_t e = d_df.grow(apss::kGrowStage, (size_t)(hi - lo), 0, nullptr, nullptr);
+  if (e == hipSuccess) e = hipMemsetAsync(d_df.p, 0, bytes, M.stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_df_hist, dim3(grid_for(nnz)), dim3(256), 0, M.stream, idx, nnz, lo, hi, d_df.p);
+  if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpyAsync(out, d_df.p, bytes, hipMemcpyDeviceToHost, M.stream);
+  return e == hipSuccess ? hipStreamSynchronize(M.stream) : e;
+}
+
 // document frequencies of a batch as the caller handed it in, added to df (on member 0's device for a device batch)
 int32_t add_batch_df(apss_group *g, const Batch &b, std::vector<uint32_t> &df) {
   const int32_t dim = g->cfg.dim;
@@ -500,16 +482,7 @@ int32_t add_batch_df(apss_group *g, const Batch &b, std::vector<uint32_t> &df) {
   if (b.nnz == 0) return APSS_OK;
   if (hipSetDevice(M0.dev) != hipSuccess) return gfail(g, APSS_E_DEVICE, "hipSetDevice failed");
   std::vector<uint32_t> part((size_t)dim, 0u);
-  unsigned int *d_df = nullptr;
-  hipError_t e = hipMalloc((void **)&d_df, (size_t)dim * sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemsetAsync(d_df, 0, (size_t)dim * sizeof(unsigned int), M0.stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_df_hist, dim3(grid_for(b.nnz)), dim3(256), 0, M0.stream, b.d_indices[0], b.nnz, 0, dim, d_df);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_df, (size_t)dim * sizeof(unsigned int), hipMemcpyDeviceToHost, M0.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(M0.stream);
-  if (d_df) (void)hipFree(d_df);
+  const hipError_t e = df_hist(M0, b.d_indices[0], b.nnz, 0, dim, part.data());
   if (e != hipSuccess) return gfail(g, APSS_E_DEVICE, std::string("document frequencies: ") + hipGetErrorString(e));
   for (size_t t = 0; t < part.size(); ++t) df[t] += part[t];
   return APSS_OK;
@@ -766,7 +739,7 @@ int32_t member_slice(apss_group::Member &M, const CallCtx &cx, const MemberBatch
   sb.n = D + 1;
   for (int k = 0; k <= D; ++k) sb.row[k] = cx.span_lo[(size_t)k];
   int32_t rc;
-  if ((rc = ensure(M, M.sp_off, (size_t)kMaxSpans + 1)) != APSS_OK) return rc;
+  if ((rc = ensure(M, (size_t)kMaxSpans + 1, M.sp_off)) != APSS_OK) return rc;
   hipLaunchKernelGGL(k_span_offsets, dim3(1), dim3(128), 0, M.stream, whole.rowptr, sb, M.sp_off.p);
   GHIP(nullptr, M, hipGetLastError());
   int64_t ent[kMaxSpans + 1];
@@ -796,10 +769,9 @@ int32_t member_slice(apss_group::Member &M, const CallCtx &cx, const MemberBatch
     if (t.n == 0) continue;
     o.n = t.out_row[t.n];
     o.nnz = t.out_ent[t.n];
-    if ((rc = ensure(M, M.sp_rowptr[slot], (size_t)o.n + 1)) != APSS_OK) return rc;
-    if ((rc = ensure(M, M.sp_ext[slot], (size_t)o.n)) != APSS_OK) return rc;
-    if ((rc = ensure(M, M.sp_idx[slot], (size_t)std::max<int64_t>(1, o.nnz))) != APSS_OK) return rc;
-    if ((rc = ensure(M, M.sp_val[slot], (size_t)std::max<int64_t>(1, o.nnz))) != APSS_OK) return rc;
+    if ((rc = ensure(M, (size_t)o.n + 1, M.sp_rowptr[slot])) != APSS_OK) return rc;
+    if ((rc = ensure(M, (size_t)o.n, M.sp_ext[slot])) != APSS_OK) return rc;
+    if ((rc = ensure(M, (size_t)std::max<int64_t>(1, o.nnz), M.sp_idx[slot], M.sp_val[slot])) != APSS_OK) return rc;
     hipLaunchKernelGGL(k_concat_rows, dim3(grid_for(o.n + 1)), dim3(256), 0, M.stream, whole.rowptr, whole.ext, t, M.sp_rowptr[slot].p,
                        M.sp_ext[slot].p);
     GHIP(nullptr, M, hipGetLastError());
@@ -849,10 +821,8 @@ int32_t member_phase1(apss_group::Member &M, int mode, const MemberBatch &b, boo
 
 int32_t member_pack(apss_group::Member &M, int64_t total, int64_t my_off) {
   int32_t rc;
-  if ((rc = ensure(M, M.keys, (size_t)total)) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.sorted, (size_t)total)) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.uniq, (size_t)total)) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.count, 4)) != APSS_OK) return rc;
+  if ((rc = ensure(M, (size_t)total, M.keys, M.sorted, M.uniq)) != APSS_OK) return rc;
+  if ((rc = ensure(M, 4, M.count)) != APSS_OK) return rc;
   if (M.n_cand > 0) {
     const int32_t *dq = nullptr, *dc = nullptr;
     const float *ds = nullptr;
@@ -873,17 +843,14 @@ int32_t member_union(apss_group::Member &M, int64_t total, int key_bits) {
   GHIP(nullptr, M, rocprim::radix_sort_keys(nullptr, a, M.keys.p, M.sorted.p, (size_t)total, 0, (unsigned)key_bits, M.stream));
   GHIP(nullptr, M, rocprim::unique(nullptr, bsz, M.sorted.p, M.uniq.p, M.count.p, (size_t)total, rocprim::equal_to<unsigned long long>(), M.stream));
   int32_t rc;
-  if ((rc = ensure(M, M.tmp, std::max(a, bsz) + 256)) != APSS_OK) return rc;
+  if ((rc = ensure(M, std::max(a, bsz) + 256, M.tmp)) != APSS_OK) return rc;
   GHIP(nullptr, M, rocprim::radix_sort_keys((void *)M.tmp.p, a, M.keys.p, M.sorted.p, (size_t)total, 0, (unsigned)key_bits, M.stream));
   GHIP(nullptr, M, rocprim::unique((void *)M.tmp.p, bsz, M.sorted.p, M.uniq.p, M.count.p, (size_t)total, rocprim::equal_to<unsigned long long>(), M.stream));
   unsigned long long nu = 0;
   GHIP(nullptr, M, hipMemcpyAsync(&nu, M.count.p, sizeof(nu), hipMemcpyDeviceToHost, M.stream));
   GHIP(nullptr, M, hipStreamSynchronize(M.stream));
   M.n_union = (int64_t)nu;
-  if ((rc = ensure(M, M.uq, (size_t)std::max<int64_t>(1, M.n_union))) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.uc, (size_t)std::max<int64_t>(1, M.n_union))) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.partial, (size_t)std::max<int64_t>(1, M.n_union))) != APSS_OK) return rc;
-  if ((rc = ensure(M, M.sum, (size_t)std::max<int64_t>(1, M.n_union))) != APSS_OK) return rc;
+  if ((rc = ensure(M, (size_t)std::max<int64_t>(1, M.n_union), M.uq, M.uc, M.partial, M.sum)) != APSS_OK) return rc;
   if (M.n_union > 0) {
     hipLaunchKernelGGL(k_unpack_keys, dim3(grid_for(M.n_union)), dim3(256), 0, M.stream, (const unsigned long long *)M.uniq.p, M.n_union, M.uq.p, M.uc.p);
     GHIP(nullptr, M, hipGetLastError());
@@ -903,9 +870,7 @@ int32_t append_triples(apss_group::Member &M, apss_group::Range &R, const int32_
     M.err = "the member's external ids are gone";
     return APSS_E_STATE;
   }
-  if ((rc = ensure_keep(M, R.tri_q, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
-  if ((rc = ensure_keep(M, R.tri_c, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
-  if ((rc = ensure_keep(M, R.tri_s, (size_t)(R.n_tri + add), (size_t)R.n_tri)) != APSS_OK) return rc;
+  GHIP(nullptr, M, apss::grow_all(apss::kGrowGroupKeep, (size_t)(R.n_tri + add), (size_t)R.n_tri, M.stream, nullptr, R.tri_q, R.tri_c, R.tri_s));
   hipLaunchKernelGGL(k_triples, dim3(grid_for(n)), dim3(256), 0, M.stream, q_row, c_slot, score, d_query, d_store, n, mirrored ? 1 : 0,
                      R.tri_q.p + R.n_tri, R.tri_c.p + R.n_tri, R.tri_s.p + R.n_tri);
   GHIP(nullptr, M, hipGetLastError());
@@ -1035,7 +1000,7 @@ bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirro
       for (int k = 1; k < T && e == hipSuccess; ++k) {
         const float *src = peers[k].partial.p;
         if (peers[k].dev != M.dev) {  // (another device: bring the vector over first)
-          if (ensure(M, M.stage, (size_t)nu) != APSS_OK) {
+          if (ensure(M, (size_t)nu, M.stage) != APSS_OK) {
             e = hipErrorOutOfMemory;
             break;
           }
@@ -1059,9 +1024,7 @@ bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirro
   if (i == 0 && ok) {
     auto finish = [&]() -> int32_t {
       int32_t rc2;
-      if ((rc2 = ensure(M, R.res_q, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
-      if ((rc2 = ensure(M, R.res_c, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
-      if ((rc2 = ensure(M, R.res_s, (size_t)std::max<int64_t>(1, nu))) != APSS_OK) return rc2;
+      if ((rc2 = ensure(M, (size_t)std::max<int64_t>(1, nu), R.res_q, R.res_c, R.res_s)) != APSS_OK) return rc2;
       GHIP(nullptr, M, hipMemsetAsync(M.count.p, 0, sizeof(unsigned long long), M.stream));
       if (nu > 0) {
         hipLaunchKernelGGL(k_threshold_compact, dim3(grid_for(nu)), dim3(256), 0, M.stream, total_score, (const int32_t *)M.uq.p,
@@ -1089,9 +1052,9 @@ bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirro
         }
         if (R.n_phase > 0) {  // (kept <= n_phase: the selected list fits the buffers it replaces)
           const size_t kept = (size_t)g->tk.kept;
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_q.p, g->topk.out_q, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_c.p, g->topk.out_c, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_s.p, g->topk.out_s, kept * sizeof(float), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_q.p, g->topk.out_q.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_c.p, g->topk.out_c.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+          GHIP(nullptr, M, hipMemcpyAsync(R.res_s.p, g->topk.out_s.p, kept * sizeof(float), hipMemcpyDeviceToDevice, M.stream));
           GHIP(nullptr, M, hipStreamSynchronize(M.stream));
           R.n_phase = g->tk.kept;
         }
@@ -1171,11 +1134,17 @@ void member_main(int m, CallCtx *pcx) {
 
 // whole rows of the store on one device, assembled by the first member on it and read in place by the others there
 struct WholeRows {
-  int64_t *rowptr = nullptr, *len = nullptr, *cur = nullptr;
-  int32_t *idx = nullptr;
-  float *val = nullptr;
+  DevBuf<int64_t> rowptr, len, cur;
+  DevBuf<int32_t> idx;
+  DevBuf<float> val;
   int64_t nnz = 0;
-  std::vector<void *> owned;  // every allocation above + staged copies of other devices' slices + scan scratch
+  struct Staged {  // the copy of another device's slice
+    DevBuf<int64_t> rp;
+    DevBuf<int32_t> ix;
+    DevBuf<float> vl;
+  };
+  std::vector<Staged> staged;
+  DevBuf<char> scan_tmp;
 };
 
 struct RelayoutCtx {
@@ -1195,15 +1164,10 @@ struct RelayoutCtx {
   std::vector<apss_handle *> fresh;
 };
 
-hipError_t dev_alloc(WholeRows &w, void **p, size_t bytes) {
-  const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-  if (e == hipSuccess) w.owned.push_back(*p);
-  return e;
-}
-
-void free_whole(WholeRows &w) {
-  for (void *p : w.owned) (void)hipFree(p);
-  w = WholeRows{};
+// b[n], at least 16 bytes (an empty store still has arrays to point at); a re-layout's arrays are made once, at their size
+template <class T>
+hipError_t dev_alloc(DevBuf<T> &b, size_t n) {
+  return b.grow(apss::kGrowStage, std::max<size_t>(n, 16 / sizeof(T)), 0, nullptr, nullptr);
 }
 
 // document frequencies of member i's stored slice: its range of the store's terms (on the member's stream)
@@ -1218,17 +1182,7 @@ int32_t member_df(apss_group *g, int m, const int32_t *cuts, uint32_t *df_range)
   (void)apss_get_store_dev(M.h, &rp, &ix, &vl, &rows, &nnz);
   std::memset(df_range, 0, (size_t)(hi - lo) * sizeof(uint32_t));
   if (nnz == 0) return APSS_OK;
-  unsigned int *d_df = nullptr;
-  GHIP(nullptr, M, hipMalloc((void **)&d_df, (size_t)(hi - lo) * sizeof(unsigned int)));
-  hipError_t e = hipMemsetAsync(d_df, 0, (size_t)(hi - lo) * sizeof(unsigned int), M.stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_df_hist, dim3(grid_for(nnz)), dim3(256), 0, M.stream, ix, nnz, lo, hi, d_df);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(df_range, d_df, (size_t)(hi - lo) * sizeof(unsigned int), hipMemcpyDeviceToHost, M.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(M.stream);
-  (void)hipFree(d_df);
-  GHIP(nullptr, M, e);
+  GHIP(nullptr, M, df_hist(M, ix, nnz, lo, hi, df_range));
   return APSS_OK;
 }
 
@@ -1238,10 +1192,10 @@ int32_t assemble_whole(RelayoutCtx &cx, int i) {
   apss_group::Member &M = g->m[(size_t)i];
   WholeRows &w = cx.whole[(size_t)i];
   const int64_t rows = cx.rows;
-  GHIP(nullptr, M, dev_alloc(w, (void **)&w.rowptr, (size_t)(rows + 1) * sizeof(int64_t)));
-  GHIP(nullptr, M, dev_alloc(w, (void **)&w.len, (size_t)(rows + 1) * sizeof(int64_t)));
-  GHIP(nullptr, M, dev_alloc(w, (void **)&w.cur, (size_t)(rows + 1) * sizeof(int64_t)));
-  GHIP(nullptr, M, hipMemsetAsync(w.len, 0, (size_t)(rows + 1) * sizeof(int64_t), M.stream));
+  GHIP(nullptr, M, dev_alloc(w.rowptr, (size_t)(rows + 1)));
+  GHIP(nullptr, M, dev_alloc(w.len, (size_t)(rows + 1)));
+  GHIP(nullptr, M, dev_alloc(w.cur, (size_t)(rows + 1)));
+  GHIP(nullptr, M, hipMemsetAsync(w.len.p, 0, (size_t)(rows + 1) * sizeof(int64_t), M.stream));
   struct Slice {
     const int64_t *rp;
     const int32_t *ix;
@@ -1258,37 +1212,35 @@ int32_t assemble_whole(RelayoutCtx &cx, int i) {
       return APSS_E_STATE;
     }
     if (P.dev != M.dev) {  // another device's slice: brought over first (peer copy, or staged by the runtime)
-      int64_t *rp2 = nullptr;
-      int32_t *ix2 = nullptr;
-      float *vl2 = nullptr;
-      GHIP(nullptr, M, dev_alloc(w, (void **)&rp2, (size_t)(rows + 1) * sizeof(int64_t)));
-      GHIP(nullptr, M, dev_alloc(w, (void **)&ix2, (size_t)z * sizeof(int32_t)));
-      GHIP(nullptr, M, dev_alloc(w, (void **)&vl2, (size_t)z * sizeof(float)));
-      GHIP(nullptr, M, hipMemcpyAsync(rp2, s.rp, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDefault, M.stream));
+      w.staged.emplace_back();
+      WholeRows::Staged &c = w.staged.back();
+      GHIP(nullptr, M, dev_alloc(c.rp, (size_t)(rows + 1)));
+      GHIP(nullptr, M, dev_alloc(c.ix, (size_t)z));
+      GHIP(nullptr, M, dev_alloc(c.vl, (size_t)z));
+      GHIP(nullptr, M, hipMemcpyAsync(c.rp.p, s.rp, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDefault, M.stream));
       if (z > 0) {
-        GHIP(nullptr, M, hipMemcpyAsync(ix2, s.ix, (size_t)z * sizeof(int32_t), hipMemcpyDefault, M.stream));
-        GHIP(nullptr, M, hipMemcpyAsync(vl2, s.vl, (size_t)z * sizeof(float), hipMemcpyDefault, M.stream));
+        GHIP(nullptr, M, hipMemcpyAsync(c.ix.p, s.ix, (size_t)z * sizeof(int32_t), hipMemcpyDefault, M.stream));
+        GHIP(nullptr, M, hipMemcpyAsync(c.vl.p, s.vl, (size_t)z * sizeof(float), hipMemcpyDefault, M.stream));
       }
       cx.bytes += (rows + 1) * (int64_t)sizeof(int64_t) + z * (int64_t)(sizeof(int32_t) + sizeof(float));
-      s = Slice{rp2, ix2, vl2};
+      s = Slice{c.rp.p, c.ix.p, c.vl.p};
     }
-    hipLaunchKernelGGL(k_row_len_add, dim3(grid_for(rows)), dim3(256), 0, M.stream, s.rp, rows, w.len);
+    hipLaunchKernelGGL(k_row_len_add, dim3(grid_for(rows)), dim3(256), 0, M.stream, s.rp, rows, w.len.p);
     GHIP(nullptr, M, hipGetLastError());
   }
   size_t tmp_bytes = 0;
-  GHIP(nullptr, M, rocprim::exclusive_scan(nullptr, tmp_bytes, w.len, w.rowptr, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
-  void *tmp = nullptr;
-  GHIP(nullptr, M, dev_alloc(w, &tmp, tmp_bytes));
-  GHIP(nullptr, M, rocprim::exclusive_scan(tmp, tmp_bytes, w.len, w.rowptr, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
-  GHIP(nullptr, M, hipMemcpyAsync(&w.nnz, w.rowptr + rows, sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
-  GHIP(nullptr, M, hipMemcpyAsync(w.cur, w.rowptr, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToDevice, M.stream));
+  GHIP(nullptr, M, rocprim::exclusive_scan(nullptr, tmp_bytes, w.len.p, w.rowptr.p, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
+  GHIP(nullptr, M, dev_alloc(w.scan_tmp, tmp_bytes));
+  GHIP(nullptr, M, rocprim::exclusive_scan((void *)w.scan_tmp.p, tmp_bytes, w.len.p, w.rowptr.p, (int64_t)0, (size_t)(rows + 1), rocprim::plus<int64_t>(), M.stream));
+  GHIP(nullptr, M, hipMemcpyAsync(&w.nnz, w.rowptr.p + rows, sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
+  GHIP(nullptr, M, hipMemcpyAsync(w.cur.p, w.rowptr.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToDevice, M.stream));
   GHIP(nullptr, M, hipStreamSynchronize(M.stream));
-  GHIP(nullptr, M, dev_alloc(w, (void **)&w.idx, (size_t)w.nnz * sizeof(int32_t)));
-  GHIP(nullptr, M, dev_alloc(w, (void **)&w.val, (size_t)w.nnz * sizeof(float)));
+  GHIP(nullptr, M, dev_alloc(w.idx, (size_t)w.nnz));
+  GHIP(nullptr, M, dev_alloc(w.val, (size_t)w.nnz));
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(rows, 256), 8192));  // 4 waves x 64 rows
   for (int k = 0; k < g->T; ++k) {
     const Slice &s = sl[(size_t)k];
-    hipLaunchKernelGGL(k_merge_slice, dim3(blocks), dim3(256), 0, M.stream, s.rp, s.ix, s.vl, rows, w.cur, w.idx, w.val);
+    hipLaunchKernelGGL(k_merge_slice, dim3(blocks), dim3(256), 0, M.stream, s.rp, s.ix, s.vl, rows, w.cur.p, w.idx.p, w.val.p);
     GHIP(nullptr, M, hipGetLastError());
   }
   GHIP(nullptr, M, hipStreamSynchronize(M.stream));  // (the other members on this device read the rows on their own streams)
@@ -1320,7 +1272,7 @@ void relayout_main(int i, RelayoutCtx *pcx) {
     if (rc != APSS_OK) fail_here(rc);
   }
   if (cx.bar->wait()) {  // ---- R1: document frequencies and whole rows are complete
-    if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+    if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
     return;
   }
   // ---- phase B: member 0 decides (the head policy runs on its device over whole rows)
@@ -1331,10 +1283,10 @@ void relayout_main(int i, RelayoutCtx *pcx) {
       const int64_t s_rows = std::min<int64_t>(cx.rows, 131072);
       if (s_rows > 0) {
         int64_t s_nnz = 0;
-        if (hipMemcpy(&s_nnz, w.rowptr + s_rows, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
+        if (hipMemcpy(&s_nnz, w.rowptr.p + s_rows, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
         const int64_t *d_ext = nullptr;
         (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
-        const int32_t rc = apss_insert_stored_dev(ph, s_rows, s_nnz, w.rowptr, w.idx, w.val, d_ext);
+        const int32_t rc = apss_insert_stored_dev(ph, s_rows, s_nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
         if (rc != APSS_OK) return rc;
       }
       return cx.b ? feed_batch(g, ph, *cx.b, std::min<int64_t>(batch_n, 131072 - s_rows)) : APSS_OK;
@@ -1350,7 +1302,7 @@ void relayout_main(int i, RelayoutCtx *pcx) {
     }
   }
   if (cx.bar->wait() || !cx.rebuild) {  // ---- R2: the decision is known
-    if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+    if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
     return;
   }
   // ---- phase C: a new handle for this member in the new layout, filled with the whole rows of its device
@@ -1362,7 +1314,7 @@ void relayout_main(int i, RelayoutCtx *pcx) {
       const int64_t *d_ext = nullptr;
       (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
       const bool inject = g->relayout_fail == i;  // (the test hook: the handle's own argument check refuses the call)
-      rc = apss_insert_stored_dev(cx.fresh[(size_t)i], inject ? -1 : cx.rows, w.nnz, w.rowptr, w.idx, w.val, d_ext);
+      rc = apss_insert_stored_dev(cx.fresh[(size_t)i], inject ? -1 : cx.rows, w.nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
       if (rc != APSS_OK) err = std::string(inject ? "APSS_DEBUG relayout_fail: " : "") + apss_last_error(cx.fresh[(size_t)i]);
       else if (hipStreamSynchronize(M.stream) != hipSuccess) rc = APSS_E_DEVICE, err = "stream synchronisation failed after the re-insert";
     }
@@ -1372,7 +1324,7 @@ void relayout_main(int i, RelayoutCtx *pcx) {
     }
   }
   const bool failed_r3 = cx.bar->wait();  // ---- R3: every new member is filled (or one failed): swap together, or not at all
-  if (cx.builder[(size_t)i] == i) free_whole(cx.whole[(size_t)i]);
+  if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
   if (failed_r3) {
     if (cx.fresh[(size_t)i]) apss_destroy(cx.fresh[(size_t)i]);
     cx.fresh[(size_t)i] = nullptr;
@@ -1702,7 +1654,7 @@ int32_t apss_group_create_grid(const apss_config *cfg, int32_t n_term_ranges, in
     for (int k = i - i % n_term_ranges; k < i; ++k)  // (the exchange runs among the members of ONE row range)
       if (g->m[(size_t)k].dev == d) g->distinct_devices = false;
     g->m[(size_t)i].dev = d;
-    if (hipSetDevice(d) != hipSuccess || hipStreamCreateWithFlags(&g->m[(size_t)i].stream, hipStreamDefault) != hipSuccess) {
+    if (hipSetDevice(d) != hipSuccess || g->m[(size_t)i].stream.make() != hipSuccess) {
       g_group_create_error = "HIP stream creation failed";
       apss_group_destroy(g);
       return APSS_E_DEVICE;
@@ -1717,31 +1669,25 @@ void apss_group_destroy(apss_group *g) {
   Rccl *r = g->exchange == APSS_EXCHANGE_RCCL ? load_rccl() : nullptr;
   for (apss_group::Member &M : g->m) {
     (void)hipSetDevice(M.dev);
-    if (M.stream) (void)hipStreamSynchronize(M.stream);
+    if (M.stream.made()) (void)hipStreamSynchronize(M.stream);
     if (M.comm && r && r->lib) (void)r->CommDestroy(M.comm);
     if (M.h) apss_destroy(M.h);
-    release(M.keys); release(M.sorted); release(M.uniq); release(M.count); release(M.tmp);
-    release(M.uq); release(M.uc); release(M.partial); release(M.sum); release(M.stage); release(M.sp_off);
-    for (int k = 0; k < 2; ++k) {
-      release(M.sp_rowptr[k]); release(M.sp_ext[k]); release(M.sp_idx[k]); release(M.sp_val[k]);
-    }
+    static_cast<apss_group::MemberBufs &>(M) = {};
   }
   if (!g->m.empty()) {
     (void)hipSetDevice(g->m[0].dev);
-    apss::topk_release(g->topk);
+    g->topk = {};
   }
   for (size_t j = 0; j < g->rr.size() && j * (size_t)g->T < g->m.size(); ++j) {
-    apss_group::Range &R = g->rr[j];
     (void)hipSetDevice(g->m[j * (size_t)g->T].dev);
-    release(R.res_q); release(R.res_c); release(R.res_s); release(R.tri_q); release(R.tri_c); release(R.tri_s);
+    static_cast<apss_group::RangeBufs &>(g->rr[j]) = {};
   }
   if (!g->m.empty()) (void)hipSetDevice(g->m[0].dev);
-  release(g->ext_q); release(g->ext_c);
-  for (apss_group::Member &M : g->m)
-    if (M.stream) {
-      (void)hipSetDevice(M.dev);
-      (void)hipStreamDestroy(M.stream);
-    }
+  g->ext = {};
+  for (apss_group::Member &M : g->m) {
+    (void)hipSetDevice(M.dev);
+    M.stream = {};
+  }
   delete g;
 }
 
@@ -1925,13 +1871,12 @@ int32_t apss_group_fetch_results(apss_group *g, int64_t offset, int64_t count, i
       M.err = "the members' external ids are gone (an insert since the last query-type call)";
       return APSS_E_STATE;
     }
-    if ((rc = ensure(M, g->ext_q, (size_t)count)) != APSS_OK) return rc;
-    if ((rc = ensure(M, g->ext_c, (size_t)count)) != APSS_OK) return rc;
+    if ((rc = ensure(M, (size_t)count, g->ext.q, g->ext.c)) != APSS_OK) return rc;
     hipLaunchKernelGGL(k_gather_ext, dim3((unsigned)ceil_div(count, 256)), dim3(256), 0, M.stream, (const int32_t *)g->rr[0].res_q.p + offset,
-                       (const int32_t *)g->rr[0].res_c.p + offset, d_query, d_store, count, g->ext_q.p, g->ext_c.p);
+                       (const int32_t *)g->rr[0].res_c.p + offset, d_query, d_store, count, g->ext.q.p, g->ext.c.p);
     GHIP(nullptr, M, hipGetLastError());
-    GHIP(nullptr, M, hipMemcpyAsync(out_q, g->ext_q.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
-    GHIP(nullptr, M, hipMemcpyAsync(out_c, g->ext_c.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
+    GHIP(nullptr, M, hipMemcpyAsync(out_q, g->ext.q.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
+    GHIP(nullptr, M, hipMemcpyAsync(out_c, g->ext.c.p, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
     GHIP(nullptr, M, hipMemcpyAsync(out_score, g->rr[0].res_s.p + offset, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, M.stream));
     GHIP(nullptr, M, hipStreamSynchronize(M.stream));
     return APSS_OK;

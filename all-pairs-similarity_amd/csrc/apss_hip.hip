@@ -36,19 +36,12 @@ namespace {
 
 thread_local std::string g_create_error;
 
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;  // elements
-};
-
 // A list of (query row, candidate, score) pairs: three arrays that grow, swap and go together, so they share one capacity
 struct PairList {
   DevBuf<int32_t> q, c;
   DevBuf<float> s;
   size_t cap() const { return q.cap; }
   int32_t ensure(apss_handle *h, size_t n, size_t keep = 0, bool exact = false);  // (grow-only, as the arrays' own ensure)
-  void release();
   void swap(PairList &o) {
     std::swap(q, o.q);
     std::swap(c, o.c);
@@ -218,9 +211,11 @@ struct apss_handle {
   apss_config cfg{};
   DebugCfg dbgcfg;
   int dev = 0;
-  hipStream_t own_stream = nullptr;
+  // (what the arrays below are counted in and run on stands in front of them: it is destroyed after them)
+  size_t bytes_reserved = 0;  // device bytes the handle's arrays hold (apss_stats.hbm_bytes): every array grows against it
+  DevStream own_stream;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvent ev0, ev1;
   std::string err;
   bool sharded = false;
   bool nonneg = true;    // every stored weight so far is >= 0
@@ -318,7 +313,7 @@ struct apss_handle {
   DevBuf<unsigned int> flagword;
   // small messages (single vectors, batches of a few dozen: the reference's LoadGenerator sends ONE vector per message): the
   // batch crosses PCIe as one packed copy out of pinned memory and the answer comes back the same way
-  char *pin = nullptr;             // pinned host staging, kPinBytes + kPinScalars
+  PinBuf<char> pin;                // pinned host staging, kPinBytes + kPinScalars
   PinScalars own_scalars{};        // (without pinned memory: pageable copies of the scalar slots)
   PinScalars *scalars = &own_scalars;  // where the small device-to-host reads land: behind `pin`, or own_scalars
   DevBuf<char> pack;               // its device twin
@@ -362,7 +357,7 @@ struct apss_handle {
   PairList uq;                        // candidate list after k_pair_dedup
   int64_t head_nonempty = 0, last_batch_head_nonempty = 0;
   double head_sample_frac = 0.0;      // fraction of sampled pairs the dense filter passed when the policy last looked
-  hipEvent_t ev2 = nullptr, ev3 = nullptr;
+  DevEvent ev2, ev3;
   // per-query top-k (apss_topk.hpp): the setting, the pass's buffers, what the last query-type call did
   int32_t top_k = 0;
   TopkWork topk;
@@ -393,7 +388,7 @@ struct apss_handle {
   DevBuf<char> rm_tmp;
   DevBuf<unsigned long long> rm_ctr;  // [1] rows newly marked / pairs kept
   PairList rm_out;
-  hipEvent_t rm_ev0 = nullptr, rm_ev1 = nullptr;  // (created where they are first recorded: begin_timed / end_timed_read)
+  DevEvent rm_ev0, rm_ev1;  // (made where they are first recorded: begin_timed / end_timed_read)
   double auto_compact = 0.0;
   apss_removal_info ri{};
   // stored rows as a query batch (apss_query_stored.hpp): the found bytes of the sorted id list (which lives in rm_sorted), the id
@@ -401,7 +396,7 @@ struct apss_handle {
   DevBuf<uint8_t> qs_found;
   DevBuf<unsigned long long> qs_ctr;  // [2] distinct ids / distinct ids that selected nothing
   DevBuf<int32_t> qs_slots;
-  hipEvent_t qs_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // (created where they are first recorded)
+  DevEvent qs_ev[4];  // (made where they are first recorded)
   apss_stored_query_info qsi{};
   // global top-K (apss_top_pairs.hpp): the setting, the stage's buffers, what the last query-type call did
   int64_t top_pairs = 0;
@@ -416,15 +411,13 @@ struct apss_handle {
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
   std::vector<int64_t> wl_off, wl_fine;  // [launches + 1] first item of every launch's list; [launches] its cut pieces
-  apss::ProbeItem *wl_pin = nullptr;
-  size_t wl_pin_cap = 0;
+  PinBuf<apss::ProbeItem> wl_pin;
   DevBuf<apss::ProbeItem> wl_dev;
-  hipEvent_t wl_ev = nullptr;            // the last upload out of wl_pin
+  DevEvent wl_ev{kUntimed};              // the last upload out of wl_pin
   std::map<const void *, int> wl_per_cu;
   int n_cus = 0;
   // stats
   apss_stats st{};
-  size_t bytes_reserved = 0;
 };
 
 namespace {
@@ -449,42 +442,16 @@ int32_t fail(apss_handle *h, int32_t rc, const std::string &msg) {
   return rc;
 }
 
-// grow-only device array; keeps the first `keep` elements
+// grow-only device array; keeps the first `keep` elements.  (A failed growth leaves the array, and the reservation, as they were)
 template <class T>
 int32_t ensure(apss_handle *h, DevBuf<T> &b, size_t n, size_t keep = 0, bool exact = false) {
-  if (n <= b.cap && b.p) return APSS_OK;
-  size_t ncap = exact ? n : std::max(n, b.cap + b.cap / 2);
-  ncap = std::max<size_t>(ncap, 64);
-  T *np = nullptr;
-  HIPCHK(h, hipMalloc((void **)&np, ncap * sizeof(T)));
-  if (keep && b.p) HIPCHK(h, hipMemcpyAsync(np, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
-  if (b.p) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipFree(b.p));
-    h->bytes_reserved -= b.cap * sizeof(T);
-  }
-  b.p = np;
-  b.cap = ncap;
-  h->bytes_reserved += ncap * sizeof(T);
+  HIPCHK(h, b.grow(exact ? kGrowHandleExact : kGrowHandle, n, keep, h->stream, &h->bytes_reserved));
   return APSS_OK;
 }
 
-template <class T>
-void release(DevBuf<T> &b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-
 int32_t PairList::ensure(apss_handle *h, size_t n, size_t keep, bool exact) {
-  APSS_TRY(::ensure(h, q, n, keep, exact));
-  APSS_TRY(::ensure(h, c, n, keep, exact));
-  return ::ensure(h, s, n, keep, exact);
-}
-void PairList::release() {
-  ::release(q);
-  ::release(c);
-  ::release(s);
+  HIPCHK(h, grow_all(exact ? kGrowHandleExact : kGrowHandle, n, keep, h->stream, &h->bytes_reserved, q, c, s));
+  return APSS_OK;
 }
 
 int32_t enter(apss_handle *h) {
@@ -870,7 +837,7 @@ int32_t begin_build(apss_handle *h, Build &bd) {
     b.sub_base = h->bk_base.p;
     b.o_ent = h->run_ent.p;
   }
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, h->ev0.record(h->stream));
   if (p.kind != BuildKind::Bucketed) return APSS_OK;
   // Bucketed: the scratch of the largest tile group (row extents are on the device: one small read), k_bucket_pass's arguments, the LDS kernels' view
   const int64_t nb = p.group_tiles * p.n_ranges;
@@ -894,7 +861,7 @@ int32_t begin_build(apss_handle *h, Build &bd) {
   b.val = h->bk_val.p;
   b.ent_base = h->bk_base.p;
   b.range_terms = p.range_terms;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // (the build's clock starts behind the reservations)
+  HIPCHK(h, h->ev0.record(h->stream));  // (the build's clock starts behind the reservations)
   return APSS_OK;
 }
 
@@ -1011,7 +978,7 @@ int32_t finish_build(apss_handle *h, Build &bd) {
   if (bd.scaled)
     hipLaunchKernelGGL(k_tile_min_sub, bd.tile_grid(1), dim3(1024), 0, h->stream, (const float *)h->sub.p, h->idx_rows, (int32_t)bd.ix.cb, bd.tmin.p, bd.tile0);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, h->ev1.record(h->stream));
   HIPCHK(h, hipEventSynchronize(h->ev1));  // (the host vector the tile bases were copied from lives on; the event gives the build its time)
   float ms = 0.f;
   HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -1038,7 +1005,7 @@ int32_t build_tiles(apss_handle *h, apss_handle::IndexSet &ix, int64_t row0) {
     bd.plan.kind = BuildKind::Append;
     bd.n_tiles = tile0 + 1;
     fill_build_args(h, bd, row0, std::min<int64_t>(h->idx_rows, (tile0 + 1) * cb));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, h->ev0.record(h->stream));
     HIPCHK(h, hipMemcpyAsync(h->app_seg.p, ix.seg.p + tile0 * (int64_t)h->cfg.dim, (size_t)h->cfg.dim * sizeof(uint2), hipMemcpyDeviceToDevice, h->stream));
     if (old_total > 0)
       HIPCHK(h, hipMemcpyAsync(h->app_post.p, ix.coarse ? (const void *)(ix.post_c.p + base) : (const void *)(ix.post.p + base), old_total * elt,
@@ -2142,14 +2109,14 @@ int32_t exact_pass(apss_handle *h, bool hybrid, double theta, const QueryRows &q
   if (n_cand > 0) {
     APSS_TRY(h->fin.ensure(h, (size_t)n_cand, 0, true));
     HIPCHK(h, hipMemsetAsync(h->counters.p, 0, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, h->ev0.record(h->stream));
     // (a launch may not have 2^32 threads or more: 16 lanes per pair -> at most 2^27 pairs per launch)
     for (int64_t p0 = 0; p0 < n_cand; p0 += (1LL << 27)) {
       const RescoreArgs r = rescore_args(h, cand_q + p0, cand_c + p0, std::min<int64_t>(1LL << 27, n_cand - p0), nullptr, q, (float)theta, h->counters.p);
       hipLaunchKernelGGL(k_rescore, rescore_grid(r.n_pairs), dim3(kRescoreBlock), 0, h->stream, r);
       HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, h->ev1.record(h->stream));
     unsigned long long nfin = 0;
     HIPCHK(h, hipMemcpyAsync(&nfin, h->counters.p, sizeof(nfin), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2639,22 +2606,17 @@ int32_t prepare_work_lists(apss_handle *h, Probe &pr) {
     h->wl_fine.push_back(apss::build_work_list(k, items));
     h->wl_off.push_back((int64_t)items.size());
   }
-  if (!h->wl_ev) HIPCHK(h, hipEventCreateWithFlags(&h->wl_ev, hipEventDisableTiming));
-  else HIPCHK(h, hipEventSynchronize(h->wl_ev));  // the last upload has left the pinned buffer
-  if (items.size() > h->wl_pin_cap) {
-    if (h->wl_pin) (void)hipHostFree(h->wl_pin);
-    h->wl_pin = nullptr;
-    h->wl_pin_cap = 0;
+  if (h->wl_ev.made()) HIPCHK(h, hipEventSynchronize(h->wl_ev));  // the last upload has left the pinned buffer
+  if (items.size() > h->wl_pin.cap) {
     const size_t cap = std::max<size_t>(items.size() + items.size() / 2, 4096);
-    HIPCHK(h, hipHostMalloc((void **)&h->wl_pin, cap * sizeof(apss::ProbeItem), hipHostMallocDefault));
-    h->wl_pin_cap = cap;
+    HIPCHK(h, h->wl_pin.grow(kGrowStage, cap, 0, nullptr, nullptr));
   }
   APSS_TRY(ensure(h, h->wl_dev, std::max<size_t>(items.size(), 1)));
   if (!items.empty()) {
-    std::memcpy(h->wl_pin, items.data(), items.size() * sizeof(apss::ProbeItem));
-    HIPCHK(h, hipMemcpyAsync(h->wl_dev.p, h->wl_pin, items.size() * sizeof(apss::ProbeItem), hipMemcpyHostToDevice, h->stream));
+    std::memcpy(h->wl_pin.p, items.data(), items.size() * sizeof(apss::ProbeItem));
+    HIPCHK(h, hipMemcpyAsync(h->wl_dev.p, h->wl_pin.p, items.size() * sizeof(apss::ProbeItem), hipMemcpyHostToDevice, h->stream));
   }
-  HIPCHK(h, hipEventRecord(h->wl_ev, h->stream));
+  HIPCHK(h, h->wl_ev.record(h->stream));
   h->wl_keys = keys;
   return APSS_OK;
 }
@@ -2671,7 +2633,7 @@ int32_t begin_attempt(apss_handle *h, Probe &pr) {
   pr.a.res_cap = h->res.cap();
   HIPCHK(h, hipMemsetAsync(h->counters.p, 0, kCtrCount * sizeof(unsigned long long), h->stream));
   if (pr.xk.cut) HIPCHK(h, hipMemsetAsync(h->row_pairs.p, 0, (size_t)pr.q.nq * sizeof(uint32_t), h->stream));  // (every attempt: a re-run counts afresh)
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  HIPCHK(h, h->ev0.record(h->stream));
   return APSS_OK;
 }
 
@@ -2815,10 +2777,10 @@ int32_t chained_exact_pass(apss_handle *h, const Probe &pr, AttemptCounts &n) {
 int32_t launch_head(apss_handle *h, const Probe &pr, AttemptCounts &n) {
   HIPCHK(h, hipMemcpyAsync(&n.sparse_results, h->counters.p + kCtrResults, sizeof(n.sparse_results), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemsetAsync(h->head_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
-  HIPCHK(h, hipEventRecord(h->ev2, h->stream));
+  HIPCHK(h, h->ev2.record(h->stream));
   const bool stored = pr.p.q_slot_base >= 0 && !pr.p.head_outside;
   APSS_TRY(run_head(h, pr.a, pr.q.nq, stored ? pr.p.q_slot_base : -1, stored ? h->W.p : h->q_W.p, stored ? (int64_t)(h->W.cap / h->head_k) : ceil_div(pr.q.nq, kHeadCTile) * kHeadCTile, pr.p.head_thr, pr.p.bound, h->idx_rows));
-  HIPCHK(h, hipEventRecord(h->ev3, h->stream));
+  HIPCHK(h, h->ev3.record(h->stream));
   HIPCHK(h, hipMemcpyAsync(n.head_c, h->head_ctr.p, sizeof(n.head_c), hipMemcpyDeviceToHost, h->stream));
   return APSS_OK;
 }
@@ -2915,7 +2877,7 @@ int32_t run_attempt(apss_handle *h, Probe &pr) {
   APSS_TRY(launch_tile_groups(h, pr, n));
   if (pr.a.merge_log2 > 0) APSS_TRY(expand_merged_rounds(h, pr));
   if (pr.a.tri) APSS_TRY(mirror_survivors(h, pr));
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHK(h, h->ev1.record(h->stream));
   for (int k = 0; k < kCtrCount; ++k) n.cc[k] = 0;
   if (pr.chain) APSS_TRY(chained_exact_pass(h, pr, n));
   if (pr.p.hybrid) APSS_TRY(launch_head(h, pr, n));
@@ -2966,14 +2928,13 @@ int32_t probe_inner(apss_handle *h, const QueryBatch &batch, int64_t *n_results)
 }
 
 // ---- the list stages behind the join (apss_stage.hpp): each takes the call's list where adopt_list left it and adopts its own ----
-// One stage that owns its device memory (`mem`) and reports a hipError_t -- or, through *bad, that its own counts disagree: the
-// handle's reservation follows the stage's, and a failure takes the call's list with it
+// One stage that owns its device memory and reports a hipError_t -- or, through *bad, that its own counts disagree: its arrays
+// grow against the handle's reservation (`mem`), and a failure takes the call's list with it
 template <class F>
 int32_t run_stage(apss_handle *h, const char *what, StageMem &mem, F fn) {
-  const size_t before = mem.bytes;
+  mem.ledger = &h->bytes_reserved;
   const char *bad = nullptr;
   const hipError_t e = fn(&bad);
-  h->bytes_reserved += mem.bytes - before;
   if (e == hipSuccess) return APSS_OK;
   h->n_res = -1;
   h->err = std::string(what) + ": " + (bad ? bad : hipGetErrorString(e));
@@ -2987,7 +2948,7 @@ int32_t cut_final_list(apss_handle *h, int64_t nq, apss_topk_info *info) {
     return topk_run(h->topk, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, nq, h->ext.p, h->n_rows, h->top_k, info,
                     h->cut_ran ? h->row_pairs.p : nullptr, h->cut_uncut);
   }));
-  if (h->n_res > 0) adopt_list(h, h->topk.out_q, h->topk.out_c, h->topk.out_s, info->kept);
+  if (h->n_res > 0) adopt_list(h, h->topk.out_q.p, h->topk.out_c.p, h->topk.out_s.p, info->kept);
   return APSS_OK;
 }
 
@@ -3293,7 +3254,7 @@ int32_t cut_top_pairs(apss_handle *h, const QueryBatch &batch) {
     return tp_run(h->tp, h->stream, h->out_q, h->out_c, h->out_s, h->n_res, batch.ext, batch.nq, h->ext.p, h->n_rows, h->top_pairs,
                   h->dbgcfg.tp_grid > 0 ? h->dbgcfg.tp_grid : kTpGridCap, h->scalars->top_pairs, &h->tpi, bad);
   }));
-  adopt_list(h, h->tp.out_q, h->tp.out_c, h->tp.out_s, h->tpi.kept);
+  adopt_list(h, h->tp.out_q.p, h->tp.out_c.p, h->tp.out_s.p, h->tpi.kept);
   return APSS_OK;
 }
 
@@ -3344,18 +3305,18 @@ int32_t upload(apss_handle *h, int64_t n, const int64_t *rowptr, const int32_t *
   APSS_TRY(ensure(h, h->in_val, (size_t)std::max<int64_t>(nnz, 1)));
   const size_t off_ext = (size_t)(n + 1) * sizeof(int64_t), off_val = off_ext + (size_t)n * sizeof(int64_t);
   const size_t off_idx = off_val + (size_t)nnz * sizeof(double), bytes = off_idx + (size_t)nnz * sizeof(int32_t);
-  if (n > 0 && h->pin && bytes <= kPinBytes) {
+  if (n > 0 && h->pin.p && bytes <= kPinBytes) {
     // a small message: packed into pinned memory [rowptr | ext ids | values | indices] -> ONE truly asynchronous copy, no
     // synchronisation here (the staging is the handle's own: the caller's arrays are consumed by the memcpy below, and every
     // entry point synchronises before it returns)
     APSS_TRY(ensure(h, h->pack, kPinBytes));
-    std::memcpy(h->pin, rowptr, off_ext);
-    std::memcpy(h->pin + off_ext, ext_ids, (size_t)n * sizeof(int64_t));
+    std::memcpy(h->pin.p, rowptr, off_ext);
+    std::memcpy(h->pin.p + off_ext, ext_ids, (size_t)n * sizeof(int64_t));
     if (nnz) {
-      std::memcpy(h->pin + off_val, values, (size_t)nnz * sizeof(double));
-      std::memcpy(h->pin + off_idx, indices, (size_t)nnz * sizeof(int32_t));
+      std::memcpy(h->pin.p + off_val, values, (size_t)nnz * sizeof(double));
+      std::memcpy(h->pin.p + off_idx, indices, (size_t)nnz * sizeof(int32_t));
     }
-    HIPCHK(h, hipMemcpyAsync(h->pack.p, h->pin, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->pack.p, h->pin.p, bytes, hipMemcpyHostToDevice, h->stream));
     h->up_rowptr = reinterpret_cast<const int64_t *>(h->pack.p);
     h->up_ext = reinterpret_cast<const int64_t *>(h->pack.p + off_ext);
     h->up_idx = reinterpret_cast<const int32_t *>(h->pack.p + off_idx);
@@ -3497,7 +3458,7 @@ int32_t refuse_shard_removal(apss_handle *h, const char *what) {
 
 // An id list of a call, d_ids[0, n) (device, n > 0), ascending in h->rm_sorted (rocprim radix sort through h->rm_tmp).  What the
 // sort needs is reserved first; the sort itself opens the call's timed stretch (e0)
-int32_t sort_ids(apss_handle *h, const int64_t *d_ids, int64_t n, hipEvent_t &e0) {
+int32_t sort_ids(apss_handle *h, const int64_t *d_ids, int64_t n, DevEvent &e0) {
   APSS_TRY(ensure(h, h->rm_sorted, (size_t)n));
   size_t tmp_bytes = 0;
   HIPCHK(h, rocprim::radix_sort_keys(nullptr, tmp_bytes, d_ids, h->rm_sorted.p, (size_t)n, 0, 64, h->stream));
@@ -3782,16 +3743,14 @@ int32_t apss_create(const apss_config *cfg, apss_handle **out) {
     delete h;
     return APSS_E_DEVICE;
   }
-  if ((e = hipSetDevice(h->dev)) != hipSuccess || (e = hipStreamCreateWithFlags(&h->own_stream, hipStreamDefault)) != hipSuccess ||
-      (e = hipEventCreate(&h->ev0)) != hipSuccess || (e = hipEventCreate(&h->ev1)) != hipSuccess ||
-      (e = hipEventCreate(&h->ev2)) != hipSuccess || (e = hipEventCreate(&h->ev3)) != hipSuccess) {
+  if ((e = hipSetDevice(h->dev)) != hipSuccess || (e = h->own_stream.make()) != hipSuccess) {
     g_create_error = std::string("HIP init failed: ") + hipGetErrorString(e);
     delete h;
     return APSS_E_DEVICE;
   }
   h->stream = h->own_stream;
-  if (hipHostMalloc((void **)&h->pin, kPinBytes + kPinScalars, hipHostMallocDefault) != hipSuccess) h->pin = nullptr;  // (without it: the unpacked copies)
-  if (h->pin) h->scalars = new (h->pin + kPinBytes) PinScalars{};
+  (void)h->pin.grow(kGrowStage, kPinBytes + kPinScalars, 0, nullptr, nullptr);  // (without it: the unpacked copies)
+  if (h->pin.p) h->scalars = new (h->pin.p + kPinBytes) PinScalars{};
   if (cfg->capacity_rows > 0) {
     if (ensure(h, h->rowptr, (size_t)cfg->capacity_rows + 1, 0, true) != APSS_OK ||
         ensure(h, h->ext, (size_t)cfg->capacity_rows, 0, true) != APSS_OK) {
@@ -3818,31 +3777,7 @@ int32_t apss_create(const apss_config *cfg, apss_handle **out) {
 void apss_destroy(apss_handle *h) {
   if (!h) return;
   (void)hipSetDevice(h->dev);
-  if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
-  release(h->rowptr); release(h->ext); release(h->idx); release(h->erow); release(h->val); release(h->sub);
-  for (apss_handle::IndexSet *s : {&h->ex, &h->cx}) { release(s->seg); release(s->post); release(s->post_c); release(s->base); release(s->total); release(s->maxlen); release(s->chunkw); release(s->scan_part); }
-  release(h->tile_min); release(h->tile_min_c); h->fin.release();
-  release(h->q_rowptr); release(h->q_ext); release(h->q_idx); release(h->q_val); release(h->q_sub);
-  release(h->s_keep); release(h->s_cnt); release(h->s_rowdst); release(h->s_nnzdst); release(h->scan_tmp);
-  release(h->in_rowptr); release(h->in_ext); release(h->in_idx); release(h->s_inv); release(h->s_sub); release(h->in_val); release(h->in_val64); release(h->vq_first); release(h->vrow_q); release(h->vrow_ptr); release(h->vrow_np); release(h->vrow_first);
-  h->res.release(); h->res2.release(); release(h->q_prenorm); release(h->counters); release(h->flagword); release(h->dbg);
-  release(h->head_pos); release(h->W);
-  for (apss_handle::TailView *v : {&h->tv, &h->qtv}) { release(v->rowptr); release(v->idx); release(v->val); release(v->erow); }
-  release(h->tv_cnt); release(h->tv_off); release(h->tv_sum); release(h->q_W); release(h->df); release(h->dedup_tab);
-  release(h->head_ctr); h->uq.release(); release(h->pack); release(h->chain_ctr); release(h->app_seg); release(h->app_post); release(h->bk_cnt); release(h->bk_base); release(h->bk_idx); release(h->bk_erow); release(h->bk_val); release(h->run_cut); release(h->run_ent); release(h->ing_cut);
-  topk_release(h->topk);
-  tp_release(h->tp);
-  cc_release(h->cc);
-  release(h->win_df); release(h->win_b); h->win.release();
-  release(h->row_pairs);
-  release(h->dead); release(h->rm_ids); release(h->rm_sorted); release(h->rm_tmp); release(h->rm_ctr); h->rm_out.release();
-  release(h->qs_found); release(h->qs_ctr); release(h->qs_slots);
-  if (h->pin) (void)hipHostFree(h->pin);
-  release(h->wl_dev);
-  if (h->wl_pin) (void)hipHostFree(h->wl_pin);
-  for (hipEvent_t e : {h->rm_ev0, h->rm_ev1, h->qs_ev[0], h->qs_ev[1], h->qs_ev[2], h->qs_ev[3], h->wl_ev, h->ev0, h->ev1, h->ev2, h->ev3})
-    if (e) (void)hipEventDestroy(e);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+  if (h->own_stream.made()) (void)hipStreamSynchronize(h->own_stream);
   delete h;
 }
 
@@ -3920,7 +3855,7 @@ int32_t apss_fetch_results(apss_handle *h, int64_t offset, int64_t count, int64_
   if (count == 0) return APSS_OK;
   if (!out_q || !out_c || !out_score) return fail(h, APSS_E_INVALID, "null output buffer");
   // map (query row, candidate slot) to external ids on the device, then copy out
-  if (h->pin && (size_t)count * 20 <= kPinBytes) {  // a small answer: one packed copy into pinned memory
+  if (h->pin.p && (size_t)count * 20 <= kPinBytes) {  // a small answer: one packed copy into pinned memory
     APSS_TRY(ensure(h, h->pack, kPinBytes));
     int64_t *pq = reinterpret_cast<int64_t *>(h->pack.p), *pc = pq + count;
     float *ps = reinterpret_cast<float *>(pc + count);
@@ -3928,11 +3863,11 @@ int32_t apss_fetch_results(apss_handle *h, int64_t offset, int64_t count, int64_
                        h->res_q_ext, (const int64_t *)h->ext.p, count, pq, pc);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(ps, h->out_s + offset, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->pin, h->pack.p, (size_t)count * 20, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->pin.p, h->pack.p, (size_t)count * 20, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::memcpy(out_q, h->pin, (size_t)count * sizeof(int64_t));
-    std::memcpy(out_c, h->pin + (size_t)count * sizeof(int64_t), (size_t)count * sizeof(int64_t));
-    std::memcpy(out_score, h->pin + (size_t)count * 2 * sizeof(int64_t), (size_t)count * sizeof(float));
+    std::memcpy(out_q, h->pin.p, (size_t)count * sizeof(int64_t));
+    std::memcpy(out_c, h->pin.p + (size_t)count * sizeof(int64_t), (size_t)count * sizeof(int64_t));
+    std::memcpy(out_score, h->pin.p + (size_t)count * 2 * sizeof(int64_t), (size_t)count * sizeof(float));
     return APSS_OK;
   }
   APSS_TRY(ensure(h, h->s_rowdst, (size_t)count));
@@ -4146,8 +4081,7 @@ int32_t apss_set_components(apss_handle *h, int32_t on) {
     if (h->cc_on) {
       APSS_TRY(enter(h));
       HIPCHK(h, hipStreamSynchronize(h->stream));  // (a hook may still be running on the arrays)
-      h->bytes_reserved -= h->cc.mem.bytes;
-      cc_release(h->cc);
+      h->cc = CcWork{};  // (its arrays take their bytes off the reservation as they go)
     }
     h->cc_on = false;
     const int64_t resets = h->cci.resets;
@@ -4183,7 +4117,7 @@ int32_t apss_components_dev(apss_handle *h, const int32_t **d_label, int64_t *ro
   APSS_TRY(enter(h));
   if (!h->cc_on) return fail(h, APSS_E_STATE, "apss_components_dev: the setting is off (apss_set_components)");
   APSS_TRY(label_components(h));
-  if (d_label) *d_label = h->n_rows > 0 ? h->cc.label : nullptr;
+  if (d_label) *d_label = h->n_rows > 0 ? h->cc.label.p : nullptr;
   if (rows) *rows = h->n_rows;
   return APSS_OK;
 }
@@ -4199,13 +4133,13 @@ int32_t apss_components_fetch(apss_handle *h, int64_t offset, int64_t count, int
     const int64_t piece = (int64_t)(kPinBytes / sizeof(int64_t));
     for (int64_t at = 0; at < count; at += piece) {
       const int64_t n = std::min(piece, count - at);
-      hipLaunchKernelGGL(k_cc_rep, dim3(cc_grid(n, kCcGridCap)), dim3(kCcThreads), 0, h->stream, (const int32_t *)h->cc.label, (const int64_t *)h->ext.p,
+      hipLaunchKernelGGL(k_cc_rep, dim3(cc_grid(n, kCcGridCap)), dim3(kCcThreads), 0, h->stream, (const int32_t *)h->cc.label.p, (const int64_t *)h->ext.p,
                          offset + at, n, h->n_rows, reinterpret_cast<int64_t *>(h->pack.p));
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipMemcpyAsync(out_rep_ext + at, h->pack.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     }
   }
-  if (out_label) HIPCHK(h, hipMemcpyAsync(out_label, h->cc.label + offset, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (out_label) HIPCHK(h, hipMemcpyAsync(out_label, h->cc.label.p + offset, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return APSS_OK;
 }

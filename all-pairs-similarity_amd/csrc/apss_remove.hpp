@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kRmThreads) void k_rm_drop(const RmDropArgs a) {
   const int64_t n_waves = (int64_t)gridDim.x * (kRmThreads / kRmWave);
   constexpr int64_t kSpan = (int64_t)kRmWave * kRmItems;
   const unsigned long long below = (1ull << lane) - 1ull;
-  // (the lists start at their arrays' first element, which hipMalloc aligns; a caller that ever hands in an offset view reads by element)
+  // (the lists start at their arrays' first element, which the device allocation aligns; a caller that ever hands in an offset view reads by element)
   const bool wide = ((reinterpret_cast<uintptr_t>(a.in_q) | reinterpret_cast<uintptr_t>(a.in_c) | reinterpret_cast<uintptr_t>(a.in_s)) & 15u) == 0;
   for (int64_t base = wave * kSpan; base < a.n; base += n_waves * kSpan) {  // (wave-uniform: every lane takes part in the ballots)
     const int64_t i0 = base + (int64_t)lane * kRmItems;

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <initializer_list>
 
+#include "apss_owned.hpp"
+
 namespace apss {
 namespace {
 
@@ -44,39 +46,48 @@ __device__ inline T wave_sum(T v) {
 }
 
 // ---- host side
-// A stage's device buffers are its own: what they hold in bytes, and the event pair its launches are timed with
-struct StageMem {
-  size_t bytes = 0;  // device bytes reserved
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+// The HIP back-end of the owning types (apss_owned.hpp): the one place in the library that reserves or frees device memory, pinned
+// memory, events and streams
+struct HipBackend {
+  using Error = hipError_t;
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  static constexpr Error ok = hipSuccess;
+  static Error alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void free(void *p) { (void)hipFree(p); }
+  static Error copy(void *dst, const void *src, size_t bytes, Stream s) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); }
+  static Error wait(Stream s) { return hipStreamSynchronize(s); }
+  static Error host_alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void host_free(void *p) { (void)hipHostFree(p); }
+  static Error event_make(Event *e, bool timing) { return timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming); }
+  static Error event_record(Event e, Stream s) { return hipEventRecord(e, s); }
+  static void event_drop(Event e) { (void)hipEventDestroy(e); }
+  static Error stream_make(Stream *s) { return hipStreamCreateWithFlags(s, hipStreamDefault); }
+  static void stream_drop(Stream s) { (void)hipStreamDestroy(s); }
+};
+template <class T>
+using DevBuf = DevArray<T, HipBackend>;
+using DevEvent = OwnedEvent<HipBackend>;
+template <class T>
+using PinBuf = PinnedArray<T, HipBackend>;
+using DevStream = OwnedStream<HipBackend>;
 
-  // p[old_n] becomes p[n], contents dropped.  (hipFree synchronises; a stage runs after the call's other work, nothing reads
-  // its buffers then)
-  template <class T>
-  hipError_t grow(T *&p, size_t old_n, size_t n) {
-    if (p) {
-      (void)hipFree(p);
-      p = nullptr;
-      bytes -= old_n * sizeof(T);
-    }
-    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-    if (e == hipSuccess) bytes += n * sizeof(T);
-    return e;
-  }
-  void free_all(std::initializer_list<void *> ptrs) {
-    for (void *p : ptrs)
-      if (p) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    *this = StageMem{};
+// A stage's arrays are its own members (sized by the stage: kGrowStage); what it shares is the ledger they are counted in (a
+// handle's reservation, set by run_stage; none for a group) and the event pair its launches are timed with
+struct StageMem {
+  size_t *ledger = nullptr;
+  DevEvent e0, e1;
+
+  // every b becomes b[n], contents dropped; the first failure ends it.  (The free synchronises; a stage runs after the call's other
+  // work, nothing reads its buffers then)
+  template <class... A>
+  hipError_t grow(size_t n, A &...b) {
+    return grow_all(kGrowStage, n, 0, nullptr, ledger, b...);
   }
 };
 
-// The timed stretch of a stage: begin_timed, the launches, end_timed_read.  Both create a missing event on first use.
-inline hipError_t begin_timed(hipStream_t stream, hipEvent_t &e0) {
-  hipError_t e;
-  if (!e0 && (e = hipEventCreate(&e0)) != hipSuccess) return e;
-  return hipEventRecord(e0, stream);
-}
+// The timed stretch of a stage: begin_timed, the launches, end_timed_read.  Both make a missing event on first use.
+inline hipError_t begin_timed(hipStream_t stream, DevEvent &e0) { return e0.record(stream); }
 
 // ... ends the stretch, copies the stage's few words to the host (a read of 0 bytes is skipped) and waits for the stream: ONE
 // synchronisation.  *ms: what the stretch took on the device
@@ -85,10 +96,9 @@ struct StageRead {
   const void *dev_src;
   size_t bytes;
 };
-inline hipError_t end_timed_read(hipStream_t stream, hipEvent_t e0, hipEvent_t &e1, std::initializer_list<StageRead> reads, float *ms) {
+inline hipError_t end_timed_read(hipStream_t stream, const DevEvent &e0, DevEvent &e1, std::initializer_list<StageRead> reads, float *ms) {
   hipError_t e;
-  if (!e1 && (e = hipEventCreate(&e1)) != hipSuccess) return e;
-  if ((e = hipEventRecord(e1, stream)) != hipSuccess) return e;
+  if ((e = e1.record(stream)) != hipSuccess) return e;
   for (const StageRead &r : reads)
     if (r.bytes && (e = hipMemcpyAsync(r.host_dst, r.dev_src, r.bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;

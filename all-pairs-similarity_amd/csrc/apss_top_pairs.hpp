@@ -364,22 +364,16 @@ __global__ __launch_bounds__(kTpThreads) void k_tp_write(const uint32_t *__restr
 
 // ---- host side: the stage's buffers (owned by a handle) and its launches
 struct TpWork {
-  unsigned long long *state = nullptr;  // [kTpWords]
-  unsigned long long *hist = nullptr;   // [(kTpScorePasses + kTpTieDigitsMax) * kTpBins]
-  uint32_t *tie = nullptr;              // [tie_cap] one index per pair at the K-th score, when a tie select runs
-  unsigned long long *key_a = nullptr, *key_b = nullptr;  // [sel_cap] a field's keys before / after its sort
-  uint32_t *perm_a = nullptr, *perm_b = nullptr;          // [sel_cap] the selection / the permutation
-  int32_t *out_q = nullptr, *out_c = nullptr;             // [sel_cap] the stage's output
-  float *out_s = nullptr;
-  char *tmp = nullptr;  // rocprim's scratch
-  size_t tie_cap = 0, sel_cap = 0, tmp_cap = 0;
+  DevBuf<unsigned long long> state;  // [kTpWords]
+  DevBuf<unsigned long long> hist;   // [(kTpScorePasses + kTpTieDigitsMax) * kTpBins]
+  DevBuf<uint32_t> tie;              // one index per pair at the K-th score, when a tie select runs
+  DevBuf<unsigned long long> key_a, key_b;  // [out_s.cap each, as the next four] a field's keys before / after its sort
+  DevBuf<uint32_t> perm_a, perm_b;          // the selection / the permutation
+  DevBuf<int32_t> out_q, out_c;             // the stage's output
+  DevBuf<float> out_s;
+  DevBuf<char> tmp;  // rocprim's scratch
   StageMem mem;
 };
-
-inline void tp_release(TpWork &w) {
-  w.mem.free_all({w.state, w.hist, w.tie, w.key_a, w.key_b, w.perm_a, w.perm_b, w.out_q, w.out_c, w.out_s, w.tmp});
-  w = TpWork{};
-}
 
 inline int tp_bits(int64_t n) {  // bits that hold 0 .. n - 1 (at least 1)
   int b = 1;
@@ -398,9 +392,9 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
   const int64_t m = std::min<int64_t>(K, n);
   const bool cut = n > K;
   constexpr size_t kHistWords = (size_t)(kTpScorePasses + kTpTieDigitsMax) * kTpBins;
-  if (!w.state) {
-    if ((e = w.mem.grow(w.state, 0, (size_t)kTpWords)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.hist, 0, kHistWords)) != hipSuccess) return e;
+  if (!w.state.p) {
+    if ((e = w.mem.grow((size_t)kTpWords, w.state)) != hipSuccess) return e;
+    if ((e = w.mem.grow(kHistWords, w.hist)) != hipSuccess) return e;
   }
   TpList l{};
   l.q = q, l.c = c, l.s = s, l.n = n, l.q_ext = q_ext, l.c_ext = c_ext, l.nq = nq, l.n_store = n_store;
@@ -408,26 +402,16 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
   l.pos_bits = l.slot_bits + tp_bits(nq);
   // the rank order's buffers, and the scratch of its widest sort
   size_t tmp_pos = 0, tmp64 = 0, tmp32 = 0;
-  if ((e = rocprim::radix_sort_pairs(nullptr, tmp_pos, w.key_a, w.key_b, w.perm_a, w.perm_b, (size_t)m, 0, (unsigned)l.pos_bits, stream)) != hipSuccess)
+  if ((e = rocprim::radix_sort_pairs(nullptr, tmp_pos, w.key_a.p, w.key_b.p, w.perm_a.p, w.perm_b.p, (size_t)m, 0, (unsigned)l.pos_bits, stream)) != hipSuccess)
     return e;
-  if ((e = rocprim::radix_sort_pairs(nullptr, tmp64, w.key_a, w.key_b, w.perm_a, w.perm_b, (size_t)m, 0, 64, stream)) != hipSuccess) return e;
-  if ((e = rocprim::radix_sort_pairs(nullptr, tmp32, (uint32_t *)nullptr, (uint32_t *)nullptr, w.perm_a, w.perm_b, (size_t)m, 0, 32, stream)) != hipSuccess)
+  if ((e = rocprim::radix_sort_pairs(nullptr, tmp64, w.key_a.p, w.key_b.p, w.perm_a.p, w.perm_b.p, (size_t)m, 0, 64, stream)) != hipSuccess) return e;
+  if ((e = rocprim::radix_sort_pairs(nullptr, tmp32, (uint32_t *)nullptr, (uint32_t *)nullptr, w.perm_a.p, w.perm_b.p, (size_t)m, 0, 32, stream)) != hipSuccess)
     return e;
   const size_t tmp_need = std::max(tmp_pos, std::max(tmp64, tmp32)) + 256;
-  if (tmp_need > w.tmp_cap) {
-    if ((e = w.mem.grow(w.tmp, w.tmp_cap, tmp_need)) != hipSuccess) return e;
-    w.tmp_cap = tmp_need;
-  }
-  if ((size_t)m > w.sel_cap) {
+  if ((e = w.mem.grow(tmp_need, w.tmp)) != hipSuccess) return e;
+  if ((size_t)m > w.out_s.cap) {  // (the array grown last says whether all seven have the room)
     const size_t cap = std::min<size_t>((size_t)APSS_TOP_PAIRS_MAX, std::max<size_t>((size_t)m + (size_t)m / 8, 1024));
-    if ((e = w.mem.grow(w.key_a, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.key_b, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.perm_a, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.perm_b, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_q, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_c, w.sel_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_s, w.sel_cap, cap)) != hipSuccess) return e;
-    w.sel_cap = cap;
+    if ((e = w.mem.grow(cap, w.key_a, w.key_b, w.perm_a, w.perm_b, w.out_q, w.out_c, w.out_s)) != hipSuccess) return e;
   }
   const auto grid = [&](int64_t items, int64_t per) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per - 1) / per, grid_cap))); };
   if ((e = begin_timed(stream, w.mem.e0)) != hipSuccess) return e;
@@ -437,18 +421,18 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
     // ---- 1. the K-th score key
     for (int k = 0; k < kTpWords; ++k) words[k] = 0ull;
     words[kTpRemaining] = (unsigned long long)K;
-    if ((e = hipMemcpyAsync(w.state, words, kTpWords * sizeof(unsigned long long), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(w.hist, 0, kHistWords * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(w.state.p, words, kTpWords * sizeof(unsigned long long), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.hist.p, 0, kHistWords * sizeof(unsigned long long), stream)) != hipSuccess) return e;
     // (words is read by the copy when the stream gets there; it is next written after the wait below)
     for (int p = 0; p < kTpScorePasses; ++p) {
-      unsigned long long *gh = w.hist + (size_t)p * kTpBins;
-      hipLaunchKernelGGL(k_tp_hist, grid(n, kTpTrips * kTpBlock), dim3(kTpThreads), 0, stream, s, n, (const unsigned long long *)w.state, p, gh);
-      hipLaunchKernelGGL(k_tp_pick, dim3(1), dim3(kTpBins), 0, stream, (const unsigned long long *)gh, w.state, (int)kTpT, 24 - 8 * p,
+      unsigned long long *gh = w.hist.p + (size_t)p * kTpBins;
+      hipLaunchKernelGGL(k_tp_hist, grid(n, kTpTrips * kTpBlock), dim3(kTpThreads), 0, stream, s, n, (const unsigned long long *)w.state.p, p, gh);
+      hipLaunchKernelGGL(k_tp_pick, dim3(1), dim3(kTpBins), 0, stream, (const unsigned long long *)gh, w.state.p, (int)kTpT, 24 - 8 * p,
                          p == kTpScorePasses - 1 ? 1 : 0, 0, (unsigned long long)K);
       info->launches += 2;
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(words, w.state, kTpWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(words, w.state.p, kTpWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;  // the first wait: (G, E) size the tie list
     above = (int64_t)words[kTpAbove];
     tied = (int64_t)words[kTpTied];
@@ -459,58 +443,54 @@ inline hipError_t tp_run(TpWork &w, hipStream_t stream, const int32_t *q, const 
     const uint32_t T = (uint32_t)words[kTpT];
     const int64_t want = K - above;  // ties kept
     const bool ties_all = want == tied;
-    if (!ties_all && (size_t)tied > w.tie_cap) {
-      const size_t cap = (size_t)tied + (size_t)tied / 8 + 1024;
-      if ((e = w.mem.grow(w.tie, w.tie_cap, cap)) != hipSuccess) return e;
-      w.tie_cap = cap;
-    }
+    if (!ties_all && (size_t)tied > w.tie.cap && (e = w.mem.grow((size_t)tied + (size_t)tied / 8 + 1024, w.tie)) != hipSuccess) return e;
     // ---- 2. collect
-    hipLaunchKernelGGL(k_tp_collect, grid(n, kTpTrips * kTpBlock), dim3(kTpThreads), 0, stream, s, n, w.state, w.perm_a, (unsigned long long)m, w.tie,
+    hipLaunchKernelGGL(k_tp_collect, grid(n, kTpTrips * kTpBlock), dim3(kTpThreads), 0, stream, s, n, w.state.p, w.perm_a.p, (unsigned long long)m, w.tie.p,
                        (unsigned long long)(ties_all ? 0 : tied), ties_all ? 1 : 0);
     ++info->launches;
     // ---- 3. ties: `remaining` is already the wanted rank among them
     if (!ties_all) {
       const int digits = 16 + (l.pos_bits + 7) / 8;
       for (int d = 0; d < digits; ++d) {
-        unsigned long long *gh = w.hist + (size_t)(kTpScorePasses + d) * kTpBins;
-        hipLaunchKernelGGL(k_tp_tie_hist, grid(tied, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)w.tie, tied, l,
-                           (const unsigned long long *)w.state, d, gh);
-        hipLaunchKernelGGL(k_tp_pick, dim3(1), dim3(kTpBins), 0, stream, (const unsigned long long *)gh, w.state, kTpTie0 + d / 8,
+        unsigned long long *gh = w.hist.p + (size_t)(kTpScorePasses + d) * kTpBins;
+        hipLaunchKernelGGL(k_tp_tie_hist, grid(tied, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)w.tie.p, tied, l,
+                           (const unsigned long long *)w.state.p, d, gh);
+        hipLaunchKernelGGL(k_tp_pick, dim3(1), dim3(kTpBins), 0, stream, (const unsigned long long *)gh, w.state.p, kTpTie0 + d / 8,
                            56 - 8 * (d % 8), 0, 1, 0ull);
         info->launches += 2;
       }
-      hipLaunchKernelGGL(k_tp_tie_collect, grid(tied, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)w.tie, tied, l, w.state,
-                         w.perm_a, (unsigned long long)m);
+      hipLaunchKernelGGL(k_tp_tie_collect, grid(tied, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)w.tie.p, tied, l, w.state.p,
+                         w.perm_a.p, (unsigned long long)m);
       ++info->launches;
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    selection = w.perm_a;
+    selection = w.perm_a.p;
     info->above = above;
     info->tied = tied;
     info->tied_kept = want;
     info->kth_score = (double)topk_key_inv(~T);
   }
   // ---- 4. rank order: stable sorts, least significant field first
-  uint32_t *pa = w.perm_a, *pb = w.perm_b;
+  uint32_t *pa = w.perm_a.p, *pb = w.perm_b.p;
   for (int level = 0; level < 4; ++level) {
     hipLaunchKernelGGL(k_tp_keys, grid(m, kTpThreads), dim3(kTpThreads), 0, stream, level, level == 0 ? selection : (const uint32_t *)pa, m, l,
-                       w.key_a, reinterpret_cast<uint32_t *>(w.key_a), pa);
+                       w.key_a.p, reinterpret_cast<uint32_t *>(w.key_a.p), pa);
     ++info->launches;
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    size_t tmp_bytes = w.tmp_cap;
+    size_t tmp_bytes = w.tmp.cap;
     if (level == 3)
-      e = rocprim::radix_sort_pairs((void *)w.tmp, tmp_bytes, reinterpret_cast<uint32_t *>(w.key_a), reinterpret_cast<uint32_t *>(w.key_b), pa, pb,
+      e = rocprim::radix_sort_pairs((void *)w.tmp.p, tmp_bytes, reinterpret_cast<uint32_t *>(w.key_a.p), reinterpret_cast<uint32_t *>(w.key_b.p), pa, pb,
                                     (size_t)m, 0, 32, stream);
     else
-      e = rocprim::radix_sort_pairs((void *)w.tmp, tmp_bytes, w.key_a, w.key_b, pa, pb, (size_t)m, 0, level == 0 ? (unsigned)l.pos_bits : 64u, stream);
+      e = rocprim::radix_sort_pairs((void *)w.tmp.p, tmp_bytes, w.key_a.p, w.key_b.p, pa, pb, (size_t)m, 0, level == 0 ? (unsigned)l.pos_bits : 64u, stream);
     if (e != hipSuccess) return e;
     std::swap(pa, pb);
   }
-  hipLaunchKernelGGL(k_tp_write, grid(m, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)pa, m, l, w.out_q, w.out_c, w.out_s);
+  hipLaunchKernelGGL(k_tp_write, grid(m, kTpThreads), dim3(kTpThreads), 0, stream, (const uint32_t *)pa, m, l, w.out_q.p, w.out_c.p, w.out_s.p);
   ++info->launches;
   if ((e = hipGetLastError()) != hipSuccess) return e;
   float ms = 0.f;  // (the second wait ends the stage)
-  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.state, cut ? kTpWords * sizeof(unsigned long long) : 0}}, &ms)) != hipSuccess) return e;
+  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.state.p, cut ? kTpWords * sizeof(unsigned long long) : 0}}, &ms)) != hipSuccess) return e;
   if (cut && (int64_t)words[kTpSelCursor] != K) {
     *bad = "the selection does not hold K pairs";
     return hipErrorUnknown;

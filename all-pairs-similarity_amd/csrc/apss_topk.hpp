@@ -390,19 +390,13 @@ __global__ __launch_bounds__(kTopkThreads) void k_topk_select(const int64_t *__r
 
 // ---- host side: the pass's buffers (owned by a handle, or by a group for the list behind its exchange) and its launches
 struct TopkWork {
-  unsigned int *cnt = nullptr;
-  int64_t *seg_start = nullptr, *out_start = nullptr;
-  unsigned long long *info = nullptr;
-  int32_t *seg_c = nullptr, *out_q = nullptr, *out_c = nullptr;
-  float *seg_s = nullptr, *out_s = nullptr;
-  size_t rows_cap = 0, seg_cap = 0, out_cap = 0;
+  DevBuf<unsigned int> cnt;
+  DevBuf<int64_t> seg_start, out_start;
+  DevBuf<unsigned long long> info;
+  DevBuf<int32_t> seg_c, out_q, out_c;
+  DevBuf<float> seg_s, out_s;
   StageMem mem;
 };
-
-inline void topk_release(TopkWork &w) {
-  w.mem.free_all({w.cnt, w.seg_start, w.out_start, w.info, w.seg_c, w.out_q, w.out_c, w.seg_s, w.out_s});
-  w = TopkWork{};
-}
 
 // Runs the pass over (q, c, s)[0, n) on `stream` and waits for it (the one host read: the four info words).  The new list is
 // w.out_*[0, info->kept).  n == 0: nothing is launched.  info: k, pairs_over_theta, kept, queries_cut, longest_segment,
@@ -419,43 +413,30 @@ inline hipError_t topk_run(TopkWork &w, hipStream_t stream, const int32_t *q, co
   info->select_launches = 0;
   if (n <= 0 || nq <= 0) return hipSuccess;
   hipError_t e;
-  if (!w.info && (e = w.mem.grow(w.info, 0, (size_t)kTopkInfoWords)) != hipSuccess) return e;
-  if ((size_t)nq + 1 > w.rows_cap) {
-    const size_t cap = std::max<size_t>((size_t)nq + 1, w.rows_cap + w.rows_cap / 2);
-    if ((e = w.mem.grow(w.cnt, w.rows_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.seg_start, w.rows_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_start, w.rows_cap, cap)) != hipSuccess) return e;
-    w.rows_cap = cap;
+  if (!w.info.p && (e = w.mem.grow((size_t)kTopkInfoWords, w.info)) != hipSuccess) return e;
+  // (arrays that grow together share a capacity; the one grown last says whether all of them have it)
+  if ((size_t)nq + 1 > w.out_start.cap) {
+    const size_t cap = std::max<size_t>((size_t)nq + 1, w.out_start.cap + w.out_start.cap / 2);
+    if ((e = w.mem.grow(cap, w.cnt, w.seg_start, w.out_start)) != hipSuccess) return e;
   }
-  if ((size_t)n > w.seg_cap) {
-    const size_t cap = (size_t)n + (size_t)n / 8 + 1024;
-    if ((e = w.mem.grow(w.seg_c, w.seg_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.seg_s, w.seg_cap, cap)) != hipSuccess) return e;
-    w.seg_cap = cap;
-  }
+  if ((size_t)n > w.seg_s.cap && (e = w.mem.grow((size_t)n + (size_t)n / 8 + 1024, w.seg_c, w.seg_s)) != hipSuccess) return e;
   const size_t out_need = (size_t)std::min<int64_t>(n, nq * (int64_t)k);
-  if (out_need > w.out_cap) {
-    const size_t cap = out_need + out_need / 8 + 1024;
-    if ((e = w.mem.grow(w.out_q, w.out_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_c, w.out_cap, cap)) != hipSuccess) return e;
-    if ((e = w.mem.grow(w.out_s, w.out_cap, cap)) != hipSuccess) return e;
-    w.out_cap = cap;
-  }
+  if (out_need > w.out_s.cap && (e = w.mem.grow(out_need + out_need / 8 + 1024, w.out_q, w.out_c, w.out_s)) != hipSuccess) return e;
   const unsigned blocks = (unsigned)((n + kTopkBlock - 1) / kTopkBlock);
-  if ((e = hipMemsetAsync(w.cnt, 0, ((size_t)nq + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(w.cnt.p, 0, ((size_t)nq + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e;
   if ((e = begin_timed(stream, w.mem.e0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_topk_count, dim3(blocks), dim3(kTopkThreads), 0, stream, q, n, (int32_t)nq, w.cnt);
-  hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(kTopkScanThreads), 0, stream, w.cnt, (int32_t)nq, k, w.seg_start, w.out_start, w.info,
+  hipLaunchKernelGGL(k_topk_count, dim3(blocks), dim3(kTopkThreads), 0, stream, q, n, (int32_t)nq, w.cnt.p);
+  hipLaunchKernelGGL(k_topk_scan, dim3(1), dim3(kTopkScanThreads), 0, stream, w.cnt.p, (int32_t)nq, k, w.seg_start.p, w.out_start.p, w.info.p,
                      uncut);
   hipLaunchKernelGGL(k_topk_scatter, dim3(blocks), dim3(kTopkThreads), 0, stream, q, c, s, n, (int32_t)nq,
-                     (const int64_t *)w.seg_start, w.cnt, w.seg_c, w.seg_s);
-  hipLaunchKernelGGL(k_topk_select, dim3((unsigned)nq), dim3(kTopkThreads), 0, stream, (const int64_t *)w.seg_start,
-                     (const int64_t *)w.out_start, (const int32_t *)w.seg_c, (const float *)w.seg_s, c_ext, n_store, k, w.out_q, w.out_c,
-                     w.out_s);
+                     (const int64_t *)w.seg_start.p, w.cnt.p, w.seg_c.p, w.seg_s.p);
+  hipLaunchKernelGGL(k_topk_select, dim3((unsigned)nq), dim3(kTopkThreads), 0, stream, (const int64_t *)w.seg_start.p,
+                     (const int64_t *)w.out_start.p, (const int32_t *)w.seg_c.p, (const float *)w.seg_s.p, c_ext, n_store, k, w.out_q.p, w.out_c.p,
+                     w.out_s.p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   unsigned long long words[kTopkInfoWords] = {0, 0, 0, 0};
   float ms = 0.f;
-  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.info, sizeof(words)}}, &ms)) != hipSuccess) return e;
+  if ((e = end_timed_read(stream, w.mem.e0, w.mem.e1, {{words, w.info.p, sizeof(words)}}, &ms)) != hipSuccess) return e;
   info->kept = (int64_t)words[kTopkKept];
   info->queries_cut = (int64_t)words[kTopkCut];
   info->longest_segment = (int64_t)words[kTopkLongest];

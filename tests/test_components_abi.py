@@ -128,8 +128,10 @@ def test_every_binding_carries_the_feature():
     # no new site that makes an event: the stage's four come out of begin_timed / end_timed_read (apss_stage.hpp)
     made = {f: open(os.path.join(PKG, "csrc", f)).read().count("hipEventCreate") for f in os.listdir(os.path.join(PKG, "csrc"))
             if f.endswith((".hip", ".hpp"))}
-    # (apss_create's four and wl_ev's hipEventCreateWithFlags in the handle, the two of begin_timed / end_timed_read)
-    assert {f: n for f, n in made.items() if n} == {"apss_hip.hip": 5, "apss_stage.hpp": 2}
+    # (every event is an owner that makes itself where it is first recorded: the timed and the untimed call of the HIP back-end,
+    # the only file that may make or destroy one -- tests/test_owned_host.py holds the frees to the same file; there were seven sites)
+    assert {f: n for f, n in made.items() if n} == {"apss_stage.hpp": 2}
+    assert sum(made.values()) <= 7
     for doc in ("README.md", "INTEGRATION.md", "DESIGN.md"):
         text = open(os.path.join(ROOT, doc)).read()
         assert "apss_set_components" in text, doc
