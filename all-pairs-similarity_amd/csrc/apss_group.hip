@@ -19,15 +19,13 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <functional>
-#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <rccl/rccl.h>
@@ -36,6 +34,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/apss.h"
+#include "apss_lockstep.hpp"
 #include "apss_topk.hpp"
 
 namespace {
@@ -109,36 +108,11 @@ Rccl *load_rccl() {
   return &r;
 }
 
-// ---- a reusable barrier for the member threads of one call (C++17: no std::barrier).  wait() returns the call's failure flag
-// as the LAST thread to arrive read it, under the mutex: every thread of one generation takes the same go / no-go decision,
-// even when a thread that already left fails (and sets the flag) before a slower one has woken up.
-class Barrier {
- public:
-  Barrier(int n, const std::atomic<int> *failed) : n_(n), failed_(failed) {}
-  bool wait() {
-    std::unique_lock<std::mutex> lk(mu_);
-    const uint64_t gen = gen_;
-    if (++count_ == n_) {
-      count_ = 0;
-      snap_ = failed_->load() != 0;
-      ++gen_;
-      cv_.notify_all();
-    } else {
-      cv_.wait(lk, [&] { return gen_ != gen; });
-    }
-    return snap_;  // (the next generation cannot overwrite it before this thread arrives there)
-  }
-
- private:
-  std::mutex mu_;
-  std::condition_variable cv_;
-  int n_, count_ = 0;
-  uint64_t gen_ = 0;
-  const std::atomic<int> *failed_;
-  bool snap_ = false;
-};
-
+using apss::Barrier;
 using apss::DevBuf;
+using apss::Lockstep;
+using apss::When;
+static_assert(APSS_OK == apss::kLockstepOk, "apss_lockstep.hpp takes 0 for success");
 
 // ---- kernels of the exchange (everything else is the shard handles' work)
 // candidate (query row of the batch, candidate slot) -> one sortable 8-B key
@@ -398,13 +372,18 @@ int32_t gfail(apss_group *g, int32_t rc, const std::string &msg) {
   g->err = msg;
   return rc;
 }
+// (a member's: its thread publishes the code, run_members reports the message)
+int32_t mfail(apss_group::Member &M, int32_t rc, const std::string &msg) {
+  M.err = msg;
+  return rc;
+}
+inline int32_t hip_rc(hipError_t e) { return e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE; }
 
 #define GHIP(g, M, expr)                                                                            \
   do {                                                                                               \
     hipError_t e_ = (expr);                                                                          \
     if (e_ != hipSuccess) {                                                                          \
-      (M).err = std::string(#expr) + ": " + hipGetErrorString(e_);                                   \
-      return e_ == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;                               \
+      return mfail((M), hip_rc(e_), std::string(#expr) + ": " + hipGetErrorString(e_));              \
     }                                                                                                \
   } while (0)
 
@@ -414,6 +393,30 @@ template <class... A>
 int32_t ensure(apss_group::Member &M, size_t n, A &...b) {
   GHIP(nullptr, M, apss::grow_all(apss::kGrowGroup, n, 0, M.stream, nullptr, b...));
   return APSS_OK;
+}
+
+// a few words of M's device into a host variable, on M's stream, which is waited for
+template <class T>
+int32_t read_back(apss_group::Member &M, T *host, const T *dev, size_t n = 1) {
+  GHIP(nullptr, M, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, M.stream));
+  GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+  return APSS_OK;
+}
+
+int32_t set_member_device(apss_group::Member &M) {
+  return hipSetDevice(M.dev) == hipSuccess ? APSS_OK : mfail(M, APSS_E_DEVICE, "hipSetDevice failed");
+}
+
+// fn(m, cx) for the n members of a call (member 0 on the caller's thread), the caller's device current again behind them; a
+// failed call reports its lowest-numbered failed member, or `fallback`
+template <class Ctx>
+int32_t run_members(apss_group *g, int n, void (*fn)(int, Ctx *), Ctx *cx, const char *fallback) {
+  apss::run_members(n, fn, cx);
+  (void)hipSetDevice(g->m[0].dev);
+  if (!cx->failed.load()) return APSS_OK;
+  const apss::MemberFailure f = apss::first_failure(
+      n, [&](int m) { return g->m[(size_t)m].rc; }, [&](int m) -> const std::string & { return g->m[(size_t)m].err; }, APSS_E_STATE, fallback);
+  return gfail(g, f.rc, f.msg);
 }
 
 // one batch as the caller handed it in
@@ -649,7 +652,8 @@ int32_t create_members(apss_group *g, const Batch &b) {
 
 // ---- one member's share of a call; every member thread runs this, the barriers keep the phases in step.  A failure is
 // published BEFORE the next barrier, and every thread acts on the flag as the barrier returned it: they leave (or skip a
-// collective) together.  A grid has one barrier per row range (its T members are a term-sharded group of their own and never
+// collective) together -- Lockstep::step (apss_lockstep.hpp) is that rule, and the only place a thread of this file waits at a
+// barrier or raises the flag.  A grid has one barrier per row range (its T members are a term-sharded group of their own and never
 // wait for another row range) and ONE failure flag for all T x D threads.
 
 // a phase's batch as ONE member reads it (host form: values; device form, on the member's device: d_values)
@@ -683,7 +687,7 @@ struct CallCtx {
   apss_group *g;
   int mode;  // 0 insert, 1 query (frozen index), 2 insert-and-query
   Batch b;
-  std::vector<Barrier *> bar;    // per row range
+  std::deque<Barrier> bar;       // per row range
   std::vector<int64_t> span_lo;  // grids: span k = rows [span_lo[k], span_lo[k + 1]) of the batch
   std::vector<RangePlan> plan;   // grids: per row range
   std::atomic<int> failed{0};
@@ -743,14 +747,11 @@ int32_t member_slice(apss_group::Member &M, const CallCtx &cx, const MemberBatch
   hipLaunchKernelGGL(k_span_offsets, dim3(1), dim3(128), 0, M.stream, whole.rowptr, sb, M.sp_off.p);
   GHIP(nullptr, M, hipGetLastError());
   int64_t ent[kMaxSpans + 1];
-  GHIP(nullptr, M, hipMemcpyAsync(ent, M.sp_off.p, (size_t)(D + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, M.stream));
-  GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+  if ((rc = read_back(M, ent, M.sp_off.p, (size_t)(D + 1))) != APSS_OK) return rc;
   bool sane = ent[0] == 0 && ent[D] == whole.nnz;
   for (int k = 0; k < D; ++k) sane = sane && ent[k] <= ent[k + 1];
-  if (!sane) {  // (the gathers below read entries [ent[k], ent[k + 1]) of arrays that are nnz long)
-    M.err = "d_rowptr is not the row offsets of a batch of nnz entries";
-    return APSS_E_INVALID;
-  }
+  // (the gathers below read entries [ent[k], ent[k + 1]) of arrays that are nnz long)
+  if (!sane) return mfail(M, APSS_E_INVALID, "d_rowptr is not the row offsets of a batch of nnz entries");
   for (int slot = 0; slot < 2; ++slot) {
     SpanTable t{};
     std::vector<int> one(1, P.span);
@@ -791,6 +792,7 @@ int32_t member_slice(apss_group::Member &M, const CallCtx &cx, const MemberBatch
 // step 1: the handle call of a phase (mode as CallCtx::mode), and what it adds to the member's sums of the call.  A
 // mirrored phase found each pair once and reports it twice: the reference's two-directional probe visits twice as much.
 int32_t member_phase1(apss_group::Member &M, int mode, const MemberBatch &b, bool mirrored) {
+  const auto t0 = Clock::now();
   int64_t n_res = 0;
   int32_t rc;
   if (!b.on_device) {
@@ -816,6 +818,7 @@ int32_t member_phase1(apss_group::Member &M, int mode, const MemberBatch &b, boo
     M.probe_ms += ms.probe_ms;
     M.head_ms += ms.head_ms;
   }
+  M.member_ms += ms_since(t0);
   return rc;
 }
 
@@ -827,10 +830,7 @@ int32_t member_pack(apss_group::Member &M, int64_t total, int64_t my_off) {
     const int32_t *dq = nullptr, *dc = nullptr;
     const float *ds = nullptr;
     int64_t n = 0;
-    if ((rc = apss_results_dev(M.h, &dq, &dc, &ds, &n)) != APSS_OK) {
-      M.err = apss_last_error(M.h);
-      return rc;
-    }
+    if ((rc = apss_results_dev(M.h, &dq, &dc, &ds, &n)) != APSS_OK) return mfail(M, rc, apss_last_error(M.h));
     hipLaunchKernelGGL(k_pack_keys, dim3(grid_for(M.n_cand)), dim3(256), 0, M.stream, dq, dc, M.n_cand, M.keys.p + my_off);
     GHIP(nullptr, M, hipGetLastError());
   }
@@ -847,8 +847,7 @@ int32_t member_union(apss_group::Member &M, int64_t total, int key_bits) {
   GHIP(nullptr, M, rocprim::radix_sort_keys((void *)M.tmp.p, a, M.keys.p, M.sorted.p, (size_t)total, 0, (unsigned)key_bits, M.stream));
   GHIP(nullptr, M, rocprim::unique((void *)M.tmp.p, bsz, M.sorted.p, M.uniq.p, M.count.p, (size_t)total, rocprim::equal_to<unsigned long long>(), M.stream));
   unsigned long long nu = 0;
-  GHIP(nullptr, M, hipMemcpyAsync(&nu, M.count.p, sizeof(nu), hipMemcpyDeviceToHost, M.stream));
-  GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+  if ((rc = read_back(M, &nu, M.count.p)) != APSS_OK) return rc;
   M.n_union = (int64_t)nu;
   if ((rc = ensure(M, (size_t)std::max<int64_t>(1, M.n_union), M.uq, M.uc, M.partial, M.sum)) != APSS_OK) return rc;
   if (M.n_union > 0) {
@@ -866,10 +865,7 @@ int32_t append_triples(apss_group::Member &M, apss_group::Range &R, const int32_
   const int64_t add = mirrored ? 2 * n : n;
   const int64_t *d_store = nullptr, *d_query = nullptr;
   int32_t rc = apss_ext_ids_dev(M.h, &d_store, &d_query);
-  if (rc != APSS_OK || !d_store || !d_query) {
-    M.err = "the member's external ids are gone";
-    return APSS_E_STATE;
-  }
+  if (rc != APSS_OK || !d_store || !d_query) return mfail(M, APSS_E_STATE, "the member's external ids are gone");
   GHIP(nullptr, M, apss::grow_all(apss::kGrowGroupKeep, (size_t)(R.n_tri + add), (size_t)R.n_tri, M.stream, nullptr, R.tri_q, R.tri_c, R.tri_s));
   hipLaunchKernelGGL(k_triples, dim3(grid_for(n)), dim3(256), 0, M.stream, q_row, c_slot, score, d_query, d_store, n, mirrored ? 1 : 0,
                      R.tri_q.p + R.n_tri, R.tri_c.p + R.n_tri, R.tri_s.p + R.n_tri);
@@ -880,198 +876,204 @@ int32_t append_triples(apss_group::Member &M, apss_group::Range &R, const int32_
   return APSS_OK;
 }
 
-// One phase of a call for member m = (row range j, term range i): the handle call on the phase's batch (step 1), then the
-// exchange among the T members of the row range (steps 2-4) and, on a grid, the phase's triples.  A plain group's call is one
-// phase; a grid's insert-and-query is two (its own span, then the outside batch as a query).  false: the call has failed, and
-// every thread of the row range has taken that decision at the same barrier.
-bool member_phase(int m, CallCtx &cx, int mode, const MemberBatch &b, bool mirrored) {
-  apss_group *g = cx.g;
-  const int T = g->T;
-  const int j = m / T, i = m % T;
-  apss_group::Member &M = g->m[(size_t)m];
-  apss_group::Member *peers = &g->m[(size_t)(j * T)];  // the row range's members, by term range
-  apss_group::Range &R = g->rr[(size_t)j];
-  Barrier &bar = *cx.bar[(size_t)j];
-  Rccl *r = g->exchange == APSS_EXCHANGE_RCCL ? load_rccl() : nullptr;
-  auto fail_here = [&](int32_t rc) {
-    M.rc = rc;
-    cx.failed.store(1);
-  };
-  M.n_cand = M.n_union = 0;
-  if (i == 0) R.n_phase = 0;
-  const auto t0 = Clock::now();
-  if (!cx.failed.load()) {
-    const int32_t rc = member_phase1(M, mode, b, mirrored);
-    if (rc != APSS_OK) fail_here(rc);
+// ---- one phase of a call, as one member sees it: the stages below take this context, member_phase sequences them
+struct Phase {
+  apss_group *g;
+  apss_group::Member &M, *peers;  // M = peers[i] of the row range's T members, by term range
+  apss_group::Range &R;
+  int T, i, mode;                 // (mode as CallCtx::mode)
+  const MemberBatch &b;           // the phase's batch
+  bool mirrored;
+  Lockstep &ls;
+  apss::ExchangeOffsets x;        // member k's candidates sit at x.off[k] of every member's key buffer
+  int32_t (*gather)(Phase &) = nullptr, (*reduce)(Phase &) = nullptr;  // the exchange's transport (g->exchange)
+  const float *total_score = nullptr;                                  // the reduced scores, once `reduce` has run
+  Clock::time_point tx;                                                // the exchange began
+};
+
+// all-gather of the candidate lists, in place: member k's list sits at off[k] in every member's buffer
+int32_t gather_rccl(Phase &P) {
+  apss_group::Member &M = P.M;
+  Rccl *r = load_rccl();
+  ncclResult_t nr = r->GroupStart();
+  for (int k = 0; k < P.T && nr == ncclSuccess; ++k) {
+    const int64_t nk = P.peers[k].n_cand;
+    if (nk > 0) nr = r->Broadcast(M.keys.p + P.x.off[(size_t)k], M.keys.p + P.x.off[(size_t)k], (size_t)nk, ncclUint64, k, M.comm, M.stream);
   }
-  M.member_ms += ms_since(t0);
-  if (bar.wait()) return false;  // ---- B1: every member's candidate count (or failure) is known
-  if (mode == 0) return true;
-  if (g->exchange == APSS_EXCHANGE_NONE) {  // one member per row range: its answer is final
-    R.n_phase = M.n_cand;
-    if (g->D > 1 && M.n_cand > 0) {
-      const int32_t *dq = nullptr, *dc = nullptr;
-      const float *ds = nullptr;
-      int64_t n = 0;
-      int32_t rc = apss_results_dev(M.h, &dq, &dc, &ds, &n);
-      if (rc != APSS_OK) M.err = apss_last_error(M.h);
-      else rc = append_triples(M, R, dq, dc, ds, n, mirrored);
-      if (rc != APSS_OK) fail_here(rc);
-    }
-    return !bar.wait();
-  }
-  const auto tx = Clock::now();
-  int64_t total = 0, my_off = 0, least = INT64_MAX;
-  std::vector<int64_t> off((size_t)T + 1, 0);
-  for (int k = 0; k < T; ++k) {
-    if (k == i) my_off = total;
-    off[(size_t)k] = total;
-    total += peers[k].n_cand;
-    least = std::min(least, peers[k].n_cand);
-  }
-  off[(size_t)T] = total;
-  if (total == 0) return true;  // nothing to exchange: every member leaves together
-  if (i == 0) R.gather_bytes += 8 * (total - least);
-  {
-    const int32_t rc = member_pack(M, total, my_off);
-    if (rc != APSS_OK) fail_here(rc);
-  }
-  if (bar.wait()) return false;  // ---- B2: every list is packed
-  // ---- step 2: all-gather of the candidate lists (in place: member k's list sits at off[k] in every member's buffer)
+  const ncclResult_t ne = r->GroupEnd();
+  if (nr == ncclSuccess) nr = ne;
+  if (nr != ncclSuccess) return mfail(M, APSS_E_DEVICE, std::string("RCCL all-gather of candidate lists: ") + r->GetErrorString(nr));
+  return APSS_OK;
+}
+
+int32_t gather_copies(Phase &P) {
+  apss_group::Member &M = P.M;
   int32_t rc = APSS_OK;
-  if (g->exchange == APSS_EXCHANGE_RCCL) {
-    ncclResult_t nr = r->GroupStart();
-    for (int k = 0; k < T && nr == ncclSuccess; ++k) {
-      const int64_t nk = peers[k].n_cand;
-      if (nk > 0) nr = r->Broadcast(M.keys.p + off[(size_t)k], M.keys.p + off[(size_t)k], (size_t)nk, ncclUint64, k, M.comm, M.stream);
-    }
-    const ncclResult_t ne = r->GroupEnd();
-    if (nr == ncclSuccess) nr = ne;
-    if (nr != ncclSuccess) {
-      M.err = std::string("RCCL all-gather of candidate lists: ") + r->GetErrorString(nr);
-      rc = APSS_E_DEVICE;
-    }
-  } else {
-    for (int k = 0; k < T && rc == APSS_OK; ++k) {
-      const int64_t nk = peers[k].n_cand;
-      if (k == i || nk == 0) continue;
-      const hipError_t e = hipMemcpyAsync(M.keys.p + off[(size_t)k], peers[k].keys.p + off[(size_t)k], (size_t)nk * sizeof(unsigned long long),
-                                          hipMemcpyDefault, M.stream);
-      if (e != hipSuccess) {
-        M.err = std::string("candidate list copy: ") + hipGetErrorString(e);
-        rc = APSS_E_DEVICE;
-      }
-    }
+  for (int k = 0; k < P.T && rc == APSS_OK; ++k) {
+    const int64_t nk = P.peers[k].n_cand;
+    if (k == P.i || nk == 0) continue;
+    const hipError_t e = hipMemcpyAsync(M.keys.p + P.x.off[(size_t)k], P.peers[k].keys.p + P.x.off[(size_t)k], (size_t)nk * sizeof(unsigned long long),
+                                        hipMemcpyDefault, M.stream);
+    if (e != hipSuccess) rc = mfail(M, APSS_E_DEVICE, std::string("candidate list copy: ") + hipGetErrorString(e));
   }
-  // sorted union (the same list in the same order on every member), then this member's exact partial score of every pair
-  if (rc == APSS_OK) {
-    int q_bits = 1;  // (query rows are rows of the PHASE's batch: a span or an outside batch)
-    while (q_bits < 31 && (1LL << q_bits) < std::max<int64_t>(2, b.n)) ++q_bits;
-    rc = member_union(M, total, 32 + q_bits);
-  }
+  return rc;
+}
+
+// B3: gather, then the sorted union (the same list in the same order on every member), then this member's exact partial score
+// of every pair
+int32_t phase_gather_union_partials(Phase &P) {
+  apss_group::Member &M = P.M;
+  int32_t rc = P.gather(P);
+  // (query rows are rows of the PHASE's batch: a span or an outside batch)
+  if (rc == APSS_OK) rc = member_union(M, P.x.total, apss::exchange_key_bits(P.b.n));
   if (rc == APSS_OK && M.n_union > 0) {
     const auto tp = Clock::now();
     rc = apss_partial_scores_dev(M.h, M.n_union, M.uq.p, M.uc.p, M.partial.p);  // (synchronises the member's stream)
     if (rc != APSS_OK) M.err = apss_last_error(M.h);
     M.partial_ms += ms_since(tp);
   }
-  if (rc != APSS_OK) fail_here(rc);
-  if (bar.wait()) return false;  // ---- B3: every member's partial scores are complete
+  return rc;
+}
+
+// B3b: the members agree on the union's size.  It cannot fail -- the same sort of the same keys -- and is checked because a
+// collective of unequal counts hangs: the decision to run the collective is this barrier's, the same on every member.
+int32_t phase_agree(Phase &P) {
+  return P.peers[0].n_union == P.M.n_union ? APSS_OK : mfail(P.M, APSS_E_STATE, "members disagree on the candidate union");
+}
+
+// all-reduce(SUM) of the partial scores: every member of the RCCL exchange holds the sums ...
+int32_t reduce_rccl(Phase &P) {
+  apss_group::Member &M = P.M;
+  Rccl *r = load_rccl();
+  const ncclResult_t nr = r->AllReduce(M.partial.p, M.sum.p, (size_t)M.n_union, ncclFloat, ncclSum, M.comm, M.stream);
+  if (nr != ncclSuccess) return mfail(M, APSS_E_DEVICE, std::string("RCCL all-reduce of partial scores: ") + r->GetErrorString(nr));
+  P.total_score = M.sum.p;
+  return APSS_OK;
+}
+
+// ... the copies exchange sums on the row range's first member only, which reads its peers' vectors
+int32_t reduce_copies(Phase &P) {
+  apss_group::Member &M = P.M;
+  if (P.i != 0) return APSS_OK;
   const int64_t nu = M.n_union;
-  if (peers[0].n_union != nu) {  // (cannot happen: the same sort of the same keys; checked because a collective of unequal counts hangs)
-    M.err = "members disagree on the candidate union";
-    fail_here(APSS_E_STATE);
-  }
-  if (bar.wait()) return false;  // ---- B3b: (the decision to run the collective is this barrier's, the same on every member)
-  // ---- step 4: all-reduce(SUM) of the partial scores
-  const float *total_score = M.partial.p;
-  bool ok = true;
-  if (nu > 0) {
-    if (g->exchange == APSS_EXCHANGE_RCCL) {
-      const ncclResult_t nr = r->AllReduce(M.partial.p, M.sum.p, (size_t)nu, ncclFloat, ncclSum, M.comm, M.stream);
-      if (nr != ncclSuccess) {
-        M.err = std::string("RCCL all-reduce of partial scores: ") + r->GetErrorString(nr);
-        fail_here(APSS_E_DEVICE);
-        ok = false;
+  hipError_t e = hipMemcpyAsync(M.sum.p, M.partial.p, (size_t)nu * sizeof(float), hipMemcpyDeviceToDevice, M.stream);
+  for (int k = 1; k < P.T && e == hipSuccess; ++k) {
+    const float *src = P.peers[k].partial.p;
+    if (P.peers[k].dev != M.dev) {  // (another device: bring the vector over first)
+      if (ensure(M, (size_t)nu, M.stage) != APSS_OK) {
+        e = hipErrorOutOfMemory;
+        break;
       }
-      total_score = M.sum.p;
-    } else if (i == 0) {
-      hipError_t e = hipMemcpyAsync(M.sum.p, M.partial.p, (size_t)nu * sizeof(float), hipMemcpyDeviceToDevice, M.stream);
-      for (int k = 1; k < T && e == hipSuccess; ++k) {
-        const float *src = peers[k].partial.p;
-        if (peers[k].dev != M.dev) {  // (another device: bring the vector over first)
-          if (ensure(M, (size_t)nu, M.stage) != APSS_OK) {
-            e = hipErrorOutOfMemory;
-            break;
-          }
-          e = hipMemcpyAsync(M.stage.p, src, (size_t)nu * sizeof(float), hipMemcpyDefault, M.stream);
-          src = M.stage.p;
-        }
-        if (e == hipSuccess) {
-          hipLaunchKernelGGL(k_accumulate, dim3(grid_for(nu)), dim3(256), 0, M.stream, M.sum.p, src, nu);
-          e = hipGetLastError();
-        }
-      }
-      if (e != hipSuccess) {
-        M.err = std::string("partial score reduction: ") + hipGetErrorString(e);
-        fail_here(e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE);
-        ok = false;
-      }
-      total_score = M.sum.p;
+      e = hipMemcpyAsync(M.stage.p, src, (size_t)nu * sizeof(float), hipMemcpyDefault, M.stream);
+      src = M.stage.p;
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(nu)), dim3(256), 0, M.stream, M.sum.p, src, nu);
+      e = hipGetLastError();
     }
   }
-  // ---- the `>= theta` prune, on the row range's first member (every member of the RCCL exchange holds the same sums)
-  if (i == 0 && ok) {
-    auto finish = [&]() -> int32_t {
-      int32_t rc2;
-      if ((rc2 = ensure(M, (size_t)std::max<int64_t>(1, nu), R.res_q, R.res_c, R.res_s)) != APSS_OK) return rc2;
-      GHIP(nullptr, M, hipMemsetAsync(M.count.p, 0, sizeof(unsigned long long), M.stream));
-      if (nu > 0) {
-        hipLaunchKernelGGL(k_threshold_compact, dim3(grid_for(nu)), dim3(256), 0, M.stream, total_score, (const int32_t *)M.uq.p,
-                           (const int32_t *)M.uc.p, nu, (float)g->cfg.theta, R.res_q.p, R.res_c.p, R.res_s.p, M.count.p);
-        GHIP(nullptr, M, hipGetLastError());
-      }
-      unsigned long long nres = 0;
-      GHIP(nullptr, M, hipMemcpyAsync(&nres, M.count.p, sizeof(nres), hipMemcpyDeviceToHost, M.stream));
-      GHIP(nullptr, M, hipStreamSynchronize(M.stream));
-      R.n_phase = (int64_t)nres;
-      R.union_pairs += nu;
-      g->tk = apss_topk_info{};
-      g->tk.pairs_over_theta = g->tk.kept = R.n_phase;
-      if (g->top_k > 0 && g->D == 1) {  // the per-query cut of the group's final list (the members are term shards: no k of their own)
-        const int64_t *d_store = nullptr, *d_query = nullptr;
-        int64_t store_rows = 0;
-        if (apss_ext_ids_dev(M.h, &d_store, &d_query) != APSS_OK || apss_size(M.h, &store_rows, nullptr) != APSS_OK || (nres > 0 && !d_store)) {
-          M.err = "per-query top-k: the member's external ids are gone";
-          return APSS_E_STATE;
-        }
-        const hipError_t e = apss::topk_run(g->topk, M.stream, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, b.n, d_store, store_rows, g->top_k, &g->tk);
-        if (e != hipSuccess) {
-          M.err = std::string("per-query top-k: ") + hipGetErrorString(e);
-          return e == hipErrorOutOfMemory ? APSS_E_NOMEM : APSS_E_DEVICE;
-        }
-        if (R.n_phase > 0) {  // (kept <= n_phase: the selected list fits the buffers it replaces)
-          const size_t kept = (size_t)g->tk.kept;
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_q.p, g->topk.out_q.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_c.p, g->topk.out_c.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
-          GHIP(nullptr, M, hipMemcpyAsync(R.res_s.p, g->topk.out_s.p, kept * sizeof(float), hipMemcpyDeviceToDevice, M.stream));
-          GHIP(nullptr, M, hipStreamSynchronize(M.stream));
-          R.n_phase = g->tk.kept;
-        }
-      }
-      if (g->D > 1) return append_triples(M, R, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, mirrored);
-      return APSS_OK;
-    };
-    const int32_t rc2 = finish();
-    if (rc2 != APSS_OK) fail_here(rc2);
-    R.exchange_ms += ms_since(tx);
-  } else if (ok) {
-    if (hipStreamSynchronize(M.stream) != hipSuccess) {
-      M.err = "stream synchronisation failed after the exchange";
-      fail_here(APSS_E_DEVICE);
+  if (e != hipSuccess) return mfail(M, hip_rc(e), std::string("partial score reduction: ") + hipGetErrorString(e));
+  P.total_score = M.sum.p;
+  return APSS_OK;
+}
+
+// The row range's FINAL LIST of a phase, finished on the range's first member -- whichever way it was produced: one member
+// per row range, whose handle's answer is final as it stands, or an exchange, whose reduced scores meet the `>= theta` prune
+// (k_threshold_compact), the count's read-back and, on a plain group, the per-query cut.  Either way the list then stands as
+// (query row, candidate slot, score), n of them, on M's device: THIS is where a list stage of the group hooks in (removal,
+// stored queries, a global top-K, components: apss_group has none of them yet).  A grid appends it to the range's triples.
+int32_t range_final_list(Phase &P) {
+  apss_group *g = P.g;
+  apss_group::Member &M = P.M;
+  apss_group::Range &R = P.R;
+  const int32_t *q = nullptr, *c = nullptr;
+  const float *s = nullptr;
+  int64_t n = 0;
+  int32_t rc;
+  if (g->exchange == APSS_EXCHANGE_NONE) {
+    R.n_phase = M.n_cand;
+    if (g->D == 1 || M.n_cand == 0) return APSS_OK;  // (a plain group's list stays in its handle)
+    if ((rc = apss_results_dev(M.h, &q, &c, &s, &n)) != APSS_OK) return mfail(M, rc, apss_last_error(M.h));
+  } else {
+    const int64_t nu = M.n_union;
+    if ((rc = ensure(M, (size_t)std::max<int64_t>(1, nu), R.res_q, R.res_c, R.res_s)) != APSS_OK) return rc;
+    GHIP(nullptr, M, hipMemsetAsync(M.count.p, 0, sizeof(unsigned long long), M.stream));
+    if (nu > 0) {
+      hipLaunchKernelGGL(k_threshold_compact, dim3(grid_for(nu)), dim3(256), 0, M.stream, P.total_score, (const int32_t *)M.uq.p,
+                         (const int32_t *)M.uc.p, nu, (float)g->cfg.theta, R.res_q.p, R.res_c.p, R.res_s.p, M.count.p);
+      GHIP(nullptr, M, hipGetLastError());
     }
+    unsigned long long nres = 0;
+    if ((rc = read_back(M, &nres, M.count.p)) != APSS_OK) return rc;
+    R.n_phase = (int64_t)nres;
+    R.union_pairs += nu;
+    g->tk = apss_topk_info{};
+    g->tk.pairs_over_theta = g->tk.kept = R.n_phase;
+    if (g->top_k > 0 && g->D == 1) {  // the per-query cut of the group's final list (the members are term shards: no k of their own)
+      const int64_t *d_store = nullptr, *d_query = nullptr;
+      int64_t store_rows = 0;
+      if (apss_ext_ids_dev(M.h, &d_store, &d_query) != APSS_OK || apss_size(M.h, &store_rows, nullptr) != APSS_OK || (nres > 0 && !d_store))
+        return mfail(M, APSS_E_STATE, "per-query top-k: the member's external ids are gone");
+      const hipError_t e = apss::topk_run(g->topk, M.stream, R.res_q.p, R.res_c.p, R.res_s.p, R.n_phase, P.b.n, d_store, store_rows, g->top_k, &g->tk);
+      if (e != hipSuccess) return mfail(M, hip_rc(e), std::string("per-query top-k: ") + hipGetErrorString(e));
+      if (R.n_phase > 0) {  // (kept <= n_phase: the selected list fits the buffers it replaces)
+        const size_t kept = (size_t)g->tk.kept;
+        GHIP(nullptr, M, hipMemcpyAsync(R.res_q.p, g->topk.out_q.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+        GHIP(nullptr, M, hipMemcpyAsync(R.res_c.p, g->topk.out_c.p, kept * sizeof(int32_t), hipMemcpyDeviceToDevice, M.stream));
+        GHIP(nullptr, M, hipMemcpyAsync(R.res_s.p, g->topk.out_s.p, kept * sizeof(float), hipMemcpyDeviceToDevice, M.stream));
+        GHIP(nullptr, M, hipStreamSynchronize(M.stream));
+        R.n_phase = g->tk.kept;
+      }
+    }
+    q = R.res_q.p, c = R.res_c.p, s = R.res_s.p, n = R.n_phase;
   }
-  return !bar.wait();  // ---- B4: the first member has read every peer's partial scores (copies exchange) before anyone goes on
+  return g->D > 1 ? append_triples(M, R, q, c, s, n, P.mirrored) : APSS_OK;
+}
+
+// B4: reduce, then the range's final list on the first member, or the wait for the stream on the others
+int32_t phase_reduce_and_finish(Phase &P) {
+  apss_group::Member &M = P.M;
+  P.total_score = M.partial.p;  // (an empty union: nothing to reduce, and nothing to read)
+  int32_t rc = M.n_union > 0 ? P.reduce(P) : APSS_OK;
+  if (rc != APSS_OK) return rc;
+  if (P.i == 0) {
+    rc = range_final_list(P);
+    P.R.exchange_ms += ms_since(P.tx);
+  } else if (hipStreamSynchronize(M.stream) != hipSuccess) {
+    rc = mfail(M, APSS_E_DEVICE, "stream synchronisation failed after the exchange");
+  }
+  return rc;
+}
+
+// One phase of a call for member m = (row range j, term range i): the handle call on the phase's batch, the exchange among the T
+// members of the row range, the range's final list.  A plain group's call is one phase; a grid's insert-and-query is two (its
+// own span, then the outside batch as a query).  This function only sequences: a line is a step of the lock-step rule behind
+// one of the barriers B1 .. B4, or an exit that the members of the row range take together.  false: the call has failed.
+bool member_phase(int m, CallCtx &cx, Lockstep &ls, int mode, const MemberBatch &b, bool mirrored) {
+  apss_group *g = cx.g;
+  const int T = g->T, j = m / T, i = m % T;
+  Phase P{g, g->m[(size_t)m], &g->m[(size_t)(j * T)], g->rr[(size_t)j], T, i, mode, b, mirrored, ls};
+  if (g->exchange == APSS_EXCHANGE_RCCL) P.gather = gather_rccl, P.reduce = reduce_rccl;
+  else P.gather = gather_copies, P.reduce = reduce_copies;
+  P.M.n_cand = P.M.n_union = 0;
+  if (i == 0) P.R.n_phase = 0;
+  // ---- B1: every member's candidate count (or failure) is known
+  if (!ls.step(When::kUnlessFailed, [&] { return member_phase1(P.M, mode, b, mirrored); })) return false;
+  if (mode == 0) return true;
+  // ---- (no exchange) B2: one member per row range, its answer is final
+  if (g->exchange == APSS_EXCHANGE_NONE) return ls.step(When::kAlways, [&] { return range_final_list(P); });
+  P.tx = Clock::now();
+  P.x = apss::exchange_offsets(T, i, [&](int k) { return P.peers[k].n_cand; });
+  if (P.x.total == 0) return true;  // nothing to exchange: every member leaves together
+  if (i == 0) P.R.gather_bytes += 8 * (P.x.total - P.x.least);
+  // ---- B2: every list is packed (the copies exchange lets the peers read it)
+  if (!ls.step(When::kAlways, [&] { return member_pack(P.M, P.x.total, P.x.mine); })) return false;
+  // ---- B3: every member's partial scores are complete
+  if (!ls.step(When::kAlways, [&] { return phase_gather_union_partials(P); })) return false;
+  // ---- B3b: the members agree on the union (a barrier of its own: a collective of unequal counts must never start)
+  if (!ls.step(When::kAlways, [&] { return phase_agree(P); })) return false;
+  // ---- B4: the first member has read every peer's partial scores (copies exchange) before anyone goes on
+  return ls.step(When::kAlways, [&] { return phase_reduce_and_finish(P); });
 }
 
 void member_main(int m, CallCtx *pcx) {
@@ -1084,32 +1086,23 @@ void member_main(int m, CallCtx *pcx) {
   M.n_cand = M.n_union = 0;
   M.member_ms = M.partial_ms = M.probe_ms = M.head_ms = 0;
   M.visits = M.dev_visits = M.touched = M.cand_sum = M.cand_max = 0;
-  auto fail_here = [&](int32_t rc) {
-    M.rc = rc;
-    cx.failed.store(1);
-  };
-  if (hipSetDevice(M.dev) != hipSuccess) {
-    M.err = "hipSetDevice failed";
-    fail_here(APSS_E_DEVICE);
-  }
+  Lockstep ls(&cx.bar[(size_t)j], &cx.failed, &M.rc);
+  ls.run(When::kAlways, [&] { return set_member_device(M); });
   const MemberBatch whole = whole_batch(cx.b, m);
   if (g->D == 1) {  // T x 1: every member holds its slice of every row, one phase
-    (void)member_phase(m, cx, cx.mode, whole, false);
+    (void)member_phase(m, cx, ls, cx.mode, whole, false);
     return;
   }
   apss_group::Range &R = g->rr[(size_t)j];
   const RangePlan &P = cx.plan[(size_t)j];
   if (cx.mode == 1) {  // frozen index: every row range that holds rows is asked the whole batch
-    if (R.rows > 0) (void)member_phase(m, cx, 1, whole, false);
+    if (R.rows > 0) (void)member_phase(m, cx, ls, 1, whole, false);
     return;
   }
   if (cx.b.n == 0) return;  // (an empty batch: no span, no outside batch, and no row offsets to read)
   MemberBatch ph[2];  // [0] the row range's own span, [1] its outside batch
-  if (cx.b.on_device) {
-    if (!cx.failed.load()) {
-      const int32_t rc = member_slice(M, cx, whole, P, ph);
-      if (rc != APSS_OK) fail_here(rc);  // (published before the row range's next barrier, B1 of the first phase below)
-    }
+  if (cx.b.on_device) {  // (a failure is published before the row range's next barrier, B1 of the first phase below)
+    ls.run(When::kUnlessFailed, [&] { return member_slice(M, cx, whole, P, ph); });
   } else {
     ph[0] = host_csr_batch(P.own);
     ph[1] = host_csr_batch(P.out);
@@ -1118,13 +1111,13 @@ void member_main(int m, CallCtx *pcx) {
   const int64_t own_n = cx.span_lo[(size_t)P.span + 1] - cx.span_lo[(size_t)P.span];
   if (own_n > 0) {  // an empty span: the row range skips the handle call
     const auto t0 = Clock::now();
-    const bool ok = member_phase(m, cx, cx.mode, ph[0], false);
+    const bool ok = member_phase(m, cx, ls, cx.mode, ph[0], false);
     if (i == 0) R.own_ms = ms_since(t0);
     if (!ok) return;
   }
   if (cx.mode == 2 && P.out_rows > 0 && R.rows + own_n > 0) {
     const auto t0 = Clock::now();
-    (void)member_phase(m, cx, 1, ph[1], P.mirrored);
+    (void)member_phase(m, cx, ls, 1, ph[1], P.mirrored);
     if (i == 0) R.outside_ms = ms_since(t0), R.outside_rows = P.out_rows;
   }
 }
@@ -1207,10 +1200,8 @@ int32_t assemble_whole(RelayoutCtx &cx, int i) {
     Slice &s = sl[(size_t)k];
     int64_t r = 0, z = 0;
     (void)apss_get_store_dev(P.h, &s.rp, &s.ix, &s.vl, &r, &z);
-    if (r != rows || !s.rp) {
-      M.err = "member " + std::to_string(k) + " holds " + std::to_string(r) + " rows, member 0 " + std::to_string(rows);
-      return APSS_E_STATE;
-    }
+    if (r != rows || !s.rp)
+      return mfail(M, APSS_E_STATE, "member " + std::to_string(k) + " holds " + std::to_string(r) + " rows, member 0 " + std::to_string(rows));
     if (P.dev != M.dev) {  // another device's slice: brought over first (peer copy, or staged by the runtime)
       w.staged.emplace_back();
       WholeRows::Staged &c = w.staged.back();
@@ -1247,91 +1238,77 @@ int32_t assemble_whole(RelayoutCtx &cx, int i) {
   return APSS_OK;
 }
 
+// phase B: member 0 decides (the head policy runs on its device over whole rows)
+int32_t relayout_decide(RelayoutCtx &cx) {
+  apss_group *g = cx.g;
+  apss_group::Member &M = g->m[0];
+  const WholeRows &w = cx.whole[(size_t)cx.builder[0]];
+  const int64_t batch_n = cx.b ? cx.b->n : 0;
+  auto feed = [&](apss_handle *ph) -> int32_t {
+    const int64_t s_rows = std::min<int64_t>(cx.rows, 131072);
+    if (s_rows > 0) {
+      int64_t s_nnz = 0;
+      if (hipMemcpy(&s_nnz, w.rowptr.p + s_rows, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
+      const int64_t *d_ext = nullptr;
+      (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
+      const int32_t rc = apss_insert_stored_dev(ph, s_rows, s_nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
+      if (rc != APSS_OK) return rc;
+    }
+    return cx.b ? feed_batch(g, ph, *cx.b, std::min<int64_t>(batch_n, 131072 - s_rows)) : APSS_OK;
+  };
+  int32_t rc = APSS_OK;
+  if (cx.decide_df && cx.b) rc = add_batch_df(g, *cx.b, cx.df);
+  if (rc == APSS_OK) rc = decide_layout(g, cx.df, cx.rows + batch_n, cx.fixed, feed, cx.next);
+  if (rc != APSS_OK) M.err = g->err;
+  else cx.rebuild = cx.next.cuts != g->cuts || cx.next.head != g->head;
+  return rc;
+}
+
+// phase C: a new handle for this member in the new layout, filled with the whole rows of its device
+int32_t relayout_refill(RelayoutCtx &cx, int i) {
+  apss_group *g = cx.g;
+  apss_group::Member &M = g->m[(size_t)i];
+  std::string err;
+  int32_t rc = create_member_handle(g, i, cx.next, &cx.fresh[(size_t)i], err);
+  if (rc == APSS_OK && cx.rows > 0) {
+    const WholeRows &w = cx.whole[(size_t)cx.builder[(size_t)i]];
+    const int64_t *d_ext = nullptr;
+    (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
+    const bool inject = g->relayout_fail == i;  // (the test hook: the handle's own argument check refuses the call)
+    rc = apss_insert_stored_dev(cx.fresh[(size_t)i], inject ? -1 : cx.rows, w.nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
+    if (rc != APSS_OK) err = std::string(inject ? "APSS_DEBUG relayout_fail: " : "") + apss_last_error(cx.fresh[(size_t)i]);
+    else if (hipStreamSynchronize(M.stream) != hipSuccess) rc = APSS_E_DEVICE, err = "stream synchronisation failed after the re-insert";
+  }
+  if (rc != APSS_OK) M.err = "re-layout: " + err;
+  return rc;
+}
+
+// One member's share of a re-layout: three steps of the lock-step rule (apss_lockstep.hpp) behind the barriers R1 .. R3.
+// This function only sequences.
 void relayout_main(int i, RelayoutCtx *pcx) {
   RelayoutCtx &cx = *pcx;
   apss_group *g = cx.g;
   apss_group::Member &M = g->m[(size_t)i];
   M.rc = APSS_OK;
   M.err.clear();
-  auto fail_here = [&](int32_t rc) {
-    M.rc = rc;
-    cx.failed.store(1);
-  };
-  if (hipSetDevice(M.dev) != hipSuccess) {
-    M.err = "hipSetDevice failed";
-    fail_here(APSS_E_DEVICE);
-  }
+  Lockstep ls(cx.bar, &cx.failed, &M.rc);
+  ls.run(When::kAlways, [&] { return set_member_device(M); });
   // ---- phase A: this member's document frequencies; the builder of each device assembles the whole rows there
-  if (!cx.failed.load() && cx.decide_df) {
-    const int32_t lo = g->T == 1 ? 0 : g->cuts[(size_t)i];
-    const int32_t rc = member_df(g, i, g->cuts.data(), cx.df.data() + lo);
-    if (rc != APSS_OK) fail_here(rc);
+  ls.run(When::kUnlessFailed, [&] { return cx.decide_df ? member_df(g, i, g->cuts.data(), cx.df.data() + (g->T == 1 ? 0 : g->cuts[(size_t)i])) : APSS_OK; });
+  const bool swap =
+      // ---- R1: document frequencies and whole rows are complete
+      ls.step(When::kUnlessFailed, [&] { return cx.rows > 0 && cx.builder[(size_t)i] == i ? assemble_whole(cx, i) : APSS_OK; }) &&
+      // ---- R2: the decision is known
+      ls.step(When::kAlways, [&] { return i == 0 ? relayout_decide(cx) : APSS_OK; }) && cx.rebuild &&
+      // ---- R3: every new member is filled (or one failed): swap together, or not at all
+      ls.step(When::kAlways, [&] { return relayout_refill(cx, i); });
+  if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};  // (whichever barrier the re-layout ended at)
+  if (swap) {
+    apss_destroy(M.h);
+    M.h = cx.fresh[(size_t)i];
+  } else if (cx.fresh[(size_t)i]) {
+    apss_destroy(cx.fresh[(size_t)i]);
   }
-  if (!cx.failed.load() && cx.rows > 0 && cx.builder[(size_t)i] == i) {
-    const int32_t rc = assemble_whole(cx, i);
-    if (rc != APSS_OK) fail_here(rc);
-  }
-  if (cx.bar->wait()) {  // ---- R1: document frequencies and whole rows are complete
-    if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
-    return;
-  }
-  // ---- phase B: member 0 decides (the head policy runs on its device over whole rows)
-  if (i == 0) {
-    const WholeRows &w = cx.whole[(size_t)cx.builder[0]];
-    const int64_t batch_n = cx.b ? cx.b->n : 0;
-    auto feed = [&](apss_handle *ph) -> int32_t {
-      const int64_t s_rows = std::min<int64_t>(cx.rows, 131072);
-      if (s_rows > 0) {
-        int64_t s_nnz = 0;
-        if (hipMemcpy(&s_nnz, w.rowptr.p + s_rows, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return APSS_E_DEVICE;
-        const int64_t *d_ext = nullptr;
-        (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
-        const int32_t rc = apss_insert_stored_dev(ph, s_rows, s_nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
-        if (rc != APSS_OK) return rc;
-      }
-      return cx.b ? feed_batch(g, ph, *cx.b, std::min<int64_t>(batch_n, 131072 - s_rows)) : APSS_OK;
-    };
-    int32_t rc = APSS_OK;
-    if (cx.decide_df && cx.b) rc = add_batch_df(g, *cx.b, cx.df);
-    if (rc == APSS_OK) rc = decide_layout(g, cx.df, cx.rows + batch_n, cx.fixed, feed, cx.next);
-    if (rc != APSS_OK) {
-      M.err = g->err;
-      fail_here(rc);
-    } else {
-      cx.rebuild = cx.next.cuts != g->cuts || cx.next.head != g->head;
-    }
-  }
-  if (cx.bar->wait() || !cx.rebuild) {  // ---- R2: the decision is known
-    if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
-    return;
-  }
-  // ---- phase C: a new handle for this member in the new layout, filled with the whole rows of its device
-  {
-    std::string err;
-    int32_t rc = create_member_handle(g, i, cx.next, &cx.fresh[(size_t)i], err);
-    if (rc == APSS_OK && cx.rows > 0) {
-      const WholeRows &w = cx.whole[(size_t)cx.builder[(size_t)i]];
-      const int64_t *d_ext = nullptr;
-      (void)apss_ext_ids_dev(M.h, &d_ext, nullptr);
-      const bool inject = g->relayout_fail == i;  // (the test hook: the handle's own argument check refuses the call)
-      rc = apss_insert_stored_dev(cx.fresh[(size_t)i], inject ? -1 : cx.rows, w.nnz, w.rowptr.p, w.idx.p, w.val.p, d_ext);
-      if (rc != APSS_OK) err = std::string(inject ? "APSS_DEBUG relayout_fail: " : "") + apss_last_error(cx.fresh[(size_t)i]);
-      else if (hipStreamSynchronize(M.stream) != hipSuccess) rc = APSS_E_DEVICE, err = "stream synchronisation failed after the re-insert";
-    }
-    if (rc != APSS_OK) {
-      M.err = "re-layout: " + err;
-      fail_here(rc);
-    }
-  }
-  const bool failed_r3 = cx.bar->wait();  // ---- R3: every new member is filled (or one failed): swap together, or not at all
-  if (cx.builder[(size_t)i] == i) cx.whole[(size_t)i] = WholeRows{};
-  if (failed_r3) {
-    if (cx.fresh[(size_t)i]) apss_destroy(cx.fresh[(size_t)i]);
-    cx.fresh[(size_t)i] = nullptr;
-    return;
-  }
-  apss_destroy(M.h);
-  M.h = cx.fresh[(size_t)i];
   cx.fresh[(size_t)i] = nullptr;
 }
 
@@ -1365,17 +1342,8 @@ int32_t relayout(apss_group *g, const std::vector<int32_t> *cuts, const Batch *b
     cx.fresh.assign((size_t)T, nullptr);
     Barrier bar(T, &cx.failed);
     cx.bar = &bar;
-    std::vector<std::thread> th;
-    for (int i = 1; i < T; ++i) th.emplace_back(relayout_main, i, &cx);
-    relayout_main(0, &cx);
-    for (std::thread &t : th) t.join();
-    (void)hipSetDevice(g->m[0].dev);
-    if (cx.failed.load()) {
-      for (int i = 0; i < T; ++i)
-        if (g->m[(size_t)i].rc != APSS_OK)
-          return gfail(g, g->m[(size_t)i].rc, "member " + std::to_string(i) + ": " + g->m[(size_t)i].err);
-      return gfail(g, APSS_E_STATE, "a member failed during the re-layout");
-    }
+    const int32_t rc = run_members(g, T, relayout_main, &cx, "a member failed during the re-layout");
+    if (rc != APSS_OK) return rc;
     if (cx.rebuild) {
       g->cuts = cx.next.cuts;
       g->head = cx.next.head;
@@ -1480,22 +1448,11 @@ int32_t run_call(apss_group *g, int mode, const Batch &b, int64_t *n_results) {
   cx.mode = mode;
   cx.b = b;
   if (D > 1) plan_ranges(g, cx);
-  std::vector<std::unique_ptr<Barrier>> bars;
-  for (int j = 0; j < D; ++j) {
-    bars.emplace_back(new Barrier(T, &cx.failed));
-    cx.bar.push_back(bars.back().get());
-  }
-  std::vector<std::thread> th;
-  for (int m = 1; m < n_members; ++m) th.emplace_back(member_main, m, &cx);
-  member_main(0, &cx);  // (member 0 runs on the caller's thread)
-  for (std::thread &t : th) t.join();
-  (void)hipSetDevice(g->m[0].dev);
-  if (cx.failed.load()) {
+  for (int j = 0; j < D; ++j) cx.bar.emplace_back(T, &cx.failed);
+  const int32_t rc = run_members(g, n_members, member_main, &cx, "a member failed");
+  if (rc != APSS_OK) {
     g->n_res = -1;
-    for (int m = 0; m < n_members; ++m)
-      if (g->m[(size_t)m].rc != APSS_OK)
-        return gfail(g, g->m[(size_t)m].rc, "member " + std::to_string(m) + ": " + g->m[(size_t)m].err);
-    return gfail(g, APSS_E_STATE, "a member failed");
+    return rc;
   }
   if (mode != 1) {
     g->n_rows = 0;
