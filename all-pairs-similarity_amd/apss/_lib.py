@@ -18,6 +18,8 @@ SYMBOLS = [
     "apss_stats_get", "apss_insert_dev", "apss_query_dev", "apss_insert_and_query_dev", "apss_clear",
     "apss_results_dev", "apss_results_copy_dev", "apss_partial_scores_dev", "apss_set_head_terms", "apss_get_head_terms", "apss_set_head_fold",
     "apss_ext_ids_dev", "apss_get_store_dev", "apss_insert_stored_dev",
+    # read-only view of a built rendering of the inverted index
+    "apss_index_view_get",
     # the term-sharded index of one node behind one object (csrc/apss_group.hip)
     "apss_group_create", "apss_group_destroy", "apss_group_last_error", "apss_group_set_term_cuts", "apss_group_insert",
     "apss_group_query", "apss_group_insert_and_query", "apss_group_insert_and_query_dev", "apss_group_clear",
@@ -50,6 +52,7 @@ DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
 TOP_K_MAX = 1024
 TOP_PAIRS_MAX = 1 << 20
 CC_RAN, CC_OFF, CC_OUTSIDE, CC_TILE_CUT = 0, 1, 2, 3
+SLOT_PLAIN, SLOT_TIMES2, SLOT_WIDE = 0, 1, 2
 SYM_RAN, SYM_FLAG, SYM_NOT_WHOLE, SYM_PATH, SYM_LONG_ROWS, SYM_ONE_TILE, SYM_CHUNK = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -140,6 +143,14 @@ class ComponentsInfo(C.Structure):
                 ("largest", C.c_int64), ("pairs_absorbed", C.c_int64), ("unions_total", C.c_int64), ("resets", C.c_int64),
                 ("hook_ms", C.c_double), ("label_ms", C.c_double), ("hook_launches", C.c_int32), ("label_launches", C.c_int32),
                 ("reserved", C.c_int64)]
+
+
+class IndexView(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("rendering", C.c_int32), ("tile_rows", C.c_int32), ("seg_align", C.c_int32),
+                ("posting_bytes", C.c_int32), ("slot_form", C.c_int32), ("weights_scaled", C.c_int32), ("dim", C.c_int32),
+                ("n_tiles", C.c_int64), ("built_rows", C.c_int64), ("post_used", C.c_int64),
+                ("d_seg", C.c_void_p), ("d_base", C.c_void_p), ("d_post", C.c_void_p), ("d_sub", C.c_void_p),
+                ("d_tile_min", C.c_void_p), ("max_seg", C.c_int64), ("long_segs", C.c_int64), ("chunk_weight", C.c_double)]
 
 
 def build_sources():
@@ -250,6 +261,8 @@ def lib():
     L.apss_ext_ids_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.apss_get_store_dev.restype = i32
     L.apss_get_store_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi64, pi64]
+    L.apss_index_view_get.restype = i32
+    L.apss_index_view_get.argtypes = [vp, i32, C.POINTER(IndexView)]
     L.apss_insert_stored_dev.restype = i32
     L.apss_insert_stored_dev.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.apss_group_create.restype = i32

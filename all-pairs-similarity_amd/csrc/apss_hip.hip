@@ -3946,6 +3946,44 @@ int32_t apss_get_store_dev(apss_handle *h, const int64_t **d_rowptr, const int32
   return APSS_OK;
 }
 
+// what the handle knows of one rendering, copied out: nothing is built, launched or reserved (include/apss.h)
+int32_t apss_index_view_get(apss_handle *h, int32_t rendering, apss_index_view *out) {
+  if (!h || !out || (rendering != 0 && rendering != 1)) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_index_view.struct_size must be set to sizeof(apss_index_view) before the call");
+  const apss_handle::IndexSet &ix = rendering ? h->cx : h->ex;
+  // (the exact rendering of a handle that filters with the coarse one goes stale at an insert: ex_built_rows says how far it holds)
+  const bool built = ix.n_tiles > 0 && ix.built_rows > 0 && (int64_t)ix.h_base.size() == ix.n_tiles + 1 &&
+                     (rendering ? h->use_coarse : h->ex_built_rows == ix.built_rows);
+  const bool scales = h->sharded || h->head_k > 0;
+  apss_index_view v{};
+  v.rendering = rendering;
+  v.tile_rows = ix.cb;
+  v.seg_align = ix.align;
+  v.posting_bytes = ix.coarse ? (int32_t)sizeof(uint32_t) : (int32_t)sizeof(Posting);
+  v.slot_form = !ix.coarse ? APSS_SLOT_PLAIN : (ix.cb <= 32768 ? APSS_SLOT_TIMES2 : (ix.cb > 65536 ? APSS_SLOT_WIDE : APSS_SLOT_PLAIN));
+  v.weights_scaled = scales && ix.coarse ? 1 : 0;
+  v.dim = h->cfg.dim;
+  if (built) {
+    v.n_tiles = ix.n_tiles;
+    v.built_rows = ix.built_rows;
+    v.post_used = ix.post_used;
+    v.d_seg = ix.seg.p;
+    v.d_base = ix.base.p;
+    v.d_post = ix.coarse ? (const void *)ix.post_c.p : (const void *)ix.post.p;
+    v.d_sub = scales ? h->sub.p : nullptr;
+    v.d_tile_min = scales ? (ix.coarse ? h->tile_min_c.p : h->tile_min.p) : nullptr;
+    v.max_seg = ix.max_seg;
+    v.long_segs = ix.long_segs;
+    v.chunk_weight = ix.round_chunks;
+  }
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_index_view));
+  v.struct_size = n;
+  std::memcpy(out, &v, (size_t)n);
+  return APSS_OK;
+}
+
 int32_t apss_query_dev(apss_handle *h, int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_indices,
                        const float *d_values, const int64_t *d_ext_ids, int64_t *n_results) {
   APSS_TRY(enter(h));

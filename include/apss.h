@@ -251,6 +251,53 @@ int32_t apss_ext_ids_dev(apss_handle *h, const int64_t **d_store_ext, const int6
  * when the store is empty; valid until the next insert or clear */
 int32_t apss_get_store_dev(apss_handle *h, const int64_t **d_rowptr, const int32_t **d_indices, const float **d_values,
                        int64_t *rows, int64_t *nnz);
+/* ---- read-only view of a built rendering of the inverted index ("What the tests hold the index to") ----
+ * rendering 0: the exact rendering (8-B postings {uint32 slot, float w}); 1: the coarse rendering (4-B posting words).
+ * The call builds nothing, launches nothing and reserves nothing: it copies out what the handle already knows.  Layout:
+ *   d_seg  uint32[n_tiles][dim][2]: {first posting, length} of term t in tile T, relative to the tile's base; every start is a
+ *          multiple of seg_align, and a segment owns the aligned extent [start, start + ceil(length / seg_align) * seg_align)
+ *   d_base int64[n_tiles + 1]: first posting of every tile in d_post; d_base[n_tiles] == post_used
+ *   d_post postings: slot = store row - tile * tile_rows.  Coarse words by slot_form:
+ *          APSS_SLOT_TIMES2  (slot * 2) | fp16 bits << 16       (tiles of at most 32768 rows)
+ *          APSS_SLOT_PLAIN    slot      | fp16 bits << 16       (65536-row tiles)
+ *          APSS_SLOT_WIDE     slot << 15 | fp16 bits & 0x7fff   (131072-row tiles; weights are non-negative there)
+ *          the fp16 is the weight rounded to nearest even, raised to bits 1 where it would be 0: no posting word is zero, and
+ *          every word of an aligned extent behind its segment's length IS zero.  The exact rendering always says APSS_SLOT_PLAIN.
+ *   d_sub  float[rows]: with weights_scaled the coarse weights are stored divided by d_sub[row] where that is positive (the
+ *          shard rule: |x_g| / |x|; a handle with a dense-head block: its tail's share); NULL otherwise
+ *   d_tile_min float[n_tiles]: the smallest positive d_sub over each tile's rows (0: none), for either rendering of a handle that
+ *          scales; NULL otherwise
+ * The rendering covers the store rows [0, built_rows): rows behind them wait outside the index until a later insert folds them in.
+ * A rendering that has not been built (or whose tiles are stale: the exact rendering of a handle that filters with the coarse one
+ * is rebuilt only by a call that needs it) answers n_tiles = 0 and NULL views.  The views are valid until the next insert, clear,
+ * compaction or query-type call (which may rebuild a rendering). */
+#define APSS_SLOT_PLAIN 0
+#define APSS_SLOT_TIMES2 1
+#define APSS_SLOT_WIDE 2
+typedef struct apss_index_view {
+  int32_t struct_size;     /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t rendering;       /* as asked */
+  int32_t tile_rows;       /* rows per tile */
+  int32_t seg_align;       /* postings per aligned unit (one 128-B line) */
+  int32_t posting_bytes;   /* 8 or 4 */
+  int32_t slot_form;       /* APSS_SLOT_* */
+  int32_t weights_scaled;  /* 1: weights are stored divided by d_sub[row] */
+  int32_t dim;             /* terms per tile of d_seg (its stride) */
+  int64_t n_tiles;
+  int64_t built_rows;
+  int64_t post_used;       /* postings of d_post in use, padding included */
+  const void *d_seg;
+  const int64_t *d_base;
+  const void *d_post;
+  const float *d_sub;
+  const float *d_tile_min;
+  int64_t max_seg;         /* longest (tile, term) segment, as the probe was told */
+  int64_t long_segs;       /* segments of more than 256 postings, as the probe was told (exact for a rendering built whole
+                              from tile 0; an append to the last tile does not recount that tile) */
+  double chunk_weight;     /* 16-posting chunks an average stored row deals out per tile (measured by a build from tile 0) */
+} apss_index_view;
+int32_t apss_index_view_get(apss_handle *h, int32_t rendering, apss_index_view *out);
+
 /* as apss_insert_dev, for rows that ALREADY passed this configuration's ingest filters (rows of some handle's store, e.g.
  * reassembled from term shards): no normalisation, value prune or admission is applied again (a pruned row re-normalised
  * would change, an admission test on its pruned sum could drop it).  A term shard still keeps its range of every row and

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from apss import synth
+from build_inputs import corner_vectors as _corner_vectors
 from helpers import assert_same_pairs, to_map
 
 pytestmark = pytest.mark.gpu
@@ -38,38 +39,6 @@ def _took(capfd, what):
     lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[apss] build ")]
     assert lines and all(": %s," % what in ln for ln in lines), lines
     return lines
-
-
-def _corner_vectors(dim, seed, n_base=1400, nnz=20, range_terms=16384):
-    """uniform rows with 5 % duplicates + the corners of the cut computation, each twice (a pair to report): rows whose
-    entries all lie in the first / in the last term range, rows of 1 entry and of 2,247, a row with entries in the first and the
-    last range only (every range between: empty runs), empty rows; shuffled, unit norm"""
-    rng = np.random.default_rng(seed)
-    rp, idx, val = synth.make_vectors(n_base, dim, nnz, 0.0, seed=seed, dup_frac=0.05)
-    rows = [(idx[rp[i]:rp[i + 1]].astype(np.int32), val[rp[i]:rp[i + 1]].astype(np.float64)) for i in range(n_base)]
-    last_lo = (dim - 1) // range_terms * range_terms
-    first_hi = min(range_terms, dim)
-
-    def row(terms):
-        t = np.unique(np.asarray(terms, np.int64)).astype(np.int32)
-        v = np.abs(rng.standard_normal(t.size)) + 0.1
-        return t, v / np.sqrt((v * v).sum())
-
-    special = [
-        row(rng.choice(first_hi, size=min(30, first_hi), replace=False)),              # all in the first range
-        row(last_lo + rng.choice(dim - last_lo, size=min(30, dim - last_lo), replace=False)),  # all in the last (short) range
-        row([int(rng.integers(0, dim))]),                                              # one entry
-        row([dim - 1]),                                                                # ... the very last term
-        row([0]),                                                                      # ... the very first
-        row(rng.choice(dim, size=min(2247, dim), replace=False)),                      # far longer than a lane group
-        row(np.concatenate([rng.choice(first_hi, 5, replace=False), [dim - 1, dim - 2]])),  # first + last range only
-    ]
-    empty = (np.zeros(0, np.int32), np.zeros(0))
-    rows += special + special + [empty] * 7
-    order = rng.permutation(len(rows))
-    rows = [rows[i] for i in order]
-    rp = np.concatenate([[0], np.cumsum([r[0].size for r in rows])]).astype(np.int64)
-    return rp, np.concatenate([r[0] for r in rows]).astype(np.int32), np.concatenate([r[1] for r in rows])
 
 
 CASES = {
