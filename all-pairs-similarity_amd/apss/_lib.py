@@ -41,6 +41,8 @@ SYMBOLS = [
     "apss_set_top_pairs", "apss_top_pairs_get",
     # near-duplicate groups: the connected components of the join (csrc/apss_components.hpp)
     "apss_set_components", "apss_components_get", "apss_components_dev", "apss_components_fetch",
+    # ... across a removal and a compaction (csrc/apss_components_repair.hpp)
+    "apss_set_components_repair", "apss_components_repair_get",
 ]
 TILE_CUT_RAN, TILE_CUT_OFF, TILE_CUT_NO_K, TILE_CUT_PATH = 0, 1, 2, 3
 TILE_CUT_REMOVED = 4
@@ -52,6 +54,7 @@ DOWNGRADE_ACC8, DOWNGRADE_HEAD = 1, 2
 TOP_K_MAX = 1024
 TOP_PAIRS_MAX = 1 << 20
 CC_RAN, CC_OFF, CC_OUTSIDE, CC_TILE_CUT = 0, 1, 2, 3
+CCR_RAN, CCR_OFF, CCR_NO_COMPONENTS, CCR_BUDGET, CCR_NOTHING = 0, 1, 2, 3, 4
 SLOT_PLAIN, SLOT_TIMES2, SLOT_WIDE = 0, 1, 2
 SYM_RAN, SYM_FLAG, SYM_NOT_WHOLE, SYM_PATH, SYM_LONG_ROWS, SYM_ONE_TILE, SYM_CHUNK = 0, 1, 2, 3, 4, 5, 6
 
@@ -143,6 +146,13 @@ class ComponentsInfo(C.Structure):
                 ("largest", C.c_int64), ("pairs_absorbed", C.c_int64), ("unions_total", C.c_int64), ("resets", C.c_int64),
                 ("hook_ms", C.c_double), ("label_ms", C.c_double), ("hook_launches", C.c_int32), ("label_launches", C.c_int32),
                 ("reserved", C.c_int64)]
+
+
+class ComponentsRepairInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("declined", C.c_int32), ("max_rows", C.c_int64), ("rows_marked", C.c_int64),
+                ("components_touched", C.c_int64), ("rows_rejoined", C.c_int64), ("pairs_rejoined", C.c_int64),
+                ("repairs", C.c_int64), ("budget_resets", C.c_int64), ("remaps", C.c_int64), ("detach_ms", C.c_double),
+                ("rejoin_ms", C.c_double), ("remap_ms", C.c_double), ("launches", C.c_int32), ("reserved0", C.c_int32)]
 
 
 class IndexView(C.Structure):
@@ -345,5 +355,9 @@ def lib():
     L.apss_components_dev.argtypes = [vp, C.POINTER(vp), pi64]
     L.apss_components_fetch.restype = i32
     L.apss_components_fetch.argtypes = [vp, i64, i64, vp, vp]
+    L.apss_set_components_repair.restype = i32
+    L.apss_set_components_repair.argtypes = [vp, i64]
+    L.apss_components_repair_get.restype = i32
+    L.apss_components_repair_get.argtypes = [vp, C.POINTER(ComponentsRepairInfo)]
     _lib = L
     return L

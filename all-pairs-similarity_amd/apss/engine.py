@@ -27,7 +27,7 @@ def _ptr(a):
 class ApssIndex:
     def __init__(self, dim, theta, device=0, tile_rows=0, term_range=None, flags=0, index_threshold=0.0,
                  capacity_rows=0, capacity_nnz=0, head_terms=0, top_k=0, top_k_window=0, top_k_tile_cut=False,
-                 auto_compact=0.0, top_pairs=0, components=False):
+                 auto_compact=0.0, top_pairs=0, components=False, components_repair=0):
         L = _lib.lib()
         cfg = _lib.Config()
         cfg.struct_size = C.sizeof(_lib.Config)
@@ -49,7 +49,7 @@ class ApssIndex:
         self._L = L
         self.dim, self.theta = int(dim), float(theta)
         self._device = int(device)
-        if top_k or top_k_window or top_k_tile_cut or auto_compact or top_pairs or components:
+        if top_k or top_k_window or top_k_tile_cut or auto_compact or top_pairs or components or components_repair:
             try:
                 if auto_compact:
                     self.set_auto_compact(auto_compact)
@@ -63,6 +63,8 @@ class ApssIndex:
                     self.set_top_pairs(top_pairs)
                 if components:
                     self.set_components(True)
+                if components_repair:
+                    self.set_components_repair(components_repair)
             except ApssError:
                 self.close()
                 raise
@@ -260,6 +262,19 @@ class ApssIndex:
         """near-duplicate groups (apss_set_components): on = the connected components of the graph "stored row - stored row, edge =
         a pair of a call's final list" are kept on the device across calls; off (the default) frees them"""
         self._chk(self._L.apss_set_components(self._h, 1 if on else 0))
+
+    def set_components_repair(self, max_rows):
+        """keep the groups across remove and compact (apss_set_components_repair): a remove re-joins the live rows of the components
+        it touched, at most `max_rows` of them (more: today's reset to singletons), and a compaction renumbers the forest; 0 (the
+        default): off"""
+        self._chk(self._L.apss_set_components_repair(self._h, int(max_rows)))
+
+    def components_repair_info(self):
+        """the setting, what the last remove's repair did and the totals since create (apss_components_repair_info)"""
+        ri = _lib.ComponentsRepairInfo()
+        ri.struct_size = C.sizeof(_lib.ComponentsRepairInfo)
+        self._chk(self._L.apss_components_repair_get(self._h, C.byref(ri)))
+        return {k: getattr(ri, k) for k, _ in _lib.ComponentsRepairInfo._fields_}
 
     def components_info(self):
         """the structure's state and what the last calls did to it (apss_components_info); brings the labels up to date"""

@@ -27,6 +27,7 @@
 #include "apss_query_stored.hpp"
 #include "apss_top_pairs.hpp"
 #include "apss_components.hpp"
+#include "apss_components_repair.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -407,6 +408,11 @@ struct apss_handle {
   bool cc_on = false;
   CcWork cc;
   apss_components_info cci{};
+  // ... across a removal and a compaction (apss_components_repair.hpp): the budget (0: off), the stage's event pair, what the last
+  // calls did
+  int64_t ccr_max = 0;
+  DevEvent cr_ev0, cr_ev1;  // (made where they are first recorded)
+  apss_components_repair_info ccri{};
   // persistent filter launches (apss_worklist.hpp): the work lists of the last call's launches, one behind the other in
   // pinned memory and on the device, kept until a call's keys differ; workgroups per CU of each instantiation as queried
   std::vector<apss::WorkListKey> wl_keys;
@@ -466,11 +472,12 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ---- ingest: validate (+ optional normalise / admission / value prune / term-range filter) and append ----
 // Source arrays are device pointers (batch-relative rowptr).  Destination: the store (to_store) or the query
 // staging buffers.  *n_out / *nnz_out: rows / entries that survived.
-// exclusive scan of n int64 (n + 1 outputs, out[n] = total) on the handle's stream
-int32_t scan_i64(apss_handle *h, const int64_t *in, int64_t *out, int64_t n) {
+// exclusive scan of n int64 (n + 1 outputs, out[n] = total) on the handle's stream; *launches (if given) += the kernels it launched
+int32_t scan_i64(apss_handle *h, const int64_t *in, int64_t *out, int64_t n, int32_t *launches = nullptr) {
   if (n <= 4 * kScanBlock) {
     hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, h->stream, in, out, n);
     HIPCHK(h, hipGetLastError());
+    if (launches) *launches += 1;
     return APSS_OK;
   }
   const int64_t nb = ceil_div(n, kScanBlock);
@@ -480,6 +487,7 @@ int32_t scan_i64(apss_handle *h, const int64_t *in, int64_t *out, int64_t n) {
   hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, h->stream, (const int64_t *)sums, offs, nb);
   hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(1024), 0, h->stream, in, (const int64_t *)offs, out, n, nb);
   HIPCHK(h, hipGetLastError());
+  if (launches) *launches += 3;
   return APSS_OK;
 }
 
@@ -1277,10 +1285,11 @@ struct QueryBatch : QueryRows {
   float max_norm2;
   int64_t nnz_end;
   const int32_t *slots = nullptr;  // [nq] the slot of every row where the batch is a SELECTION of stored rows (apss_query_stored), else NULL
+  bool absorb_only = false;        // the list is wanted by the components alone (a removal's re-join): no cut runs, nothing of it is kept
   // rows [r0, r1) as a batch of their own (a window): the offsets stay absolute
   QueryBatch rows(int64_t r0, int64_t r1) const {
     return QueryBatch{{r1 - r0, rowptr + r0, idx, val, ext + r0}, slot_first < 0 ? -1 : slot_first + r0, max_nnz, max_norm2, nnz_end,
-                      slots ? slots + r0 : nullptr};
+                      slots ? slots + r0 : nullptr, absorb_only};
   }
 };
 
@@ -3126,6 +3135,11 @@ int32_t finish_list(apss_handle *h, const QueryBatch &batch, apss_topk_info *inf
   APSS_TRY(drop_removed(h, batch.slot_first));
   if (h->cc_on) APSS_TRY(absorb_components(h, batch));
   info->pairs_over_theta = info->kept = h->n_res;
+  if (batch.absorb_only) {  // (the forest has the list: nobody reads it, so no cut selects from it and a window keeps none of it)
+    info->kept = 0;
+    adopt_list(h, h->out_q, h->out_c, h->out_s, 0);
+    return APSS_OK;
+  }
   if (h->top_k <= 0 || h->sharded) return APSS_OK;
   return cut_final_list(h, batch.nq, info);
 }
@@ -3276,7 +3290,7 @@ int32_t probe(apss_handle *h, const QueryBatch &batch, int64_t *n_results) {
     h->cc.hook_open = false;
   }
   APSS_TRY(probe_lists(h, batch, n_results));
-  if (h->top_pairs > 0 && !h->sharded) APSS_TRY(cut_top_pairs(h, batch));
+  if (h->top_pairs > 0 && !h->sharded && !batch.absorb_only) APSS_TRY(cut_top_pairs(h, batch));
   if (n_results) *n_results = h->n_res;
   return APSS_OK;
 }
@@ -3468,6 +3482,18 @@ int32_t sort_ids(apss_handle *h, const int64_t *d_ids, int64_t n, DevEvent &e0) 
   return APSS_OK;
 }
 
+// ---- components across a removal (apss_components_repair.hpp) ----
+// what apss_components_repair_info says of a call, before the call knows that it marked a row
+void begin_repair_call(apss_handle *h) {
+  apss_components_repair_info &ri = h->ccri;
+  ri.declined = h->ccr_max <= 0 ? APSS_CCR_OFF : !h->cc_on ? APSS_CCR_NO_COMPONENTS : APSS_CCR_NOTHING;
+  ri.rows_marked = ri.components_touched = ri.rows_rejoined = ri.pairs_rejoined = 0;
+  ri.detach_ms = ri.rejoin_ms = 0;
+  ri.launches = 0;
+}
+
+int32_t repair_components(apss_handle *h, int64_t marked);
+
 // marks the stored rows whose external id is in d_ids[0, n) (device); *newly = rows that were live before
 int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *newly) {
   *newly = 0;
@@ -3489,7 +3515,16 @@ int32_t remove_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64_t *ne
   h->rm_marked += (int64_t)marked;
   h->ri.removed_total += (int64_t)marked;
   *newly = (int64_t)marked;
-  if (h->cc_on && marked > 0) reset_components(h, true);  // (a removed row can split a component)
+  h->ccri.rows_marked = (int64_t)marked;
+  if (h->cc_on && marked > 0) {  // (a removed row can split a component)
+    if (h->ccr_max <= 0) {
+      reset_components(h, true);
+    } else {  // ... so the components that held one are taken apart and re-joined
+      const int32_t rc = repair_components(h, (int64_t)marked);
+      if (rc != APSS_OK) reset_components(h, true);  // (the marks stay: the removal happened)
+      return rc;
+    }
+  }
   return APSS_OK;
 }
 
@@ -3506,6 +3541,17 @@ int32_t compact_impl(apss_handle *h) {
   HIPCHK(h, hipGetLastError());
   APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, n));
   APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, n));
+  // with apss_set_components_repair the forest moves with the rows: renumbered by the ranks just scanned and written aside, since
+  // the rebuild below resets the structure on its way (apss_components_repair.hpp)
+  const bool carry = h->cc_on && h->ccr_max > 0;
+  const int32_t cc_complete = h->cci.complete;
+  const int64_t cc_resets = h->cci.resets;
+  if (carry) {
+    int32_t launches = 0;
+    HIPCHK(h, begin_timed(h->stream, h->cr_ev0));
+    APSS_TRY(components_stage(h, [&] { return cr_remap(h->cc, h->stream, n, h->dead.p, h->s_rowdst.p, &launches); }));
+    HIPCHK(h, h->cr_ev1.record(h->stream));
+  }
   int64_t live_rows = 0, live_nnz = 0;
   HIPCHK(h, hipMemcpyAsync(&live_rows, h->s_rowdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(&live_nnz, h->s_nnzdst.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -3541,7 +3587,15 @@ int32_t compact_impl(apss_handle *h) {
   h->ri.compact_ms = ms;
   h->ri.compacted_rows = marked;
   ++h->ri.compactions;
-  if (h->cc_on) reset_components(h, true);  // (the slots shifted: clear_impl emptied the structure, the insert made it incomplete)
+  if (h->cc_on && !carry) reset_components(h, true);  // (the slots shifted: clear_impl emptied the structure, the insert made it incomplete)
+  if (carry) {  // the renumbered forest and its unions word become the structure of the rebuilt store: as complete as it was
+    APSS_TRY(components_stage(h, [&] { return cr_install(h->cc, h->stream, live_rows); }));
+    h->cci.complete = cc_complete || live_rows == 0;
+    h->cci.resets = cc_resets;
+    float remap_ms = 0.f;
+    if (hipEventElapsedTime(&remap_ms, h->cr_ev0, h->cr_ev1) == hipSuccess) h->ccri.remap_ms = remap_ms;  // (the stream has been waited for)
+    ++h->ccri.remaps;
+  }
   return APSS_OK;
 }
 
@@ -3644,6 +3698,18 @@ int32_t gather_stored_rows(apss_handle *h, int64_t sel_rows, int64_t sel_nnz) {
   return APSS_OK;
 }
 
+// ... step 3: the rows the handle's scan arrays select -- whoever wrote them: k_qs_select for an id list, k_cr_detach for the
+// components a removal touched -- become the staged query batch and are probed with their slot list
+int32_t probe_selected_rows(apss_handle *h, int64_t sel_rows, int64_t sel_nnz, bool absorb_only, int64_t *n_results) {
+  h->q_nonneg = true;
+  h->q_max_nnz = 0;
+  h->q_max_norm2 = 0.f;
+  if (sel_rows > 0) APSS_TRY(gather_stored_rows(h, sel_rows, sel_nnz));
+  // (qs_slots: the slot of every selected row -- what the components stage maps the batch's rows with)
+  return probe(h, QueryBatch{{sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz,
+                             sel_rows > 0 ? h->qs_slots.p : nullptr, absorb_only}, n_results);
+}
+
 // apss_query_stored: the live stored rows named by d_ids[0, n) (device) become the staged query batch -- selected, scanned and
 // gathered on the device (apss_query_stored.hpp), never through ingest: they were normalised, pruned and admitted when they came
 // in -- and the batch is probed as the outside batch apss_query_dev would stage from the same rows.
@@ -3657,13 +3723,60 @@ int32_t query_stored_impl(apss_handle *h, int64_t n, const int64_t *d_ids, int64
   h->qsi.rows_selected = sel_rows;
   h->qsi.nnz_selected = sel_nnz;
   if (n_rows) *n_rows = sel_rows;
-  h->q_nonneg = true;
-  h->q_max_nnz = 0;
-  h->q_max_norm2 = 0.f;
-  if (sel_rows > 0) APSS_TRY(gather_stored_rows(h, sel_rows, sel_nnz));
-  // (qs_slots: the slot of every selected row -- what the components stage maps the batch's rows with)
-  return probe(h, QueryBatch{{sel_rows, h->q_rowptr.p, h->q_idx.p, h->q_val.p, h->q_ext.p}, -1, h->q_max_nnz, h->q_max_norm2, sel_nnz,
-                             sel_rows > 0 ? h->qs_slots.p : nullptr}, n_results);
+  return probe_selected_rows(h, sel_rows, sel_nnz, false, n_results);
+}
+
+// The components a removal touched, taken apart and re-joined (apss_components_repair.hpp; include/apss.h: "with the repair on").
+// Runs behind k_rm_mark with `marked` > 0 rows newly marked, the repair and the components on.  A failure leaves the caller to
+// reset the structure.
+int32_t repair_components(apss_handle *h, int64_t marked) {
+  apss_components_repair_info &ri = h->ccri;
+  const int64_t rows = h->n_rows;
+  ri.declined = APSS_CCR_RAN;
+  for (DevBuf<int64_t> *b : {&h->s_keep, &h->s_cnt, &h->s_rowdst, &h->s_nnzdst}) APSS_TRY(ensure(h, *b, (size_t)rows + 1));
+  APSS_TRY(ensure(h, h->qs_ctr, 2));
+  HIPCHK(h, hipMemsetAsync(h->qs_ctr.p, 0, 2 * sizeof(unsigned long long), h->stream));
+  HIPCHK(h, begin_timed(h->stream, h->cr_ev0));
+  APSS_TRY(run_stage(h, "components repair", h->cc.mem, [&](const char **) {
+    return cr_detach_select(h->cc, h->stream, rows, h->dead.p, h->rowptr.p, h->s_keep.p, h->s_cnt.p, h->qs_ctr.p, &ri.launches);
+  }));
+  APSS_TRY(scan_i64(h, (const int64_t *)h->s_keep.p, h->s_rowdst.p, rows, &ri.launches));
+  APSS_TRY(scan_i64(h, (const int64_t *)h->s_cnt.p, h->s_nnzdst.p, rows, &ri.launches));
+  // the ONE readback between detach and gather: the two scan totals (the rows to re-join, their entries) and the flagged roots
+  int64_t *back = h->scalars->stored_back;
+  float ms = 0.f;
+  HIPCHK(h, end_timed_read(h->stream, h->cr_ev0, h->cr_ev1, {{&back[0], h->s_rowdst.p + rows, sizeof(int64_t)}, {&back[1], h->s_nnzdst.p + rows, sizeof(int64_t)},
+                                                       {&back[2], h->qs_ctr.p, sizeof(unsigned long long)}}, &ms));
+  ri.detach_ms = ms;
+  const int64_t sel_rows = back[0], sel_nnz = back[1];
+  // (every row marked by an earlier call is a singleton that flagged itself: the others are the components this call touched)
+  ri.components_touched = back[2] - (h->rm_marked - marked);
+  if (sel_rows < 0 || sel_rows > rows - h->rm_marked || sel_nnz < 0 || sel_nnz > h->nnz || ri.components_touched < 0)
+    return fail(h, APSS_E_STATE, "components repair: the selection and the store disagree");
+  if (sel_rows > h->ccr_max) {  // today's rule: a remove never costs more than the caller allowed
+    ri.declined = APSS_CCR_BUDGET;
+    ++ri.budget_resets;
+    reset_components(h, true);
+    return APSS_OK;
+  }
+  ++ri.repairs;
+  if (sel_rows == 0) return APSS_OK;  // (the marked rows were singletons: the last call's results stay)
+  ri.rows_rejoined = sel_rows;
+  // the re-join is a probe of the selected rows: the last results and query batch are gone from here on, also when it fails
+  forget_last_call(h);
+  h->qsi = apss_stored_query_info{};
+  h->qsi.rows_selected = sel_rows;
+  h->qsi.nnz_selected = sel_nnz;
+  HIPCHK(h, begin_timed(h->stream, h->cr_ev0));
+  const int32_t rc = probe_selected_rows(h, sel_rows, sel_nnz, true, nullptr);  // (no per-query or global cut: the forest alone wants the list)
+  forget_last_call(h);  // (its list went into the forest; nobody asked for it)
+  APSS_TRY(rc);
+  HIPCHK(h, end_timed_read(h->stream, h->cr_ev0, h->cr_ev1, {}, &ms));
+  ri.rejoin_ms = ms;
+  ri.launches += h->qsi.launches;
+  ri.pairs_rejoined = h->cci.pairs_absorbed;
+  if (h->cci.declined != APSS_CC_RAN) return fail(h, APSS_E_STATE, "components repair: the re-join's list was not absorbed");
+  return APSS_OK;
 }
 
 int32_t check_stored_query(apss_handle *h, const char *what, int64_t n, const int64_t *ids, int64_t *n_rows, int64_t *n_results) {
@@ -4182,6 +4295,32 @@ int32_t apss_components_fetch(apss_handle *h, int64_t offset, int64_t count, int
   return APSS_OK;
 }
 
+int32_t apss_set_components_repair(apss_handle *h, int64_t max_rows) {
+  if (!h) return APSS_E_INVALID;
+  // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
+  if (h->sharded)
+    return fail(h, APSS_E_UNSUPPORTED, g_create_error = "apss_set_components_repair: a term shard keeps no components (apss_set_components) to repair");
+  if (max_rows < 0 || max_rows > 0x7fffffffLL)
+    return fail(h, APSS_E_INVALID, g_create_error = "apss_set_components_repair: max_rows must be in [0, 2^31 - 1] (0: off)");
+  h->ccr_max = max_rows;
+  return APSS_OK;
+}
+
+int32_t apss_components_repair_get(apss_handle *h, apss_components_repair_info *out) {
+  if (!h || !out) return APSS_E_INVALID;
+  const int32_t caller = out->struct_size;
+  if (caller < (int32_t)(2 * sizeof(int32_t)) || caller > (1 << 16))
+    return fail(h, APSS_E_INVALID, "apss_components_repair_info.struct_size must be set to sizeof(apss_components_repair_info) before the call");
+  const int32_t n = std::min<int32_t>(caller, (int32_t)sizeof(apss_components_repair_info));
+  apss_components_repair_info ri = h->ccri;  // (what the last remove left is the handle's; the answer is a copy)
+  ri.struct_size = n;
+  ri.max_rows = h->ccr_max;
+  // no remove has marked a row yet, or the last one marked none: `declined` says why a remove would not repair NOW (include/apss.h)
+  if (ri.rows_marked == 0) ri.declined = h->ccr_max <= 0 ? APSS_CCR_OFF : !h->cc_on ? APSS_CCR_NO_COMPONENTS : APSS_CCR_NOTHING;
+  std::memcpy(out, &ri, (size_t)n);
+  return APSS_OK;
+}
+
 int32_t apss_set_top_k_window(apss_handle *h, int64_t max_pairs) {
   if (!h) return APSS_E_INVALID;
   // (a refusal is left for apss_last_error(NULL) too, as apss_set_top_k's)
@@ -4218,6 +4357,7 @@ int32_t apss_remove(apss_handle *h, int64_t n, const int64_t *ext_ids, int64_t *
   if (n_rows_removed) *n_rows_removed = 0;
   if (h->sharded) return refuse_shard_removal(h, "apss_remove");
   if (n < 0 || (n > 0 && !ext_ids)) return fail(h, APSS_E_INVALID, "apss_remove: n >= 0 ids");
+  begin_repair_call(h);
   if (n == 0 || h->n_rows == 0) return APSS_OK;
   APSS_TRY(ensure(h, h->rm_ids, (size_t)n));
   HIPCHK(h, hipMemcpyAsync(h->rm_ids.p, ext_ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
@@ -4232,6 +4372,7 @@ int32_t apss_remove_dev(apss_handle *h, int64_t n, const int64_t *d_ext_ids, int
   if (n_rows_removed) *n_rows_removed = 0;
   if (h->sharded) return refuse_shard_removal(h, "apss_remove_dev");
   if (n < 0 || (n > 0 && !d_ext_ids)) return fail(h, APSS_E_INVALID, "apss_remove_dev: n >= 0 ids");
+  begin_repair_call(h);
   int64_t newly = 0;
   APSS_TRY(remove_impl(h, n, d_ext_ids, &newly));
   if (n_rows_removed) *n_rows_removed = newly;

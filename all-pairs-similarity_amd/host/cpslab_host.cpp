@@ -242,6 +242,10 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
       last_error_ = "cpslab.allpair.gpu.components ignored: a term-sharded worker keeps no components (apss_set_components: plain handles only)";
       conf_.components = false;
     }
+    if (conf.componentsRepairRows != 0) {
+      last_error_ = "cpslab.allpair.gpu.componentsRepairRows ignored: a term-sharded worker keeps no components (apss_set_components_repair: plain handles only)";
+      conf_.componentsRepairRows = 0;
+    }
     return;
   }
   if (conf.devices.size() == 1) c.device_id = conf.devices[0];
@@ -273,6 +277,12 @@ GpuIndexingWorker::GpuIndexingWorker(const Config &conf, ReplyTo replyTo) : conf
   }
   if (conf.components && apss_set_components(h_, 1) != APSS_OK) {
     const std::string msg = std::string("apss_set_components: ") + apss_last_error(h_);
+    apss_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error(msg);
+  }
+  if (conf.componentsRepairRows != 0 && apss_set_components_repair(h_, conf.componentsRepairRows) != APSS_OK) {
+    const std::string msg = std::string("apss_set_components_repair: ") + apss_last_error(h_);
     apss_destroy(h_);
     h_ = nullptr;
     throw std::runtime_error(msg);

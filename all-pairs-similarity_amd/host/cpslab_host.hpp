@@ -117,6 +117,10 @@ struct Config {
   // -- the connected components of the graph whose edges are the pairs of its replies -- on the device (apss_set_components) and
   // GpuIndexingWorker::groups() reads them.  A term-sharded worker has none: reported through lastError(), it runs without
   bool components = false;
+  // cpslab.allpair.gpu.componentsRepairRows: 0 (default) = off; N in 1 .. 2^31 - 1 = with components, a remove re-joins the live
+  // vectors of the groups it touched, at most N of them, instead of forgetting every group, and a compaction keeps the groups
+  // (apss_set_components_repair).  A term-sharded worker has none: reported through lastError(), it runs with 0
+  long componentsRepairRows = 0;
 };
 
 // IndexingWorkerActor with vectorsStore / invertedIndex resident on the GPU.

@@ -89,6 +89,15 @@ private class GpuIndexingWorkerActor(conf: Config) extends Actor {
     System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.components needs one GPU (cpslab.allpair.gpu.devices with one entry); running without")
   if (!grouped && components)
     require(NativeApss.setComponents(handle, true) == 0, NativeApss.lastError(handle))
+  // cpslab.allpair.gpu.componentsRepairRows = N (default 0: off; one GPU only, with components): a withdrawal re-joins the live
+  // vectors of the groups it touched, at most N of them, instead of forgetting every group, and a compaction keeps the groups
+  // (apss_set_components_repair)
+  private val componentsRepairRows =
+    if (conf.hasPath("cpslab.allpair.gpu.componentsRepairRows")) conf.getLong("cpslab.allpair.gpu.componentsRepairRows") else 0L
+  if (grouped && componentsRepairRows != 0L)
+    System.err.println("GpuIndexingWorkerActor: cpslab.allpair.gpu.componentsRepairRows needs one GPU (cpslab.allpair.gpu.devices with one entry); running with 0")
+  if (!grouped && componentsRepairRows != 0L)
+    require(NativeApss.setComponentsRepair(handle, componentsRepairRows) == 0, NativeApss.lastError(handle))
   /** the near-duplicate groups: for every store slot (smallest slot of its component | -1 for a withdrawn vector, the name of the
     * vector in that slot); null when cpslab.allpair.gpu.components is off */
   def groups(): (Array[Int], Array[String]) =

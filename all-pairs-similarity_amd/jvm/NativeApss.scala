@@ -29,6 +29,12 @@ object NativeApss {
     * frees them.  Travels through `submit` (mode 8 of apss_jni.c): no further native entry point.  0 or a negative status */
   def setComponents(h: Long, on: Boolean): Int =
     submit(h, 8, Array(0L, 0L), new Array[Int](0), new Array[Double](0), Array(if (on) 1L else 0L)).toInt
+  /** the groups across remove and compact (include/apss.h, apss_set_components_repair; one handle only): 0 = off; maxRows in
+    * 1 .. 2^31 - 1 = a remove re-joins the live vectors of the groups it touched, at most maxRows of them (more: every group is
+    * forgotten, as with 0), and a compaction keeps the groups.  Travels through `submit` (mode 10 of apss_jni.c).  0 or a negative
+    * status */
+  def setComponentsRepair(h: Long, maxRows: Long): Int =
+    submit(h, 10, Array(0L, 0L), new Array[Int](0), new Array[Double](0), Array(maxRows)).toInt
   /** the groups as they are now: for every store slot, in slot order, (the smallest slot of its component | -1 for a removed
     * vector, the id of the vector in that slot | the removed vector's own).  Rides on `submit` (mode 9: apss_components_get, the
     * slots labelled) and on `fetch` with minus that count (apss_components_fetch).  null when the setting is off or on an error

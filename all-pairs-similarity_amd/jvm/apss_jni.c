@@ -147,6 +147,9 @@ static int32_t handle_submit(void *t, int mode, int64_t n, const int64_t *rp, co
     if (rc == APSS_OK) *n_res = ci.rows;
     return rc;
   }
+  /* ... and their repair across remove and compact (NativeApss.setComponentsRepair): mode 10 = apss_set_components_repair of ids(0)
+   * (the CSR is one empty row) */
+  if (mode == 10) return apss_set_components_repair((apss_handle *)t, n == 1 ? id[0] : -1);
   return apss_insert_and_query((apss_handle *)t, n, rp, ix, vl, id, n_res);
 }
 

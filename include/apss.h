@@ -658,6 +658,69 @@ int32_t apss_components_get(apss_handle *h, apss_components_info *out);
 int32_t apss_components_dev(apss_handle *h, const int32_t **d_label, int64_t *rows);
 int32_t apss_components_fetch(apss_handle *h, int64_t offset, int64_t count, int32_t *out_label, int64_t *out_rep_ext);
 
+/* ---- near-duplicate groups across a removal and a compaction: the repair ----
+ * The rules above make apss_remove and apss_compact forget the groups: every slot becomes a singleton and only a whole-store
+ * apss_self_join brings them back.  With the repair on, a removal re-joins the components it touched and nothing else, and a
+ * compaction renumbers the forest instead of forgetting it.  Plain handles only.  Default off: with the setting off every call
+ * launches, reads and allocates exactly what it does without this section.
+ *
+ * The setting.
+ *  - apss_set_components_repair(h, max_rows): 0 is off.  1 .. 2^31 - 1 is the budget: the most live rows one apss_remove[_dev]
+ *    may re-join.
+ *  - It may change at any time and survives apss_clear.  It has no effect while apss_set_components is off.
+ * What changes with the repair on (and apss_set_components on).
+ *  - apss_remove[_dev] that newly marks at least one row, on the handle's stream behind the marking:
+ *    - The forest is flattened, every marked slot flags its root, and every slot under a flagged root becomes a singleton again.
+ *      The live ones among them, A rows, are the rows to re-join.  A is read back: one wait.
+ *    - A = 0 (the marked rows were singletons): nothing is re-joined.  The last call's results stay fetchable, complete and resets
+ *      are unchanged, declined = APSS_CCR_RAN.
+ *    - 0 < A <= max_rows: the A rows are gathered and probed as the batch apss_query_stored of them would be, and their list goes
+ *      behind k_rm_drop into the forest.  complete and resets stay as they were.  The re-join is a probe: the last call's results
+ *      and query batch are gone afterwards (APSS_E_STATE, as after an insert), and apss_stats, apss_removal_info.pairs_dropped
+ *      and apss_components_info.pairs_absorbed speak of the re-join.  Its list is wanted by the forest alone: neither
+ *      apss_set_top_k nor apss_set_top_pairs cuts it, nothing of it is kept (apss_stats.result_pairs = 0), and
+ *      apss_set_top_k_window bounds its memory as it bounds a call's.
+ *    - A > max_rows: the rule without the repair -- reset to singletons, complete = 0 unless the store is empty, resets + 1 --
+ *      and declined = APSS_CCR_BUDGET, budget_resets + 1.  A remove never costs more than the caller allowed.
+ *    - A failure inside the stage fails the call and leaves the structure reset with complete = 0.  The marks stay: the removal
+ *      happened.
+ *  - Why complete may stay 1: a marked row is always a singleton once apss_remove returns.  A live edge with no end in a touched
+ *    component is still in the forest; one with an end in a touched component has both ends there, both are re-joined, and the
+ *    edge is in the re-join's list.  The labels are those of a fresh apss_self_join over the live rows.  A structure that was
+ *    incomplete stays incomplete and stays never wrong about an edge.
+ *  - apss_compact and auto-compaction renumber the forest: label and parent move with the rows to their new slots.  complete and
+ *    resets stay, remaps + 1.  The insert that an auto-compaction precedes then follows its own rule above.
+ *  - Errors.
+ *    - APSS_E_INVALID: NULL handle, max_rows < 0 or > 2^31 - 1, bad struct_size.
+ *    - APSS_E_UNSUPPORTED ("term shard"): the setter on a term shard.
+ *    - apss_group has no such call. */
+#define APSS_CCR_RAN 0
+#define APSS_CCR_OFF 1            /* this setting off */
+#define APSS_CCR_NO_COMPONENTS 2  /* apss_set_components off */
+#define APSS_CCR_BUDGET 3         /* more rows to re-join than max_rows: reset to singletons */
+#define APSS_CCR_NOTHING 4        /* nothing newly marked: nothing launched */
+typedef struct apss_components_repair_info {
+  int32_t struct_size;         /* IN: caller's sizeof; OUT: bytes written (as apss_stats) */
+  int32_t declined;            /* APSS_CCR_* of the last apss_remove[_dev].  While that call (or no call yet) marked no row, the getter
+                                  answers from the settings as they are now: OFF, NO_COMPONENTS or NOTHING */
+  int64_t max_rows;            /* the setting (0: off) */
+  int64_t rows_marked;         /* rows newly marked by that call */
+  int64_t components_touched;  /* components that held a newly marked row */
+  int64_t rows_rejoined;       /* live rows taken apart and re-joined */
+  int64_t pairs_rejoined;      /* length of the list the re-join absorbed */
+  int64_t repairs;             /* since create: removes that ran the stage */
+  int64_t budget_resets;       /* since create: removes declined with APSS_CCR_BUDGET */
+  int64_t remaps;              /* since create: compactions that renumbered the forest */
+  double detach_ms;            /* device time of flatten, touch, detach and the scans of that call, HIP events */
+  double rejoin_ms;            /* device time of its gather and probe */
+  double remap_ms;             /* device time of the last compaction's flatten and renumbering */
+  int32_t launches;            /* kernel launches of that call's repair stage, its scans and gather included, the re-join's probe not
+                                  (apss_stats has it) */
+  int32_t reserved0;           /* 0 */
+} apss_components_repair_info; /* 104 bytes */
+int32_t apss_set_components_repair(apss_handle *h, int64_t max_rows);
+int32_t apss_components_repair_get(apss_handle *h, apss_components_repair_info *out);
+
 
 /* =====================================================================================================================
  * apss_group: the sharded index of one node -- T term ranges x D row ranges of member shards, one per GPU -- behind ONE

@@ -4,7 +4,13 @@ profiles/components.md quotes them.
                                           replaces (fetch the whole list, scipy connected_components on the host); labels compared
   python profiles/components.py stream    bench_stream.py's shape: 1M vectors in 1,024-row insert_and_query calls, off against on
   python profiles/components.py stream-short [on]   the first 64 such calls alone (the run a kernel trace is taken of)
-  python profiles/components.py path | star         the adversarial shapes at 1M rows through apss_self_join"""
+  python profiles/components.py path | star         the adversarial shapes at 1M rows through apss_self_join
+  python profiles/components.py repair    the stream case's store (1M rows) with planted duplicate clusters, 1,000 ids removed in
+                                          batches of 100 with apss_set_components_repair on: wall of every remove, rows_rejoined,
+                                          detach_ms, rejoin_ms; then compact() with the forest carried
+  python profiles/components.py rejoin    the route without the repair, which every commit since apss_set_components has: the same
+                                          removes, each followed by the apss_self_join that makes the structure complete again;
+                                          then compact()"""
 import json
 import os
 import sys
@@ -136,6 +142,46 @@ def adversarial(which):
         print(json.dumps(dict(what=which + " of 1M rows", labels_all_zero=bool((labels == 0).all()))), flush=True)
 
 
+def removal(repair_on):
+    c = synth.CONFIGS["c3"]
+    n, dup = c["n"], 0.2
+    rp, idx, val = synth.make_vectors(n, c["dim"], c["nnz"], c["zipf_s"], c["seed"], dup_frac=dup)
+    ids = np.arange(n, dtype=np.int64)
+    gone = np.random.default_rng(1).permutation(n)[:1000].astype(np.int64)
+    kw = dict(components_repair=n) if repair_on else {}
+    with ApssIndex(c["dim"], c["theta"], components=True, **kw) as ix:
+        ix.insert(ids, rp, idx, val)
+        ix.self_join(fetch=False)
+        start = ix.components_info()
+        print(json.dumps(dict(what="store", rows=n, dup_frac=dup, components=start["components"], largest=start["largest"],
+                              complete=start["complete"])), flush=True)
+        for b in range(0, 1000, 100):
+            t = time.perf_counter()
+            marked = ix.remove(gone[b:b + 100])
+            remove_ms = (time.perf_counter() - t) * 1e3
+            rec = dict(what="remove of 100 ids", repair=repair_on, batch=b // 100, rows_marked=int(marked), remove_wall_ms=remove_ms)
+            if repair_on:
+                ri = ix.components_repair_info()
+                rec.update(declined=ri["declined"], components_touched=ri["components_touched"], rows_rejoined=ri["rows_rejoined"],
+                           pairs_rejoined=ri["pairs_rejoined"], detach_ms=ri["detach_ms"], rejoin_ms=ri["rejoin_ms"], launches=ri["launches"])
+            else:
+                t = time.perf_counter()
+                ix.self_join(fetch=False)
+                rec.update(self_join_wall_ms=(time.perf_counter() - t) * 1e3)
+                rec.update(route_wall_ms=remove_ms + rec["self_join_wall_ms"])
+            info = ix.components_info()
+            rec.update(complete=info["complete"], components=info["components"])
+            print(json.dumps(rec), flush=True)
+        t = time.perf_counter()
+        ix.compact()
+        rec = dict(what="compact", repair=repair_on, compact_wall_ms=(time.perf_counter() - t) * 1e3, compact_ms=ix.removal_info()["compact_ms"])
+        info = ix.components_info()
+        rec.update(complete=info["complete"], components=info["components"], rows=info["rows"])
+        if repair_on:
+            rec.update(remap_ms=ix.components_repair_info()["remap_ms"])
+        print(json.dumps(rec), flush=True)
+
+
 which = sys.argv[1] if len(sys.argv) > 1 else "join"
 if which == "join":
     join()
@@ -143,5 +189,7 @@ elif which == "stream":
     stream()
 elif which == "stream-short":
     stream(calls=64, settings=(len(sys.argv) > 2 and sys.argv[2] == "on",))
+elif which in ("repair", "rejoin"):
+    removal(which == "repair")
 else:
     adversarial(which)
