@@ -45,7 +45,7 @@
 // strip of round v readable during round v while round v + 2 is being staged.
 //
 // TWO PLANES, ONE BARRIER PER ROUND (TWO: k_probe_planes, the plain 512-thread handle over <= 32768-row tiles whose sums fit a
-// byte -- acc8_scale() in apss_hip.hip).  The second barrier of a round exists only because the clears write the plane the
+// byte -- acc8_scale() in apss_filter_plan.hpp).  The second barrier of a round exists only because the clears write the plane the
 // next round adds into.  With two planes of 8-bit sums in the same 64 KB, round v adds into plane v mod 2, and round v - 1 is
 // cleared on the OTHER plane at the top of round v, directly ahead of round v's adds, from the posting registers that still
 // hold it (the wfa / wfb set that round v's loads for v + 1 have not yet overwritten): one barrier and one drain of the LDS

@@ -81,25 +81,15 @@ struct DebugCfg {
                                // run_sub=W      run-reading build: scatter in two passes through sub-ranges of W terms (a power of two >= 64; 0: one pass)
                                // no_bucket      large dims build with global atomics (never the bucketed LDS build)
   bool build_trace = false;    // build_trace    one line on stderr per index build: which kernels it took
-  bool chunk8 = false;         // chunk8         filter kernel with 8-posting chunks (4-step window)
+  FilterHooks filter;          // what the filter plan reads (apss_filter_plan.hpp has each token): chunk8, window=U, no_acc8, no_planes, planes, flat_group=L, no_even, merge=L, merge_u=U, merge_single=U
   bool shard_exact = false;    // shard_exact    term-range shards run the single-pass exact kernel
   bool diag = false;           // diag           in-kernel cycle stamps of the single-pass kernel (stderr)
   bool force_general = false;  // force_general  as APSS_FLAG_FORCE_GENERAL
   bool exact_accum = false;    // exact_accum    as APSS_FLAG_EXACT_ACCUM, decided per probe
-  bool big_u5 = false;         // big_u5         1024-thread filter kernel keeps its 5-step window
   int cx_tile = 0;             // cx_tile=N      rows per tile of the coarse index (multiple of 64, <= 65536)
-  int window = 0;              // window=U       register-window steps of the 512-thread filter kernel (2..5)
   int chunks = 0;              // chunks=N       query chunks per tile (grid shape)
   int tiles_per_launch = 0;    // tiles_per_launch=N
   bool no_tail = false;        // no_tail        every insert extends the tile index at once (no tail of waiting rows)
-  bool no_acc8 = false;        // no_acc8        term shards keep 16-bit accumulators over 32768-row tiles
-  bool no_planes = false;      // no_planes      a plain 512-thread handle keeps k_probe_even's 16-bit sums and two barriers per round (never k_probe_planes); no_acc8 implies it
-  bool planes = false;         // planes         ... and takes k_probe_planes whatever the length of its query chunks (default: chunks of kPlanesMinChunk rounds or more)
-  int flat_group = -1;         // flat_group=L   k_probe_even: 2^L staging lanes per term (default: as many as keep the staging waves <= 1/4)
-  int pad_lds = 0;             // pad_lds=N      N bytes of dynamic LDS on the filter launch (occupancy experiments)
-  bool longpf = false;         // longpf         prefetched, group-parallel long-segment sweeps on a plain handle too (experiment)
-  bool even_wide = false;      // even_wide      k_probe_even also with one staging lane per term and windows of up to 7 steps (experiment)
-  bool no_even = false;        // no_even        the filter stages every round on all waves (k_probe_coarse), never on F of them (k_probe_even)
   int seg_align = 0;           // seg_align=N    postings per aligned unit of the coarse index (16 | 32)
   int fold_w = 0;              // fold_w=N       columns of the dense head's folded block (128 | 256)
   bool no_sym = false;         // no_sym         as APSS_FLAG_NO_SYMMETRY
@@ -108,10 +98,7 @@ struct DebugCfg {
   bool no_append = false;      // no_append      a batch that lands in a partly filled tile rebuilds the whole tile (never appends to it)
   int res_cap = 0;             // res_cap=N      initial capacity of the candidate list (tests of the overflow -> regrow -> re-run path)
   bool head_bf16 = false;      // head_bf16      the dense-head block keeps bf16 rows (v_mfma_f32_32x32x16_bf16), never the INT8 rendering
-  int merge = -1;              // merge=L        a term shard's thin rounds: at most 2^L query rows share a round (0: never; default 1: two rows)
   bool no_merge_prune = false; // no_merge_prune merged rounds hand every expanded pair to the exchange (no exact shard-rule test behind k_expand_merged)
-  int merge_u = 0;             // merge_u=U      ... as long as the merged round fits a window of U steps (default 7)
-  int merge_single = 0;        // merge_single=U ... and a single row's round takes a window of at most U steps (default 4)
   bool no_fused_ingest = false; // no_fused_ingest a plain batch is ingested by k_ingest_count + k_ingest_write too (never the one-pass k_ingest_plain)
   bool no_persist = false;     // no_persist     k_probe_even launches one workgroup per (tile, chunk) cell, never resident workgroups over a work list
   int persist_wgs = 0;         // persist_wgs=N  ... the persistent launch has N workgroups (default: as many as the chip holds at a time)
@@ -143,25 +130,21 @@ DebugCfg parse_debug_env() {
     else if (key == "run_lanes") d.build.run_lanes = val;
     else if (key == "run_sub") d.build.run_sub = val;
     else if (key == "build_trace") d.build_trace = val != 0;
-    else if (key == "chunk8") d.chunk8 = val != 0;
+    else if (key == "chunk8") d.filter.chunk8 = val != 0;
     else if (key == "shard_exact") d.shard_exact = val != 0;
     else if (key == "diag") d.diag = val != 0;
     else if (key == "force_general") d.force_general = val != 0;
     else if (key == "exact_accum") d.exact_accum = val != 0;
-    else if (key == "big_u5") d.big_u5 = val != 0;
     else if (key == "cx_tile") d.cx_tile = val;
-    else if (key == "window") d.window = val;
+    else if (key == "window") d.filter.window = val;
     else if (key == "chunks") d.chunks = val;
     else if (key == "tiles_per_launch") d.tiles_per_launch = val;
     else if (key == "no_tail") d.no_tail = val != 0;
-    else if (key == "no_acc8") d.no_acc8 = val != 0;
-    else if (key == "no_planes") d.no_planes = val != 0;
-    else if (key == "planes") d.planes = val != 0;
-    else if (key == "no_even") d.no_even = val != 0;
-    else if (key == "even_wide") d.even_wide = val != 0;
-    else if (key == "longpf") d.longpf = val != 0;
-    else if (key == "pad_lds") d.pad_lds = (int)val;
-    else if (key == "flat_group") d.flat_group = (int)val;
+    else if (key == "no_acc8") d.filter.no_acc8 = val != 0;
+    else if (key == "no_planes") d.filter.no_planes = val != 0;
+    else if (key == "planes") d.filter.planes = val != 0;
+    else if (key == "no_even") d.filter.no_even = val != 0;
+    else if (key == "flat_group") d.filter.flat_group = (int)val;
     else if (key == "seg_align") d.seg_align = val;
     else if (key == "fold_w") d.fold_w = val;
     else if (key == "mix") d.mix = val;
@@ -171,10 +154,10 @@ DebugCfg parse_debug_env() {
     else if (key == "head_bf16") d.head_bf16 = val != 0;
     else if (key == "res_cap") d.res_cap = val;
     else if (key == "no_bucket") d.build.no_bucket = val != 0;
-    else if (key == "merge") d.merge = (int)val;
-    else if (key == "merge_u") d.merge_u = (int)val;
+    else if (key == "merge") d.filter.merge = (int)val;
+    else if (key == "merge_u") d.filter.merge_u = (int)val;
     else if (key == "no_merge_prune") d.no_merge_prune = val != 0;
-    else if (key == "merge_single") d.merge_single = (int)val;
+    else if (key == "merge_single") d.filter.merge_single = (int)val;
     else if (key == "no_fused_ingest") d.no_fused_ingest = val != 0;
     else if (key == "no_persist") d.no_persist = val != 0;
     else if (key == "persist_wgs") d.persist_wgs = val;
@@ -466,8 +449,6 @@ int32_t enter(apss_handle *h) {
   if (e != hipSuccess) return fail(h, APSS_E_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
   return APSS_OK;
 }
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- ingest: validate (+ optional normalise / admission / value prune / term-range filter) and append ----
 // Source arrays are device pointers (batch-relative rowptr).  Destination: the store (to_store) or the query
@@ -1044,38 +1025,11 @@ int32_t ensure_exact_index(apss_handle *h) {
   return APSS_OK;
 }
 
-// 8-bit accumulator scale of a term shard: the largest S = 2^k <= 2^7 with  S * max|q||c| * 1.0005 + shared terms < 2^8  (no
-// carry into the neighbour's byte), taken only while the threshold in units stays well above what a chance pair collects
-// (one unit of round-up per shared term).  0: not usable.
-double acc8_scale(double bound, double shared, double theta) {
-  for (int k = 7; k >= 5; --k) {
-    const double S = std::ldexp(1.0, k);
-    if (bound * 1.0005 * S < 255.0 - shared && std::floor(theta * S * (1.0 - 1.0 / 2048 - 1e-6)) - 2 >= 12.0) return S;
-  }
-  return 0.0;
-}
-
-// rows per tile of the coarse rendering when the handle chooses them (no tile_rows, no cx_tile), from the store's shape: `rows`
-// rows of `nnz` entries, the longest of `max_nnz`, the largest squared norm `max_norm2`
-int32_t pick_cx_tile(const apss_handle *h, int64_t rows, int64_t nnz, int64_t max_nnz, float max_norm2) {
-  // a round's cost is mostly fixed, so what matters is how many postings a (tile, term) segment holds:
-  // rows_per_tile * nnz_per_row / dim.  Below ~16 at 32768 rows (C5 shape: 6.5) the 65536-row tile with one
-  // 1024-thread workgroup per CU wins (C5 shape at N=2M: 647 vs 790 ms); at C3 (33) two workgroups per CU win.
-  const double seg32 = 32768.0 * ((double)nnz / (double)rows) / (double)h->cfg.dim;
-  int32_t cb = seg32 < 16.0 && !h->sharded && !h->head_k ? 65536 : 32768;  // (the 1024-thread kernel has no shard variant)
-  // sparser still (C5: 6.5): 131072-row tiles with 8-bit accumulators (k_probe_coarse<1024, .., ACC8>) when the norms and
-  // row lengths leave room for them: half the segment-descriptor look-ups and half the half-empty posting lines
-  if (cb == 65536 && seg32 < 8.0 && h->nonneg && !h->dbgcfg.no_acc8 && !h->no_acc8 && max_nnz <= 512 &&
-      acc8_scale((double)max_norm2 * 1.0001 + 1e-6, (double)max_nnz, h->cfg.theta) > 0)
-    cb = 131072;
-  // a term shard's rounds are thin (1/T of every query's terms): 8-bit accumulators hold 65536 candidates in the same
-  // 64 KB, i.e. half the rounds at the same two workgroups per CU -- when the norms and row lengths leave room for them
-  // (with a dense-head block: only while the tail has no long segments -- the prefetched long-segment sweeps exist for
-  // 16-bit accumulators over 32768-row tiles only; known after the build, so an optimistic first build may be repeated)
-  if ((h->sharded || h->head_k) && !(h->head_k && h->head_longseg) && !h->dbgcfg.no_acc8 && !h->no_acc8 &&
-      acc8_scale((double)max_norm2 * 1.0001 + 1e-6, (double)max_nnz, h->cfg.theta) > 0)
-    cb = 65536;
-  return cb;
+// rows per tile of the coarse rendering when the handle chooses them (no tile_rows, no cx_tile), for a store of `rows` rows of `nnz` entries
+int32_t pick_cx_tile(const apss_handle *h, int64_t rows, int64_t nnz) {
+  return pick_cx_tile(TileFacts{rows, nnz, h->store_max_nnz, h->store_max_norm2, h->sharded, h->head_k, h->head_longseg, h->nonneg, h->no_acc8,
+                                h->cfg.theta, h->cfg.dim},
+                      h->dbgcfg.filter);
 }
 
 // Will the index build that follows a plain store batch of n rows / nnz entries at row dst_row0 read runs (build_tiles), and in
@@ -1087,7 +1041,7 @@ bool ingest_wants_cuts(const apss_handle *h, int64_t dst_row0, int64_t n, int64_
   const apss_handle::IndexSet &ix = h->use_coarse ? h->cx : h->ex;
   *cb = ix.cb;
   if (h->use_coarse && ix.n_tiles == 0 && h->cfg.tile_rows == 0 && !h->dbgcfg.cx_tile)
-    *cb = pick_cx_tile(h, rows, entries, h->store_max_nnz, h->store_max_norm2);
+    *cb = pick_cx_tile(h, rows, entries);
   if (*cb <= 0) return false;
   // build_tiles' own decision, for the tiles this batch is expected to (re)build and the store as it will be
   const BuildPlan plan = build_plan(BuildShape{h->cfg.dim, h->cfg.term_lo, h->cfg.term_hi, *cb, ix.coarse, std::min(h->idx_rows, dst_row0) / *cb,
@@ -1589,7 +1543,7 @@ int32_t build_index(apss_handle *h, int64_t row0) {
   }
   if (h->use_coarse) {
     if (h->cx.n_tiles == 0 && h->cfg.tile_rows == 0 && !h->dbgcfg.cx_tile && h->idx_rows > 0) {
-      h->cx.cb = pick_cx_tile(h, h->n_rows, h->nnz, h->store_max_nnz, h->store_max_norm2);
+      h->cx.cb = pick_cx_tile(h, h->n_rows, h->nnz);
     }
     APSS_TRY(build_tiles(h, h->cx, row0));
     h->st.build_ms += h->cx.build_ms;
@@ -1660,127 +1614,27 @@ int32_t launch_exact(apss_handle *h, const KernelRef &k, const ProbeArgs &a, siz
 // of LDS: ONE workgroup per CU.  512 threads over tiles of <= 8192 rows hold 58 KB: two per CU
 inline int gen_block(int mode, int cb) { return mode == 2 && cb <= 8192 ? 512 : kProbeBlock; }
 
-// ---- the filter kernel's instantiations: (threads, register-window steps, shard rule, postings per chunk, virtual
-// rows, signed weights).  One table, one lookup: a combination that is not listed is an error, never another kernel.
-#define APSS_CX_VARIANTS(X)                          \
-  X(512, 5, false, 16, false, false, false, false)   \
-  X(512, 4, false, 16, false, false, false, false)   \
-  X(512, 3, false, 16, false, false, false, false)   \
-  X(512, 2, false, 16, false, false, false, false)   \
-  X(512, 5, true, 16, false, false, false, false)    \
-  X(512, 4, true, 16, false, false, false, false)    \
-  X(512, 3, true, 16, false, false, false, false)    \
-  X(512, 2, true, 16, false, false, false, false)    \
-  X(512, 5, true, 16, false, false, false, true)     \
-  X(512, 4, true, 16, false, false, false, true)     \
-  X(512, 3, true, 16, false, false, false, true)     \
-  X(512, 2, true, 16, false, false, false, true)     \
-  X(512, 5, false, 16, false, false, false, true)    \
-  X(512, 4, false, 16, false, false, false, true)    \
-  X(512, 3, false, 16, false, false, false, true)    \
-  X(512, 2, false, 16, false, false, false, true)    \
-  X(512, 5, true, 16, false, false, true, false)     \
-  X(512, 5, false, 16, false, false, true, false)    \
-  X(512, 5, true, 16, true, false, true, false)      \
-  X(512, 4, false, 8, false, false, false, false)    \
-  X(512, 5, false, 16, true, false, false, false)    \
-  X(512, 5, false, 16, false, true, false, false)    \
-  X(512, 5, true, 16, false, true, false, false)     \
-  X(512, 5, false, 16, true, true, false, false)     \
-  X(1024, 5, false, 16, false, false, false, false)  \
-  X(1024, 3, false, 16, false, false, false, false)  \
-  X(1024, 5, false, 16, true, false, false, false)   \
-  X(1024, 3, false, 16, true, false, false, false)   \
-  X(1024, 5, false, 16, false, true, false, false)   \
-  X(1024, 3, false, 16, false, true, false, false)   \
-  X(1024, 5, false, 16, false, false, false, true)   \
-  X(1024, 3, false, 16, false, false, false, true)
-
-struct CxVariant {
-  int block, u;
-  bool shard;
-  int chunk;
-  bool vrows, sgn;
-  bool longpf;  // prefetched long-segment sweeps: the sparse half of a handle with a dense-head block
-  bool acc8;    // 8-bit accumulators over 65536-row tiles: thin rounds of a term shard
-  bool even;    // k_probe_even: a round is staged by ceil(longest query / 64) waves and its chunks dealt out evenly
-  bool merge;   // k_probe_even<.., MERGE>: neighbouring query rows share a round (term shards)
-  bool planes;  // k_probe_planes: two planes of 8-bit sums over the 16-bit rendering of <= 32768-row tiles, one barrier per round (acc8 is set too)
-};
-
-// k_probe_even's instantiations: (threads, window steps, shard rule, signed weights, 8-bit accumulators)
-#define APSS_EVEN_VARIANTS(X)          \
-  X(512, 7, false, false, false)       \
-  X(512, 6, false, false, false)       \
-  X(512, 5, false, false, false)       \
-  X(512, 4, false, false, false)       \
-  X(512, 3, false, false, false)       \
-  X(512, 2, false, false, false)       \
-  X(512, 7, true, false, false)        \
-  X(512, 6, true, false, false)        \
-  X(512, 5, true, false, false)        \
-  X(512, 4, true, false, false)        \
-  X(512, 3, true, false, false)        \
-  X(512, 2, true, false, false)        \
-  X(512, 7, true, false, true)         \
-  X(512, 6, true, false, true)         \
-  X(512, 5, true, false, true)         \
-  X(512, 4, true, false, true)         \
-  X(512, 3, true, false, true)         \
-  X(512, 2, true, false, true)         \
-  X(512, 4, false, false, true)        \
-  X(512, 3, false, false, true)        \
-  X(512, 2, false, false, true)        \
-  X(1024, 7, false, false, false)      \
-  X(1024, 6, false, false, false)      \
-  X(1024, 5, false, false, false)      \
-  X(1024, 3, false, false, false)      \
-  X(1024, 7, false, false, true)       \
-  X(1024, 6, false, false, true)       \
-  X(1024, 5, false, false, true)       \
-  X(1024, 3, false, false, true)
-// ... and with MERGE (shard rule, non-negative weights): (window steps, 8-bit accumulators)
-#define APSS_EVEN_MERGE_VARIANTS(X) \
-  X(7, false) X(6, false) X(5, false) X(4, false) X(3, false) X(2, false) \
-  X(7, true) X(6, true) X(5, true) X(4, true) X(3, true) X(2, true)
-// ... and with two planes of 8-bit sums (k_probe_planes): every window a plain 512-thread handle takes (2 .. 6 steps; 7 only
-// under APSS_DEBUG=even_wide, which keeps k_probe_even: at 7 steps the clears ahead of the adds cost the kernel 20 B of scratch)
-#define APSS_EVEN_PLANES_VARIANTS(X) X(6) X(5) X(4) X(3) X(2)
-
-// THE lookup: the instantiation of a variant (fn == null: not listed).  The only walk of the three tables
+// ---- the filter kernel's instantiations, in the order of the tables' walk (filter_variant_index, apss_filter_plan.hpp):
+// THE lookup of a variant's instantiation (fn == null: not listed)
 KernelRef cx_kernel(const CxVariant &v) {
-  const bool even_shape = v.chunk == 16 && !v.vrows && !v.longpf;  // (what every k_probe_even is built for)
-  if (v.even && v.planes) {
-#define X(U) \
-    if (v.block == 512 && v.u == U && !v.shard && !v.sgn && v.acc8 && !v.merge && even_shape) return {kernel_addr(&k_probe_planes<U>), 512};
-    APSS_EVEN_PLANES_VARIANTS(X)
+  static const KernelRef refs[] = {
+#define X(U) {kernel_addr(&k_probe_planes<U>), 512},
+      APSS_EVEN_PLANES_VARIANTS(X)
 #undef X
-    return {nullptr, 0};
-  }
-  if (v.even && v.merge) {
-#define X(U, A8) \
-    if (v.block == 512 && v.u == U && v.shard && !v.sgn && v.acc8 == A8 && even_shape) return {kernel_addr(&k_probe_even_merged<U, A8>), 512};
-    APSS_EVEN_MERGE_VARIANTS(X)
+#define X(U, A8) {kernel_addr(&k_probe_even_merged<U, A8>), 512},
+      APSS_EVEN_MERGE_VARIANTS(X)
 #undef X
-    return {nullptr, 0};
-  }
-  if (v.even) {
-#define X(B, U, SH, SG, A8) \
-    if (v.block == B && v.u == U && v.shard == SH && v.sgn == SG && v.acc8 == A8 && even_shape) \
-      return {kernel_addr(&k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>), B};
-    APSS_EVEN_VARIANTS(X)
+#define X(B, U, SH, SG, A8) {kernel_addr(&k_probe_even<B, U, (B <= 512 ? 128 : 256), SH, SG, A8>), B},
+      APSS_EVEN_VARIANTS(X)
 #undef X
-    return {nullptr, 0};
-  }
-#define X(B, U, SH, CH, VR, SG, LP, A8)                                                                                 \
-  if (v.block == B && v.u == U && v.shard == SH && v.chunk == CH && v.vrows == VR && v.sgn == SG && v.longpf == LP &&   \
-      v.acc8 == A8)                                                                                                     \
-    return {kernel_addr(&k_probe_coarse<B, U, (B <= 512 ? 128 : 256), (B <= 512 ? 512 : 1024), SH, CH, VR, SG, LP, A8>), B};
-  APSS_CX_VARIANTS(X)
+#define X(B, U, SH, CH, VR, SG, LP, A8) \
+  {kernel_addr(&k_probe_coarse<B, U, (B <= 512 ? 128 : 256), (B <= 512 ? 512 : 1024), SH, CH, VR, SG, LP, A8>), B},
+      APSS_CX_VARIANTS(X)
 #undef X
-  return {nullptr, 0};
+  };
+  const int i = filter_variant_index(v);
+  return i < 0 ? KernelRef{nullptr, 0} : refs[i];
 }
-inline bool cx_variant_exists(const CxVariant &v) { return cx_kernel(v).fn != nullptr; }
 
 // workgroups of a k_probe_even instantiation that the chip holds at a time: the occupancy query (the kernels' LDS is static,
 // so the query sees it: two per CU for the 512-thread ones, one for the 1024-thread ones) x the CUs; asked once per instantiation
@@ -1791,7 +1645,7 @@ int32_t even_resident_slots(apss_handle *h, const CxVariant &v, int *slots) {
   auto it = h->wl_per_cu.find(kern);
   if (it == h->wl_per_cu.end()) {
     int per_cu = 0;
-    HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, v.block, (size_t)h->dbgcfg.pad_lds));
+    HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, v.block, 0));
     it = h->wl_per_cu.emplace(kern, std::max(per_cu, 1)).first;
   }
   *slots = it->second * h->n_cus;
@@ -1799,12 +1653,12 @@ int32_t even_resident_slots(apss_handle *h, const CxVariant &v, int *slots) {
 }
 
 // persist_wgs > 0 (k_probe_even only): a.items holds the launch's work list and that many workgroups take its items
-// (the filter kernels keep their LDS in static arrays: the dynamic bytes are pad_lds's experiment, on k_probe_even alone)
+// (the filter kernels keep their LDS in static arrays: no dynamic bytes)
 int32_t launch_cx(apss_handle *h, const CxVariant &v, const ProbeArgs &a, int64_t persist_wgs = 0) {
   const KernelRef k = cx_kernel(v);
   if (!k.fn) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
   const dim3 grid((unsigned)(persist_wgs > 0 ? persist_wgs : (int64_t)a.n_tiles * a.n_chunks));
-  return launch_ref(h, k, grid, v.even ? (size_t)h->dbgcfg.pad_lds : 0, a);
+  return launch_ref(h, k, grid, 0, a);
 }
 
 // ---- dense-head filter of one query batch (apss_head.hpp): appends its candidates to the sparse filter's list ----
@@ -1925,143 +1779,6 @@ int32_t run_head(apss_handle *h, const ProbeArgs &a, int64_t nq, int64_t q_slot_
 // ---- probe the whole index with a query batch resident on the device ----
 // q_head: rows of the batch in the dense-head block (null when the handle has none): the store's W for a stored batch,
 // the staged q_W otherwise.
-// What a probe knows when it picks the filter kernel's instantiation (plan_filter)
-struct FilterFacts {
-  bool acc8;         // this call's norms and row lengths leave room for 8-bit sums over the handle's >= 65536-row tiles
-  bool shard_rule;   // term shard, or the sparse half of a handle with a dense-head block
-  bool sgn;          // weights of either sign: the filter sums the positive products
-  bool hybrid;       // the handle has a dense-head block
-  int64_t s_max_nnz, s_nnz_end;  // longest staged query row, elements staged
-  int64_t nq, idx_nnz;           // query rows, postings in the inverted index
-  int max_merge_log2;            // k_probe_even: up to 2^this query rows may share a round (0: none)
-  double planes_scale;           // k_probe_planes: units per 1.0 at which this call's sums fit a byte (acc8_scale; 0: they do not)
-};
-
-// ---- which instantiation of the filter kernel: the register window (U steps of 8 chunks per wave) is sized for the
-// chunks a wave expects per round; a round's cost grows with U whether or not its slots hold postings, so thin rounds
-// (term shards: 1/T of a query's terms; sparse regimes: short segments) take a short window
-// Pure host arithmetic on what ingest and the index build measured; the choice is reported in apss_stats.probe_kernel.
-int32_t plan_filter(apss_handle *h, const FilterFacts &f, CxVariant &cxv, ProbeArgs &a) {
-  const DebugCfg &dbg = h->dbgcfg;
-  cxv.acc8 = f.acc8;
-  cxv.block = h->cx.cb > 65536 || (h->cx.cb > 32768 && !cxv.acc8) ? 1024 : 512;
-  cxv.shard = f.shard_rule;
-  cxv.chunk = dbg.chunk8 ? 8 : 16;
-  cxv.vrows = f.s_max_nnz > 512;
-  cxv.sgn = f.sgn;
-  const double nw = cxv.block / kWave;
-  const double seg = (double)h->cx.cb * ((double)f.idx_nnz / (double)h->n_rows) / (double)h->cfg.dim;  // postings per (tile, term)
-  double q_terms = (double)f.s_nnz_end / (double)f.nq;
-  // a shard holds a binomial share of each query's terms; a window that overflows costs a whole-tile clear, so the
-  // shard-rule launches size it for the upper end (3 sigma) and for segments one chunk longer than their mean
-  const double t_hi = f.shard_rule ? q_terms + 3.0 * std::sqrt(q_terms) : q_terms;
-  const double wave_chunks = std::ceil(t_hi / nw - 1e-9) * std::max(1.0, seg / 16.0 + (f.shard_rule ? 1.0 : 0.5));
-  int u = (int)std::ceil(wave_chunks * (f.shard_rule ? 1.0 : 1.05) / 8.0);
-  if (cxv.block == 1024) u = (q_terms / nw) * std::max(1.0, seg / 16.0 + 0.5) <= 17.0 && !dbg.big_u5 ? 3 : 5;
-  else u = std::max(2, std::min(5, u));
-  if (cxv.vrows || cxv.sgn) u = cxv.block == 1024 ? u : 5;
-  if (dbg.chunk8) u = 4;
-  if (dbg.window && cxv.block == 512 && !cxv.vrows && !cxv.sgn) u = dbg.window;
-  // the skewed tail of a handle with a dense-head block: full window, prefetched long sweeps.  (A term shard's tail range
-  // may hold no long segment at all once the block has taken the frequent terms: it then runs like any other shard)
-  const bool long_tail = f.hybrid && h->cx.max_seg > (uint32_t)kLongLenW && !cxv.acc8;
-  if (long_tail && !dbg.window) {
-    u = 5;
-    cxv.longpf = true;
-  }
-  if (cxv.vrows && cxv.shard && !cxv.sgn) {  // long rows (real TF-IDF) on a term shard: the shard-rule instantiation that takes virtual rows
-    u = 5;
-    cxv.longpf = true;
-  }
-  if (dbg.longpf && cxv.block == 512 && !cxv.vrows && !cxv.sgn && !cxv.acc8) {
-    u = 5;
-    cxv.longpf = true;
-  }
-  cxv.u = u;
-  // k_probe_even (apss_even.hpp): F waves stage the round, the others add an even share of its chunks -- a wave's window
-  // then holds a 1/A share of the ROUND's chunks, not the chunks of the wave's own terms.
-  // Staging lanes per term: as many as keep the staging waves at <= a quarter of the workgroup.
-  // Where it is taken (measured on C3 and its shards, ms of the filter kernel, k_probe_even vs k_probe_coarse): term shards
-  // T = 8: 23.4 vs 40.5, T = 4: 35.6 vs 62.4, T = 2 (one staging lane per term, 7-step windows): 58.7 vs 77.9; the sparse
-  // regime's 1024-thread kernel (C5's shape at a fifth of N): 218.2 vs 291.5; the plain handle of C3 itself (100-term rows,
-  // LDS-throughput-bound): 100.6 vs 111.3 with six adding waves x 6 steps, 115.4 with 7 steps -- a plain 512-thread handle
-  // takes it when its adding waves issue no more window steps per round than k_probe_coarse's eight would.
-  const bool wide_ok = f.shard_rule || cxv.block == 1024 || dbg.even_wide;
-  // (not where long segments abound -- more than 16 long terms per tile: the thin-round kernel sweeps them on its rare
-  // path, meant for one round in a few.  C3 with Zipf(0.5) terms, ~400 long terms per tile and half a dozen in every round,
-  // measured 1395 ms there against 518 ms on k_probe_coarse)
-  const bool few_longs = (double)h->cx.long_segs <= 16.0 * (double)std::max<int64_t>(1, h->cx.n_tiles) || f.shard_rule || cxv.block == 1024;
-  // MERGED rounds (apss_even.hpp): M = 2^m neighbouring query rows staged as one row, when a single query's round is thin (a
-  // window of <= 4 steps) and the merged round still fits a window; the caller says how many the accumulators have room for
-  a.merge_log2 = 0;
-  int ue_single = 0;
-  for (int m = 0; m <= f.max_merge_log2; ++m) {
-    const int64_t M = 1LL << m;
-    const int64_t row_max = std::min<int64_t>(f.s_max_nnz * M, f.s_nnz_end);  // longest staged row: at most M of the longest
-    int flat_group_log2 = 2;
-    while (flat_group_log2 > 0 && ceil_div(row_max, kWave >> flat_group_log2) > (int64_t)nw / 4) --flat_group_log2;
-    if (dbg.flat_group >= 0 && dbg.flat_group < flat_group_log2) flat_group_log2 = dbg.flat_group;
-    const int64_t flat_waves = std::max<int64_t>(1, ceil_div(row_max, kWave >> flat_group_log2));
-    if (!(!cxv.vrows && !cxv.longpf && cxv.chunk == 16 && !dbg.no_even && !dbg.window && flat_waves <= (int64_t)nw / 4 && few_longs)) break;
-    CxVariant ev = cxv;
-    ev.even = true;
-    ev.merge = m > 0;
-    const double add_waves = nw - (double)flat_waves;               // a wave that stages a round adds nothing in it
-    // postings per (tile, term) over the terms this handle indexes (a term shard: its range, not the whole dimension)
-    const double seg_here = seg * (double)h->cfg.dim / (double)std::max<int64_t>(1, (int64_t)h->cfg.term_hi - h->cfg.term_lo);
-    const double cpt = std::max(1.0, seg_here / 16.0 + 0.5);      // chunks per term
-    const double mq_terms = q_terms * (double)M;                    // terms of a round
-    // (mean + 2 sigma of a binomial share of the terms: the rounds beyond read their last chunks from the strip and end
-    // with a whole-tile clear, ~2 % of them; at 3 sigma the T = 8 shard took a 3-step window: 24.8 vs 23.2 ms)
-    double round_chunks = mq_terms * cpt + 2.0 * std::sqrt(mq_terms * cpt * cpt + mq_terms * 0.3);
-    // ... that is the uniform-terms estimate; the index build MEASURED what an average stored row deals out per tile
-    // (sum over terms of P(term in the row) x chunks of its segment): under a skewed distribution the terms a query holds
-    // are the ones with the long segments, and the estimate above falls short by a factor (power-law C5's tail: 85
-    // estimated, 200 dealt out: most rounds overflowed their window, a whole-tile clear each)
-    if (h->cx.round_chunks > 0.0) {
-      const double rc = h->cx.round_chunks * (double)M;
-      const double per_term = std::max(1.0, rc / std::max(1.0, mq_terms));
-      round_chunks = std::max(round_chunks, rc + 2.0 * std::sqrt(rc * per_term));
-    }
-    // (a plain handle's rows are whole rows: no binomial share of the terms; the longest row bounds the round)
-    if (!f.shard_rule) round_chunks = std::min(round_chunks, 1.05 * (double)f.s_max_nnz * cpt);
-    int ue = (int)std::ceil(round_chunks / (8.0 * add_waves));
-    // (a window that overflows most rounds pays a whole-tile clear each time)
-    const bool fits = ue <= 7 && !cxv.sgn && (wide_ok || add_waves * std::max(2, ue) <= nw * (double)cxv.u);
-    ue = cxv.block == 1024 ? (ue <= 3 ? 3 : std::max(5, ue)) : std::max(2, ue);
-    ev.u = ue;
-    if (dbg.diag)
-      fprintf(stderr, "[apss diag] even? merge %lld block %d u %d | F %lld G %d A %.0f chunks %.1f ue %d fits %d exists %d q_max %lld q_terms %.1f seg %.1f\n",
-              (long long)M, cxv.block, cxv.u, (long long)flat_waves, 1 << flat_group_log2, add_waves, round_chunks, ue, (int)fits,
-              (int)cx_variant_exists(ev), (long long)f.s_max_nnz, q_terms, seg);
-    if (m == 0) ue_single = ue;
-    if (!(fits && cx_variant_exists(ev))) break;
-    // (measured on C3's shards, filter kernel: T = 8, window 2 -> 4 steps: 13.1 -> 11.1 ms; T = 4, 4 -> 7 steps: 19.9 -> 17.3 ms; T = 2
-    // needs its 7 steps for one row.  FOUR rows per round at T = 8, 7 steps and 2^5 units per 1.0: 10.6 ms but 6.5 x the
-    // candidates for the exchange -- not by default, APSS_DEBUG=merge=2)
-    if (m > 0 && !(ue_single <= (dbg.merge_single > 0 ? dbg.merge_single : 4) && ue <= (dbg.merge_u > 0 ? dbg.merge_u : 7))) break;
-    cxv = ev;
-    a.flat_waves = (int32_t)flat_waves;
-    a.flat_group_log2 = flat_group_log2;
-    a.merge_log2 = m;
-  }
-  // TWO PLANES (apss_even.hpp): exactly where the plain 512-thread k_probe_even is taken -- same U, F and work list, the
-  // same 16-bit rendering of the index -- when the tiles fit a plane and this call's norms and row lengths leave room for byte
-  // sums; the caller launches it on the 8-bit scale.  A launch that turns out unselective latches the handle back (drop_planes).
-  // Only for query chunks of kPlanesMinChunk rounds or more: what the kernel saves, it saves per round, and what two planes cost
-  // they cost per item.  Measured (profiles/even_planes.md): the whole-store join of C3, chunks of 977 rounds (the last items
-  // in pieces of 128): filter kernel -2.2 %; C3 streamed in batches of 16,384 rows, chunks of 16 to 124 rounds: +0.6 %.
-  constexpr int kPlanesMinChunk = 256;
-  if (cxv.even && !cxv.merge && cxv.block == 512 && !cxv.shard && !cxv.sgn && !cxv.acc8 && h->cx.cb <= 32768 && f.planes_scale > 0 &&
-      (a.q_chunk >= kPlanesMinChunk || dbg.planes) && !dbg.no_planes && !dbg.no_acc8 && !h->no_acc8) {
-    CxVariant pv = cxv;
-    pv.acc8 = pv.planes = true;
-    if (cx_variant_exists(pv)) cxv = pv;
-  }
-  if (!cx_variant_exists(cxv)) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
-  return APSS_OK;
-}
-
 // Queries of more terms than a round of the filter takes (512) are cut into parts that share the accumulators: part v covers
 // elements vrow_ptr[v] .. vrow_ptr[v + 1]) of query vrow_q[v]; vq_first[q] is query q's first part.
 int32_t cut_long_queries(apss_handle *h, const int64_t *s_rowptr, int64_t nq, int vrow_part, ProbeArgs &a) {
@@ -2182,6 +1899,7 @@ struct ProbePath {
   int mode;
   bool forced_general;
   double cx_shared, cx_scale, cx_theta, a8_scale;  // (cx_scale as launched: a8_scale when that is > 0; cx_theta: theta in its units)
+  double byte_scale;  // acc8_scale of this call's norms and row lengths (0: its sums do not fit a byte): a8_scale where the tiles take 8-bit sums, k_probe_planes' scale
   bool coarse_path, cx_signed, shard_rule, hybrid, head_outside;
   float head_thr;
   int64_t tail_n, q_slot_base;
@@ -2295,12 +2013,10 @@ int32_t choose_path(apss_handle *h, Probe &pr) {
   // S = the largest power of two that fits (2^15 for unit-norm input); un-normalised input gets a smaller one as long as
   // the threshold in units stays well above the round-up bias (one unit per shared term), else the filter passes too much
   const double cx_shared = p.cx_shared = (double)std::min<int64_t>(pr.s.max_nnz, pr.s.c_max_nnz);
-  const double cx_room = 65535.0 - cx_shared;
-  double cx_scale = 0.0;
-  for (int k = 15; k >= 4 && cx_scale == 0.0; --k)
-    if (bound * 1.0005 * std::ldexp(1.0, k) < cx_room) cx_scale = std::ldexp(1.0, k);
-  const double cx_theta = std::floor(theta * cx_scale * (1.0 - 1.0 / 2048 - 1e-6));
-  const bool cx_selective = cx_scale >= 16384.0 || cx_theta >= 4.0 * cx_shared;
+  const Scale16 s16 = acc16_scale(bound, cx_shared, theta);
+  double cx_scale = s16.scale;
+  const double cx_theta = filter_threshold(theta, cx_scale);
+  const bool cx_selective = s16.selective;
   const bool cx_fp16_ok = std::sqrt((double)h->store_max_norm2) < 60000.0;  // a weight never exceeds its row's norm
   // the shard rule (term-range shards, and the sparse half of a handle with a dense-head block) scales the threshold
   // down per query and tile: the kernel clamps it at 1, which only admits more
@@ -2311,17 +2027,17 @@ int32_t choose_path(apss_handle *h, Probe &pr) {
   // dense-head block (and long queries over 65536-row tiles) has no such instantiation and keeps the general kernel
   const bool shard_rule = p.shard_rule = h->sharded || hybrid_wanted;
   p.cx_signed = p.mode == 1 && !(h->cfg.flags & APSS_FLAG_FORCE_SCAN) && !hybrid_wanted &&
-                (h->cx.cb <= 32768 || pr.s.max_nnz <= 512) && !h->dbgcfg.chunk8 && !h->dbgcfg.window;
+                (h->cx.cb <= 32768 || pr.s.max_nnz <= 512) && !h->dbgcfg.filter.chunk8 && !h->dbgcfg.filter.window;
   // 65536-row tiles (term shards; the sparse regime of a plain handle): the 8-bit filter -- 65536 candidates in 64 KB, two
   // 512-thread workgroups per CU -- if this call's norms and row lengths leave room for its sums
   const bool big_shard_tiles = shard_rule && h->cx.cb > 32768;
-  const double a8_scale = p.a8_scale = h->cx.cb >= 65536 && p.mode == 0 && pr.s.max_nnz <= 512 && !h->dbgcfg.no_acc8 && !h->no_acc8 && !h->dbgcfg.chunk8
-                                           ? acc8_scale(bound, cx_shared, theta) : 0.0;
+  p.byte_scale = p.mode == 0 && pr.s.max_nnz <= 512 ? acc8_scale(bound, cx_shared, theta) : 0.0;
+  const double a8_scale = p.a8_scale = h->cx.cb >= 65536 && !h->dbgcfg.filter.no_acc8 && !h->no_acc8 && !h->dbgcfg.filter.chunk8 ? p.byte_scale : 0.0;
   // not this time (a long row, a large norm, signed weights): back to 16-bit accumulators over smaller tiles, for good
   if ((big_shard_tiles || h->cx.cb > 65536) && !(a8_scale > 0)) return drop_acc8(h, shard_rule);
   if (a8_scale > 0) cx_scale = a8_scale;
   p.cx_scale = cx_scale;
-  p.cx_theta = std::floor(theta * cx_scale * (1.0 - 1.0 / 2048 - 1e-6));
+  p.cx_theta = filter_threshold(theta, cx_scale);
   p.coarse_path = h->use_coarse && (p.mode == 0 || p.cx_signed) && (cx_selective || a8_scale > 0) && cx_fp16_ok && !p.forced_general && pr.q.nq < (1LL << 30) &&
                   !(shard_rule && h->cx.cb > 32768 && !(a8_scale > 0)) &&
                   !h->dbgcfg.exact_accum && cx_scale > 0 && cx_theta < 65000.0 && (shard_rule || cx_theta - 2 >= 1.0) &&
@@ -2357,20 +2073,6 @@ int32_t choose_path(apss_handle *h, Probe &pr) {
   if (p.hybrid && (p.q_slot_base < 0 || p.head_outside) && !h->sharded) APSS_TRY(pack_query_head(h, pr.q.rowptr, pr.q.idx, pr.q.val, pr.q.nq));  // (a shard's ingest packed them)
   p.q_sub = !shard_rule ? nullptr : (p.q_slot_base >= 0 ? h->sub.p + p.q_slot_base : h->q_sub.p);
   return APSS_OK;
-}
-
-// MERGED rounds (a term shard's thin rounds, apss_even.hpp): M neighbouring query rows share a round, their M filter sums one
-// accumulator -- which then has to hold M sums: the scale for M rows is the scale of one row with M times the norm bound and
-// M times the shared terms.  How many rows the accumulators have room for (plan_filter decides how many a window has):
-double merged_scale(const ProbePath &p, int m) {
-  const double Mx = (double)(1 << m);
-  if (p.a8_scale > 0) return acc8_scale(p.bound * Mx, p.cx_shared * Mx, p.theta);
-  for (int k = 15; k >= 4; --k) {
-    const double S = std::ldexp(1.0, k);
-    if (p.bound * Mx * 1.0005 * S < 65535.0 - p.cx_shared * Mx)
-      return S >= 16384.0 || std::floor(p.theta * S * (1.0 - 1.0 / 2048 - 1e-6)) >= 4.0 * p.cx_shared * Mx ? S : 0.0;
-  }
-  return 0.0;
 }
 
 // the kernels' arguments but the candidate list: store, staged rows, query chunks, the index rendering of the path
@@ -2459,36 +2161,33 @@ int32_t choose_exact_kernel(apss_handle *h, Probe &pr) {
   return APSS_OK;
 }
 
-// The filter kernel's instantiation (plan_filter), with as many query rows per round as the accumulators have room for AND
-// the filter stays SELECTIVE with: a chance pair collects about 1 / t of the threshold's scale per shared term
-// (t = terms of a row inside this shard), and a round of M rows hits a given candidate M t^2 / R times on average (R = terms
-// of the range).  Rows of a dozen terms over thousands of terms (C3's shards: t = 12.5, R = 12500): a chance candidate is
-// hit once, by one row.  Rows of three or four terms over a few hundred: three chance hits from different rows of a round
-// cross the threshold (measured: 8 x more candidates than unmerged) -- not there.  A fuse behind the estimate: a merged
-// launch that reports more than two rounds per query row turns merging off for the handle (merge_off).
+// The filter kernel's instantiation (plan_filter, apss_filter_plan.hpp), with as many query rows per round as merge_rows_log2
+// allows.  A fuse behind its estimate: a merged launch that reports more than two rounds per query row turns merging off for
+// the handle (merge_off).
 // (Term shards only, with or without a dense-head block -- power-law C5's 8 x 1 shard at N = 2M: tail filter 39.5 -> 24.0 ms.  The
 // sparse half of a PLAIN handle with a block was tried: its rounds take 4-5 window steps, two rows do not fit one window.)
 int32_t plan_merged_rounds(apss_handle *h, Probe &pr) {
-  const double t_shard = (double)pr.s.nnz_end / (double)std::max<int64_t>(pr.q.nq, 1);
-  const double r_shard = (double)std::max<int64_t>(1, (int64_t)h->cfg.term_hi - h->cfg.term_lo);
-  int max_merge_log2 = 0;
-  if (pr.p.coarse_path && h->sharded && pr.p.mode == 0 && !pr.p.cx_signed && h->dbgcfg.merge != 0 && !h->merge_off && t_shard >= 8.0)
-    while (max_merge_log2 < (h->dbgcfg.merge > 0 ? std::min(h->dbgcfg.merge, 2) : 1) && (pr.q.nq >> (max_merge_log2 + 1)) >= 1 &&
-           (double)(2 << max_merge_log2) * t_shard * t_shard <= 0.25 * r_shard && merged_scale(pr.p, max_merge_log2 + 1) > 0)
-      ++max_merge_log2;
+  const ProbePath &p = pr.p;
+  const FilterHooks &hooks = h->dbgcfg.filter;
   pr.cxv = CxVariant{};
-  if (pr.p.coarse_path)
-    APSS_TRY(plan_filter(h, FilterFacts{pr.p.a8_scale > 0, pr.p.shard_rule, pr.p.cx_signed, pr.p.hybrid, pr.s.max_nnz, pr.s.nnz_end, pr.q.nq, pr.s.idx_nnz, max_merge_log2,
-                                             pr.p.mode == 0 && pr.s.max_nnz <= 512 ? acc8_scale(pr.p.bound, pr.p.cx_shared, pr.p.theta) : 0.0}, pr.cxv, pr.a));
-  if (pr.cxv.planes) {  // (the threshold in the units of byte sums, as a term shard's 8-bit filter takes it)
-    const double S = acc8_scale(pr.p.bound, pr.p.cx_shared, pr.p.theta);
+  if (!p.coarse_path) return APSS_OK;
+  const int max_merge_log2 = h->sharded && p.mode == 0 && !p.cx_signed && !h->merge_off
+                                 ? merge_rows_log2(pr.q.nq, pr.s.nnz_end, h->cfg.term_lo, h->cfg.term_hi, p.a8_scale > 0, p.bound, p.cx_shared, p.theta, hooks) : 0;
+  const FilterFacts f{p.a8_scale > 0, p.shard_rule, p.cx_signed, p.hybrid, pr.s.max_nnz, pr.s.nnz_end, pr.q.nq, pr.s.idx_nnz, max_merge_log2, p.byte_scale, pr.a.q_chunk,
+                      h->cx.cb, h->cx.max_seg, h->cx.long_segs, h->cx.n_tiles, h->cx.round_chunks, h->n_rows, h->cfg.dim, h->cfg.term_lo, h->cfg.term_hi, h->no_acc8};
+  std::string diag;
+  const FilterPlan plan = plan_filter(f, hooks, h->dbgcfg.diag ? &diag : nullptr);
+  if (!diag.empty()) fputs(diag.c_str(), stderr);
+  if (!plan.listed) return fail(h, APSS_E_UNSUPPORTED, "no filter kernel for this combination of options");
+  pr.cxv = plan.v;
+  pr.a.flat_waves = plan.flat_waves;
+  pr.a.flat_group_log2 = plan.flat_group_log2;
+  pr.a.merge_log2 = plan.merge_log2;
+  // the threshold in the units of byte sums (two planes: as a term shard's 8-bit filter takes it) or of a round's M rows
+  if (plan.v.planes || plan.merge_log2 > 0) {
+    const double S = plan.v.planes ? p.byte_scale : merged_scale(p.a8_scale > 0, p.bound, p.cx_shared, p.theta, plan.merge_log2);
     pr.a.cx_scale = (float)S;
-    pr.a.cx_theta = (float)std::floor(pr.p.theta * S * (1.0 - 1.0 / 2048 - 1e-6));
-  }
-  if (pr.a.merge_log2 > 0) {
-    const double S = merged_scale(pr.p, pr.a.merge_log2);
-    pr.a.cx_scale = (float)S;
-    pr.a.cx_theta = (float)std::floor(pr.p.theta * S * (1.0 - 1.0 / 2048 - 1e-6));
+    pr.a.cx_theta = (float)filter_threshold(p.theta, S);
   }
   return APSS_OK;
 }
@@ -3445,7 +3144,7 @@ int32_t clear_impl(apss_handle *h) {
   forget_last_call(h);
   h->nonneg = true;
   h->q_nonneg = true;
-  h->no_acc8 = h->dbgcfg.no_acc8;
+  h->no_acc8 = h->dbgcfg.filter.no_acc8;
   h->merge_off = false;
   h->downgrades = 0;
   h->store_max_nnz = 0;
@@ -3827,7 +3526,7 @@ int32_t apss_create(const apss_config *cfg, apss_handle **out) {
   h->ex.align = kSegAlign;
   h->cx.cb = std::min(2 * h->cb, 32768);
   if (h->dbgcfg.cx_tile) h->cx.cb = h->dbgcfg.cx_tile;  // experiment hook (multiple of 64, <= 65536)
-  h->no_acc8 = h->dbgcfg.no_acc8;
+  h->no_acc8 = h->dbgcfg.filter.no_acc8;
   if (h->dbgcfg.fold_w == 128 || h->dbgcfg.fold_w == 256) {  // experiment: two blocks
     h->head_exact = 256;
     h->head_fold_w = h->dbgcfg.fold_w;

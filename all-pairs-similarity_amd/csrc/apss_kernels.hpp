@@ -18,12 +18,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "apss_filter_plan.hpp"
 #include "apss_topk_key.hpp"
 #include "apss_worklist.hpp"
 
 namespace apss {
 
-constexpr int kWave = 64;          // CDNA wavefront
+// (kWave, the CDNA wavefront, and kLongLenW are in apss_filter_plan.hpp: the host rule that sizes the filter reads them too)
 constexpr int kGroup = 16;         // lanes that share one short-segment work item (16 x 8 B = one 128-B line)
 constexpr int kItemCap = 2048;     // short-segment work items per round held in LDS
 constexpr int kLongCap = 256;      // long segments per round held in LDS
@@ -1103,7 +1104,6 @@ __global__ __launch_bounds__(BLOCK) void k_probe(const ProbeArgs a) {
 //     still in registers): LDS traffic proportional to posting visits, not to the tile size.  Rounds that
 //     overflow the register window or sweep a long segment fall back to clearing the tile.
 constexpr int kChunk = 8;        // postings per chunk: 8 lanes x 8 B = 64 B
-constexpr int kLongLenW = 256;   // longer segments are swept by the whole workgroup
 
 __host__ __device__ inline size_t probe_wave_lds_bytes(int cb, int block, int u, int longcap, int survcap) {
   return ((size_t)(cb + kWave) * 4 + (size_t)(block / kWave) * (kWave / kChunk) * u * 8 + 3 * (size_t)longcap * 12 +
